@@ -5,15 +5,20 @@ A "step" = one pass of the hot path (ORBextractor::operator(): pyramid -> FAST+N
 IC-angle -> rBRIEF) over one batch of synthetic KITTI-00-like stereo pairs (1241x376, 2000 features/frame),
 inputs already resident in HBM.  value = keypoints returned per second, whole job.
 
-  python bench.py --gpus N --steps K --warmup W [--pairs B]
+  python bench.py --gpus N --steps K --warmup W [--pairs B] [--dump-outputs DIR] [--full]
 
 N=1: both eyes of every pair on the one GPU.  N>1 (launched by torch.distributed.run, one rank per GPU):
 stereo left/right split — even ranks extract the left eyes, odd ranks the right eyes of their pair group,
 then the odd rank sends counts/keypoints/descriptors to its even partner over RCCL (xGMI point-to-point);
 per-GPU work is fixed (weak scaling).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed) and `cpu_baseline`
-(the CPU oracle timed on a bounded sample of the same workload on this box's host cores).
+Prints ONE JSON line on rank 0.  A plain run does what the headline `value` / `ms_per_step` need: set-up, the
+per-stage timing the two batches' offset is derived from (also the source of `stage_ms_per_step` and `roofline`:
+dominant kernel, HIP-event timed), warm-up, the timed steps.  `--full` adds the measurements and checks of their
+own: the roofline's traffic by live rocprofv3 --pmc passes, `cpu_baseline` (the CPU oracle timed on a bounded
+sample of the same workload on the host's cores), the Hamming / stereo / tracking / per-frame / host-fed /
+density / 4Seasons / sparsification legs and, at N>1, the split's self-validation.  `--dump-outputs DIR` writes
+what the last timed step returned (see dump_outputs).
 """
 import argparse
 import json
@@ -39,13 +44,46 @@ from bench_legs.split import split_self_validation  # noqa: E402
 from bench_legs.stereo import stereo_leg  # noqa: E402
 from bench_legs.tracking import reference_keyframe_leg, tracking_cpu_leg, tracking_loop_leg  # noqa: E402
 
+DUMP_BUDGET = 60_000_000   # bytes of array data --dump-outputs may write (the contract allows 64 MB in all, .npy headers included)
+
+
+def dump_outputs(path, counts, mono, d_kps, d_desc):
+    """--dump-outputs: what the caller of the timed path receives for one batch, as .npy files in `path`, so that two builds
+    can be compared output for output.  counts / mono: per image (float64).  keypoints: one row per returned keypoint, image
+    by image in the returned order — x, y, size, angle, response, octave, class_id (float32, exact).  descriptors: the same
+    rows, each 256-bit descriptor as eight little-endian 32-bit words (float64, exact).  If the rows exceed DUMP_BUDGET, a
+    fixed seeded sample of them is written, sorted, and keypoint_index.npy holds the row numbers it kept."""
+    import msorb
+    os.makedirs(path, exist_ok=True)
+    counts = np.asarray(counts, np.int64)
+    kps, desc = d_kps.cpu().numpy(), d_desc.cpu().numpy()
+    kp = np.concatenate([kps[i, :c] for i, c in enumerate(counts)]).reshape(-1).view(msorb.KP_DTYPE)
+    words = np.concatenate([desc[i, :c] for i, c in enumerate(counts)]).reshape(-1).view("<u4").reshape(-1, 8)
+    out = {"counts": counts.astype(np.float64), "mono": np.asarray(mono, np.float64)}
+    row_bytes = 4 * len(msorb.KP_DTYPE.names) + 8 * 8
+    fixed = sum(a.nbytes for a in out.values())
+    if fixed + len(kp) * row_bytes > DUMP_BUDGET:
+        keep = (DUMP_BUDGET - fixed) // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(kp), keep, replace=False))
+        kp, words = kp[idx], words[idx]
+        out["keypoint_index"] = idx.astype(np.float64)
+    out["keypoints"] = np.stack([kp[f].astype(np.float32) for f in msorb.KP_DTYPE.names], axis=1)
+    out["descriptors"] = words.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--pairs", type=int, default=128, help="stereo pairs per step per GPU-pair group")
-    ap.add_argument("--cpu-pairs", type=int, default=160, help="stereo pairs in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and checks: live PMC traffic, CPU baselines, the other legs, the N>1 "
+                         "self-validation")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-pairs", type=int, default=160, help="stereo pairs in the CPU baseline sample (0 = skip; --full only)")
     ap.add_argument("--unique-pairs", type=int, default=8, help="distinct synthetic stereo pairs tiled to the batch (<= --pairs)")
     ap.add_argument("--lean", action="store_true",
                     help="profiling aid: only the extraction loop (no Hamming / stereo / tracking / per-frame / host-fed / sparsification "
@@ -55,7 +93,7 @@ def main():
                     help="profiling aid: no sub-batch / blur overlap anywhere, so every kernel launch covers the whole "
                          "batch and runs alone (rocprofv3 per-kernel durations and PMC traffic are then per-launch clean)")
     args = ap.parse_args()
-    if args.lean:
+    if args.lean or not args.full:
         args.cpu_pairs = 0
 
     import torch
@@ -190,6 +228,7 @@ def main():
     fence_kp = [0]
     filled = [False, False]
     last_ex = [ex]
+    last_out = [None]   # (counts, mono, d_keypoints, d_desc) of the batch that completed last: what --dump-outputs writes
     all_ex = [ex] if exs[1] is ex else [exs[0], exs[1]]
 
     def associate(b):
@@ -242,22 +281,22 @@ def main():
         total = 0
         refill[0] = True
         while inflight:
-            counts, _, _, _ = inflight.pop(0).extract_batch_wait()
-            total += int(counts.sum())
+            last_out[0] = inflight.pop(0).extract_batch_wait()
+            total += int(last_out[0][0].sum())
         return total
 
     def step():
         if world == 1:
             if not mode["pipelined"]:
-                counts, mono, _, _ = ex.extract_batch(images, (0, 0), out=(d_kps, d_desc))
+                last_out[0] = ex.extract_batch(images, (0, 0), out=(d_kps, d_desc))
                 last_ex[0] = ex
-                return int(counts.sum())
+                return int(last_out[0][0].sum())
             k = step_no[0] % depth
             step_no[0] += 1
             done = 0
             if len(inflight) == depth:  # handle k still holds the batch submitted `depth` steps ago
-                counts, _, _, _ = inflight.pop(0).extract_batch_wait()
-                done = int(counts.sum())
+                last_out[0] = inflight.pop(0).extract_batch_wait()
+                done = int(last_out[0][0].sum())
             exp[k].extract_batch_submit(images, (0, 0), out=outs[k])
             inflight.append(exp[k])
             if len(inflight) == depth:
@@ -273,7 +312,8 @@ def main():
         associate(b)                              # ... and its pairs are joined before block / handle are reused
         if mode["sync_nccl"]:                     # stage timings: one batch at a time
             last_ex[0] = exs[b]
-            counts, mono, _, _ = exs[b].extract_batch(images, (0, 0), out=(mine[b].kps, mine[b].desc))
+            last_out[0] = exs[b].extract_batch(images, (0, 0), out=(mine[b].kps, mine[b].desc))
+            counts = last_out[0][0]
             ship(b, counts)
             return int(counts.sum())
         # two batches in flight, as at N = 1: this step's extraction is enqueued (the extractor writes straight into the send
@@ -291,7 +331,8 @@ def main():
     def collect(b):
         if not submitted[b]:
             return 0
-        counts, _, _, _ = exs[b].extract_batch_wait()
+        last_out[0] = exs[b].extract_batch_wait()
+        counts = last_out[0][0]
         submitted[b] = False
         last_ex[0] = exs[b]
         ship(b, counts)
@@ -317,7 +358,7 @@ def main():
     # second half of the metric: Gpairs/s of the brute-force Hamming match (left-eye descriptors of every pair
     # against the right-eye descriptors of the same pair, dense top-2), on the descriptors just extracted
     hamming = ham_ctx = None
-    aux = world == 1 and not args.lean
+    aux = world == 1 and args.full and not args.lean
     counts_h = None
     if aux:
         counts_h, _, _, _ = ex.extract_batch(images, (0, 0), out=(d_kps, d_desc))
@@ -420,6 +461,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         dt, kp_total = float(tmax[0]), int(t[1])
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_out[0])
+
     if aux and not args.isolated:
         hf_ex = [ex, make_ex()]
         all_ex.append(hf_ex[1])
@@ -435,7 +479,7 @@ def main():
                                    exp[:2] if world == 1 and pipelined and len(exp) >= 2 and same_params else None)
 
     validation = None
-    if world > 1:
+    if world > 1 and args.full:
         validation = split_self_validation(msorb, torch, dist, stereo_split, rank, world, eye, half, exs[0], ex_rp, make_ex, images,
                                            other_images, mine[0], theirs[0], kp_total_rank / dt_rank if dt_rank > 0 else 0.0, dev,
                                            rank_keypoints_per_step=int(round(kp_total_rank / max(args.steps, 1))))

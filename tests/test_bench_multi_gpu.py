@@ -2,12 +2,13 @@
 loop — two ranks launched by torch.distributed.run, one eye each, half-swap of the feature blocks, split association,
 self-validation — with both ranks on cuda:0 and gloo carrying the exchange (MSORB_DIST_BACKEND=gloo); the RCCL launch itself
 failing loudly and early on a box with fewer GPUs than ranks (on a box with >= 2 GPUs the same test runs the real RCCL path);
-and the bench line surviving a failing optional leg."""
+the bench line surviving a failing optional leg (all three with --full); and the plain run's line and --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,7 +36,7 @@ def _launch(n, port, extra, env, timeout=600):
 
 def test_bench_two_ranks_share_one_gpu_over_gloo():
     port = 29000 + os.getpid() % 2000
-    p = _launch(2, port, ["--pairs", "16", "--steps", "4", "--warmup", "2"], _env(MSORB_DIST_BACKEND="gloo"))
+    p = _launch(2, port, ["--pairs", "16", "--steps", "4", "--warmup", "2", "--full"], _env(MSORB_DIST_BACKEND="gloo"))
     assert p.returncode == 0, p.stderr[-3000:]
     out = _last_json(p.stdout)
     assert out["n_gpus"] == 2 and out["steps"] == 4 and out["value"] > 0 and out["scaling"] == "weak"
@@ -57,7 +58,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
 def test_bench_rccl_launch_is_a_number_or_a_diagnosis():
     import torch
     port = 31000 + os.getpid() % 2000
-    p = _launch(2, port, ["--pairs", "8", "--steps", "3", "--warmup", "1"], _env(MSORB_DIST_TIMEOUT_S="60"), timeout=400)
+    p = _launch(2, port, ["--pairs", "8", "--steps", "3", "--warmup", "1", "--full"], _env(MSORB_DIST_TIMEOUT_S="60"), timeout=400)
     if torch.cuda.device_count() >= 2:      # a multi-GPU box: this IS the RCCL run over xGMI
         assert p.returncode == 0, p.stderr[-3000:]
         out = _last_json(p.stdout)
@@ -74,7 +75,7 @@ def test_bench_rccl_launch_is_a_number_or_a_diagnosis():
 
 def test_a_failing_optional_leg_costs_the_leg_not_the_line():
     q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "16", "--steps", "4", "--warmup", "2", "--cpu-pairs", "0",
-                        "--no-pmc"], cwd=ROOT, env=_env(MSORB_BENCH_FAIL_LEG="per_frame"), capture_output=True, text=True, timeout=900)
+                        "--no-pmc", "--full"], cwd=ROOT, env=_env(MSORB_BENCH_FAIL_LEG="per_frame"), capture_output=True, text=True, timeout=900)
     assert q.returncode == 0, q.stderr[-3000:]
     out = _last_json(q.stdout)
     assert out["value"] > 0 and out["roofline"]["achieved"] > 0
@@ -86,6 +87,28 @@ def test_a_failing_optional_leg_costs_the_leg_not_the_line():
 def test_a_library_failure_inside_a_leg_fails_the_run():
     """round-5 advice: optional_leg used to turn an MsorbError of a core leg into an "error" field of a line that exits 0"""
     q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "16", "--steps", "4", "--warmup", "2", "--cpu-pairs", "0",
-                        "--no-pmc"], cwd=ROOT, env=_env(MSORB_BENCH_FAIL_LEG="hamming_match:library"), capture_output=True, text=True, timeout=900)
+                        "--no-pmc", "--full"], cwd=ROOT, env=_env(MSORB_BENCH_FAIL_LEG="hamming_match:library"), capture_output=True, text=True, timeout=900)
     assert q.returncode != 0 and "forced library failure" in q.stderr
     assert not [l for l in q.stdout.splitlines() if l.startswith("{")]
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing that takes a measurement of its own; --dump-outputs writes the
+    keypoints and descriptors of the last timed step, the same for two runs with the same arguments."""
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        q = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pairs", "16", "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", str(d)], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert q.returncode == 0, q.stderr[-3000:]
+        out = _last_json(q.stdout)
+        assert out["steps"] == 5 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+        assert out["cpu_baseline"] is None and out["hamming_match"] is None and out["tracking_loop"] is None and out["host_fed"] is None
+        counts = np.load(d / "counts.npy")
+        kps, desc = np.load(d / "keypoints.npy"), np.load(d / "descriptors.npy")
+        assert counts.shape == (32,) and counts.sum() == out["keypoints_per_step"] == len(kps) == len(desc)
+        assert kps.dtype == np.float32 and kps.shape[1] == 7 and desc.dtype == np.float64 and desc.shape[1] == 8
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64_000_000
+        outs.append((counts, kps, desc))
+    for a, b in zip(*outs):
+        assert np.array_equal(a, b)

@@ -4,7 +4,7 @@ Oracle and kernels share ms-slam_amd/csrc/orb_pattern.inc and take their scale /
 repository's code: a wrong shared constant would pass every GPU-vs-oracle comparison.  tests/golden/reference_constants.json is
 derived a second way (tools/make_reference_constants.py: the pattern from the reference's TEXT, the rest from the constructor's
 formulas restated in numpy).  Here:
-  CPU  the fixture == the reference text / a fresh run of the tool (when /root/reference is mounted), == SURVEY.md section 8's table
+  CPU  the fixture == the tool's formulas, == SURVEY.md section 8's table
        (the surveyor's own computation: umax, quotas, level sizes), == the three copies of the pattern the repo carries
        (csrc/orb_pattern.inc, the pin kit's embedded copy) and the oracle's constructor tables;
   GPU  the fixture == what the DEVICE holds: the __constant__ pattern and umax read back from the chip
@@ -59,11 +59,14 @@ def test_fixture_is_the_reference_text_and_the_surveys_table():
         if s["sizes"]:
             assert [tuple(x) for x in c["level_sizes_wh"]] == s["sizes"], name
         assert np.array(c["scale_bits"], np.uint32).view(np.float32).tolist() == [float(np.float32(v)) for v in SURVEY_SCALE]
-    if os.path.exists("/root/reference/src/ORBextractor.cc"):     # this container; the GPU box has the fixture only
-        tool = _load(os.path.join(ROOT, "tools", "make_reference_constants.py"), "mrc")
-        pat = tool.reference_pattern()
-        assert _sha(pat) == FIX["pattern_sha256"] and pat[:4].tolist() == FIX["pattern_first_pair"] and pat[-4:].tolist() == FIX["pattern_last_pair"]
-        assert tool.umax_table() == FIX["umax"]
+    # the tool's formulas (which need no reference text) still give the fixture's tables
+    tool = _load(os.path.join(ROOT, "tools", "make_reference_constants.py"), "mrc")
+    assert tool.umax_table() == FIX["umax"]
+    for name, c in FIX["configs"].items():
+        scale, inv_scale, sigma2, inv_sigma2, per_level = tool.ctor_tables(c["nfeatures"], c["scale_factor"], c["nlevels"])
+        assert [tool.bits(v) for v in (scale, inv_scale, sigma2, inv_sigma2)] == [c["scale_bits"], c["inv_scale_bits"], c["sigma2_bits"],
+                                                                                   c["inv_sigma2_bits"]], name
+        assert per_level == c["features_per_level"] and tool.level_sizes(c["rows"], c["cols"], inv_scale) == c["level_sizes_wh"], name
 
 
 def test_every_copy_of_the_pattern_in_the_repo_is_the_fixtures():

@@ -19,7 +19,8 @@ surface only at integration ("weak" item 3):
      tests/slam_stub declare the same member, their type must be the reference's too.
 
 Documented, deliberate additions the integration makes to the reference are listed in ALLOWED_MISSING.
-Runs in the build container only (the reference is not on the GPU box); `pytest -m "not gpu"` runs it through
+Where the reference headers are absent it checks against tests/golden/reference_members.json, the parsed declarations it
+consults, stored by `--write-table` from the headers; `pytest -m "not gpu"` runs it on that table through
 tests/test_check_members.py.  Exit code 0 = consistent; prints a JSON report.
 """
 import glob
@@ -223,6 +224,12 @@ def parse_reference():
 
 
 def lookup(classes, cls, name):
+    c = owner(classes, cls, name)
+    return None if c is None else classes[c]["members"][name]
+
+
+def owner(classes, cls, name):
+    """the class of `cls`'s hierarchy that declares `name` (None: no such member)"""
     seen = set()
     stack = [cls]
     while stack:
@@ -231,9 +238,39 @@ def lookup(classes, cls, name):
             continue
         seen.add(c)
         if name in classes[c]["members"]:
-            return classes[c]["members"][name]
+            return c
         stack.extend(classes[c]["bases"])
     return None
+
+
+# The stored table (tests/golden/reference_members.json) lets the check run where the reference is absent.  It keeps, of the
+# parsed declarations, only what the checks consult: the members the host layer touches, the public interface of the two
+# classes it replaces, EXPECTED_TYPES, and PROBES (members tests/test_check_members.py asks about: access, kind, arity).
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_members.json")
+PROBES = [("KeyFrame", "NLeft"), ("KeyFrame", "GetNLeft"), ("Frame", "mvKeysUn"), ("KeyFrame", "mvKeysUn"), ("MapPoint", "mfMaxDistance"),
+          ("ORBmatcher", "SearchByProjection"), ("ORBmatcher", "mfNNratio"), ("ORBextractor", "mvImagePyramid")]
+
+
+def table(classes):
+    """the stored form of parse_reference()'s result: the consulted members only, sets as sorted lists"""
+    keep = set(host_accesses()) | set(EXPECTED_TYPES) | set(PROBES)
+    keep |= {(c, n) for c in ("ORBmatcher", "ORBextractor") for n, e in classes[c]["members"].items() if "public" in e["access"]}
+    out = {c: {"bases": v["bases"], "file": v["file"], "n_members": len(v["members"]), "members": {}} for c, v in classes.items()}
+    for cls, name in keep:
+        c = owner(classes, cls, name)
+        if c is not None:
+            out[c]["members"][name] = {k: sorted(x) if isinstance(x, set) else x for k, x in classes[c]["members"][name].items()}
+    return out
+
+
+def load_table(path=FIXTURE):
+    """-> the classes of the stored table, in parse_reference()'s form"""
+    classes = json.load(open(path))
+    for v in classes.values():
+        for e in v["members"].values():
+            for k in ("access", "arity", "types"):
+                e[k] = set(e[k])
+    return classes
 
 
 def host_accesses():
@@ -331,11 +368,19 @@ def type_check(classes, accesses):
     return problems, n
 
 
-def main():
-    if not os.path.isdir(os.path.join(REF, "include")):
-        print(json.dumps({"skipped": f"{REF}/include not present (the reference exists in the build container only)"}))
+def main(argv):
+    """no argument: the reference headers if present, else the stored table; --stored: the stored table;
+    --write-table: parse the reference headers and (re)write the stored table"""
+    if "--write-table" in argv:
+        with open(FIXTURE, "w") as f:
+            json.dump(table(parse_reference()), f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("wrote", os.path.relpath(FIXTURE, ROOT))
         return 0
-    classes = parse_reference()
+    if "--stored" in argv or not os.path.isdir(os.path.join(REF, "include")):
+        classes, source = load_table(), os.path.relpath(FIXTURE, ROOT)
+    else:
+        classes, source = parse_reference(), REF
     problems, checked = [], 0
     for (cls, member), uses in sorted(host_accesses().items()):
         if (cls, member) in ALLOWED_MISSING:
@@ -352,7 +397,7 @@ def main():
     problems += dropin_check(classes)
     type_problems, n_types = type_check(classes, host_accesses())
     problems += type_problems
-    report = {"type_comparisons": n_types, "reference": REF, "classes_parsed": {c: len(v["members"]) for c, v in classes.items() if c in
+    report = {"type_comparisons": n_types, "reference": source, "classes_parsed": {c: v.get("n_members", len(v["members"])) for c, v in classes.items() if c in
                                                   ("Frame", "KeyFrame", "MapPoint", "ORBextractor", "ORBmatcher", "GeometricCamera")},
               "member_accesses_checked": checked, "allowed_additions": sorted("::".join(a) for a in ALLOWED_MISSING), "problems": problems}
     print(json.dumps(report, indent=1))
@@ -360,4 +405,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(sys.argv[1:]))
