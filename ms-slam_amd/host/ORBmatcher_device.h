@@ -529,6 +529,49 @@ int SearchLocalPoints(DeviceFrame<FrameT>& dev, FrameT& F, const std::vector<Map
 }
 
 // ---- SearchByBoW ----------------------------------------------------------------------------------------------
+// Every feature's keypoint in feature order.  A KeyFrame: GetKeyPoint(i) for i < GetN() (KeyFrame.h:377-385) — on a two-camera
+// KeyFrame GetAllKeyUn() holds only the left camera's NLeft keypoints (Frame.cc:679-683), so it is read only for one camera.  A frame:
+// mvKeys, followed by mvKeysRight when it has two cameras (Nleft != -1: mvKeys holds Nleft keypoints, Frame.h:324-332).
+// (A KeyFrame / Frame type without the two-camera members — GetNLeft(), Nleft — is a one-camera one.)
+namespace detail {
+template <class T, class = void> struct HasNLeft : std::false_type {};
+template <class T> struct HasNLeft<T, std::void_t<decltype(std::declval<T&>().GetNLeft())>> : std::true_type {};
+template <class T, class = void> struct HasFrameNleft : std::false_type {};
+template <class T> struct HasFrameNleft<T, std::void_t<decltype(std::declval<const T&>().Nleft)>> : std::true_type {};
+}  // namespace detail
+template <class KeyFramePtr>
+int KeyFrameNLeft(const KeyFramePtr& pKF) {
+    if constexpr (detail::HasNLeft<std::remove_reference_t<decltype(*pKF)>>::value) return pKF->GetNLeft();
+    else return -1;
+}
+template <class KeyFramePtr>
+auto KeyFrameKeyPoint(const KeyFramePtr& pKF, int i) {   // GetKeyPoint(i); GetKeyUn(i) is the same keypoint on one camera
+    if constexpr (detail::HasNLeft<std::remove_reference_t<decltype(*pKF)>>::value) return pKF->GetKeyPoint(i);
+    else return pKF->GetKeyUn(i);
+}
+template <class KeyFramePtr>
+auto KeyFrameKeyPoints(const KeyFramePtr& pKF) -> std::decay_t<decltype(pKF->GetAllKeyUn())> {
+    if constexpr (detail::HasNLeft<std::remove_reference_t<decltype(*pKF)>>::value) {
+        if (pKF->GetNLeft() != -1) {
+            const int n = pKF->GetN();
+            std::decay_t<decltype(pKF->GetAllKeyUn())> kp(n);
+            for (int i = 0; i < n; i++) kp[i] = pKF->GetKeyPoint(i);
+            return kp;
+        }
+    }
+    return pKF->GetAllKeyUn();
+}
+template <class FrameT>
+auto FrameKeyPoints(const FrameT& F) -> std::decay_t<decltype(F.mvKeys)> {
+    if constexpr (detail::HasFrameNleft<FrameT>::value) {
+        if (F.Nleft != -1) {
+            std::decay_t<decltype(F.mvKeys)> kp(F.mvKeys.begin(), F.mvKeys.begin() + F.Nleft);
+            kp.insert(kp.end(), F.mvKeysRight.begin(), F.mvKeysRight.end());
+            return kp;
+        }
+    }
+    return F.mvKeys;
+}
 struct BowSide {  // one KeyFrame / Frame flattened for msorb_bow_pair
     std::vector<uint8_t> desc, flag;
     std::vector<int> node, begin, feat;
@@ -552,8 +595,23 @@ struct BowSide {  // one KeyFrame / Frame flattened for msorb_bow_pair
         }
     }
     template <class KeyFramePtr>
-    void FillKeyFrame(const KeyFramePtr& pKF) {
-        Fill(pKF->GetN(), [&](int i) { return pKF->GetDescriptor(i); }, pKF->GetFeatureVector(), pKF->GetAllKeyUn());
+    void FillKeyFrame(const KeyFramePtr& pKF) {   // angles: GetKeyPoint(realIdxKF).angle (:335, :359)
+        Fill(pKF->GetN(), [&](int i) { return pKF->GetDescriptor(i); }, pKF->GetFeatureVector(), KeyFrameKeyPoints(pKF));
+    }
+    template <class FrameT>
+    void FillFrame(const FrameT& F) {             // angles: mvKeys, or mvKeysRight for the right camera's rows (:344-346, :365-367)
+        Fill(F.N, [&](int i) { return F.mDescriptors.row(i); }, F.mFeatVec, FrameKeyPoints(F));
+    }
+    // one side of a KeyFrame-to-KeyFrame search: flag = pMP && !pMP->isBad() (:910-920 / :934-944; the loop form adds its mnLoopPointForKF test).  On a
+    // two-camera KeyFrame the features past vKeysUn.size() = NLeft (the right camera's) are skipped on both sides (:907-909 / :929-931,
+    // :1054-1056 / :1078-1080).
+    template <class KeyFramePtr, class MapPointPtr>
+    void FillKeyFramePair(const KeyFramePtr& pKF, const std::vector<MapPointPtr>& mps) {
+        FillKeyFrame(pKF);
+        FlagGood(mps);
+        const int NL = KeyFrameNLeft(pKF);
+        if (NL != -1)
+            for (size_t i = (size_t)std::max(NL, 0); i < flag.size(); i++) flag[i] = 0;
     }
     template <class MapPointPtr>
     void FlagGood(const std::vector<MapPointPtr>& mps) {  // pMP && !pMP->isBad()
@@ -582,7 +640,7 @@ std::vector<int> SearchByBoWBatch(const std::vector<KeyFramePtr>& vpKFs, FrameT&
                                   bool mbCheckOrientation, int device = 0) {
     const size_t K = vpKFs.size();
     BowSide frame;
-    frame.Fill(F.N, [&](int i) { return F.mDescriptors.row(i); }, F.mFeatVec, F.mvKeys);
+    frame.FillFrame(F);
     std::vector<BowSide> kf(K);
     std::vector<std::vector<MapPointPtr>> mpsKF(K);
     std::vector<msorb_bow_pair> pairs(K);
@@ -613,17 +671,16 @@ int SearchByBoW(const KeyFramePtr& pKF, FrameT& F, std::vector<MapPointPtr>& vpM
     vpMapPointMatches = std::move(out[0]);
     return n;
 }
-// ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (:872-1016, GetNLeft() == -1)
+// ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (:872-1016); on a two-camera KeyFrame only the left camera's features take part
+// (:907-909, :929-931)
 template <class KeyFramePtr, class MapPointPtr>
 int SearchByBoWKeyFrames(const KeyFramePtr& pKF1, const KeyFramePtr& pKF2, std::vector<MapPointPtr>& vpMatches12, float mfNNratio,
                 bool mbCheckOrientation, int device = 0) {
     const auto mps1 = pKF1->GetMapPointMatches();
     const auto mps2 = pKF2->GetMapPointMatches();
     BowSide a, b;
-    a.FillKeyFrame(pKF1);
-    b.FillKeyFrame(pKF2);
-    a.FlagGood(mps1);
-    b.FlagGood(mps2);                                                      // :934-944
+    a.FillKeyFramePair(pKF1, mps1);
+    b.FillKeyFramePair(pKF2, mps2);                                        // :929-944
     msorb_bow_pair P;
     std::vector<int> m12, m21;
     BindBowPair(P, a, b, false, m12, m21);
@@ -670,7 +727,9 @@ void ProjectKeyFramePoints(FrameT& CurrentFrame, const KeyFramePtr& pKF, const M
         P.u[i] = uv(0);
         P.v[i] = uv(1);
         P.level[i] = pMP->PredictScale(dist3D, &CurrentFrame);             // :2198
-        P.angle[i] = pKF->GetKeyUn(i).angle;                               // :2237
+        // :2237 reads pKF->GetKeyUn(i).angle, past the end of mvKeysUn (NLeft entries) for a right-camera feature of a two-camera
+        // KeyFrame; GetKeyPoint(i) is the in-bounds reading of that index (the same keypoint for every i < NLeft and for one camera)
+        P.angle[i] = KeyFrameKeyPoint(pKF, i).angle;
         const auto d = pMP->GetDescriptor();
         std::memcpy(&P.desc[(size_t)i * 32], d.template ptr<unsigned char>(0), 32);
     }
@@ -978,7 +1037,7 @@ public:
         stats_.adds++;
         BowSide side;
         side.FillKeyFrame(pKF);
-        const auto keys = pKF->GetAllKeyUn();
+        const auto keys = KeyFrameKeyPoints(pKF);   // n = GetN() entries for either kind of KeyFrame
         static_assert(sizeof(keys[0]) == sizeof(msorb_keypoint), "cv::KeyPoint must be the 28-byte layout");
         int id = -1;
         check(msorb_kf_store_add(h_->h, n, reinterpret_cast<const msorb_keypoint*>(keys.data()), side.desc.data(), (int)side.node.size(),
@@ -1116,7 +1175,7 @@ std::vector<int> SearchByBoWBatch(KeyFrameStore& store, const std::vector<KeyFra
                                   std::vector<std::vector<MapPointPtr>>& vvpMapPointMatches, float mfNNratio, bool mbCheckOrientation) {
     const size_t K = vpKFs.size();
     BowSide frame;
-    frame.Fill(F.N, [&](int i) { return F.mDescriptors.row(i); }, F.mFeatVec, F.mvKeys);
+    frame.FillFrame(F);
     const msorb_bow_frame bf{F.N, frame.desc.data(), (int)frame.node.size(), frame.node.data(), frame.begin.data(), frame.feat.data(),
                              frame.angle.data()};
     std::vector<std::vector<MapPointPtr>> mpsKF(K);

@@ -296,17 +296,13 @@ template <class KeyFramePtr, class MapPointPtr>
 int SearchByBoWLoop(const KeyFramePtr& pKF1, const KeyFramePtr& pKF2, std::vector<KeyFramePtr>& vpMatchedCurrentKeyFrame,
                     std::vector<MapPointPtr>& vpMatchedCurrentMapPoint, std::vector<KeyFramePtr>& vpMatchedLoopKeyFrame,
                     std::vector<MapPointPtr>& vpMatchedLoopMapPoint, long unsigned int& nCurrentId, float mfNNratio, int device = 0) {
-    const auto vKeysUn1 = pKF1->GetAllKeyUn();
-    const auto vKeysUn2 = pKF2->GetAllKeyUn();
     const auto mps1 = pKF1->GetMapPointMatches();
     const auto mps2 = pKF2->GetMapPointMatches();
     BowSide a, b;
-    a.FillKeyFrame(pKF1);
-    b.FillKeyFrame(pKF2);
-    a.flag.assign(mps1.size(), 0);
-    b.flag.assign(mps2.size(), 0);
-    for (size_t i = 0; i < mps1.size(); i++) a.flag[i] = mps1[i] && !mps1[i]->isBad() && mps1[i]->mnLoopPointForKF != nCurrentId;   // :1059-1066
-    for (size_t i = 0; i < mps2.size(); i++) b.flag[i] = mps2[i] && !mps2[i]->isBad() && mps2[i]->mnLoopPointForKF != nCurrentId;   // :1086-1096
+    a.FillKeyFramePair(pKF1, mps1);                                        // :1054-1056, :1059-1062
+    b.FillKeyFramePair(pKF2, mps2);                                        // :1078-1080, :1086-1092
+    for (size_t i = 0; i < a.flag.size(); i++) a.flag[i] = a.flag[i] && mps1[i]->mnLoopPointForKF != nCurrentId;   // :1059-1066
+    for (size_t i = 0; i < b.flag.size(); i++) b.flag[i] = b.flag[i] && mps2[i]->mnLoopPointForKF != nCurrentId;   // :1086-1096
     msorb_bow_pair P;
     std::vector<int> m12, m21;
     BindBowPair(P, a, b, false, m12, m21);
@@ -322,7 +318,7 @@ int SearchByBoWLoop(const KeyFramePtr& pKF1, const KeyFramePtr& pKF2, std::vecto
         if (!fv2.count(e.first)) continue;
         for (unsigned idx1 : e.second) {
             if ((size_t)idx1 >= m12.size() || m12[idx1] < 0) continue;
-            float rot = vKeysUn1[idx1].angle - vKeysUn2[m12[idx1]].angle;
+            float rot = a.angle[idx1] - b.angle[m12[idx1]];                // vKeysUn1[idx1].angle - vKeysUn2[idx2].angle (idx < NLeft)
             if (rot < 0.0) rot += 360.0f;
             int bin = (int)std::round(rot * factor);
             if (bin == L) bin = 0;

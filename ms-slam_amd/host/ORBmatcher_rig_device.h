@@ -168,10 +168,7 @@ int SearchByBoWRig(const KeyFramePtr& pKF, FrameT& F, std::vector<MapPointPtr>& 
     BowSide kf, frame;
     kf.FillKeyFrame(pKF);
     kf.FlagGood(mpsKF);                                                    // :253-259
-    frame.Fill(F.N, [&](int i) { return F.mDescriptors.row(i); }, F.mFeatVec, F.mvKeys);
-    // the angle of a frame feature: mvKeys for the left camera's rows, mvKeysRight for the right camera's (:344-346, :365-367)
-    frame.angle.resize(F.N);
-    for (int i = 0; i < F.N; i++) frame.angle[i] = i < F.Nleft ? F.mvKeys[i].angle : F.mvKeysRight[i - F.Nleft].angle;
+    frame.FillFrame(F);                                                    // mvKeys / mvKeysRight angles (:344-346, :365-367)
     msorb_bow_pair P;
     std::vector<int> m12, m21;
     BindBowPair(P, kf, frame, true, m12, m21);

@@ -534,7 +534,9 @@ void orc_fuse_search_gated(void* fp, const KeyPoint* gate_kps, const float* gate
 
 // ORBmatcher::SearchByProjection(Frame& CurrentFrame, pKF, sAlreadyFound, th, ORBdist), ORBmatcher.cc:2154-2275, from the
 // projected coordinates on.  One entry per KeyFrame map point that passed :2173-2196 (valid), with its projection u, v,
-// predicted level (:2198), the KeyFrame keypoint's angle (:2237), descriptor and id.  cur_mp[N] in/out.
+// predicted level (:2198), the KeyFrame keypoint's angle (:2237), descriptor and id.  cur_mp[N] in/out.  kf_angle of a two-camera
+// KeyFrame's right-camera map point: the reference's GetKeyUn(i) is past the end of mvKeysUn there (undefined); the stated reading is
+// GetKeyPoint(i).angle, the in-bounds keypoint of that index ("Two-camera frames").
 int orc_search_by_projection_kf(void* fp, int n, const uint8_t* valid, const float* u, const float* v,
                                 const int* predicted_level, const float* kf_angle, const uint8_t* mp_desc, const int* mp_id,
                                 int* cur_mp, float th, int ORBdist, int check_orientation) {
@@ -970,6 +972,26 @@ int orc_search_by_bow(int n1, int n2, const uint8_t* desc1, const uint8_t* desc2
         for (int i = 0; i < n1; i++) if (match12[i] >= 0) match21[match12[i]] = i;
     }
     return nmatches;
+}
+
+// ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (:872-1016) and its loop form (:1018-1166) with the two-camera rule stated:
+//   if(pKF1->GetNLeft() != -1 && idx1 >= vKeysUn1.size()) continue;   (:907-909, :1054-1056)
+//   if(pKF2->GetNLeft() != -1 && idx2 >= vKeysUn2.size()) continue;   (:929-931, :1078-1080)
+// vKeysUn = GetAllKeyUn() holds the left camera's n_left keypoints on such a KeyFrame (Frame.cc:679-683).  n_left1 / n_left2: NLeft, -1
+// for a one-camera KeyFrame.  A skipped query is never visited, a skipped train never enters best / second best: orc_search_by_bow on
+// valid1 / avail2 with those features cleared.  avail2 NULL = every train available apart from the rule.
+int orc_search_by_bow_keyframes(int n1, int n2, int n_left1, int n_left2, const uint8_t* desc1, const uint8_t* desc2, const uint8_t* valid1,
+                                const uint8_t* avail2, int nn1, const int* node1, const int* begin1, const int* feat1, int nn2,
+                                const int* node2, const int* begin2, const int* feat2, const float* angle1, const float* angle2,
+                                int th_low, int inclusive, float nnratio, int check_orientation, int* match12, int* match21) {
+    std::vector<uint8_t> v1(valid1, valid1 + n1), a2(n2, 1);
+    if (avail2) a2.assign(avail2, avail2 + n2);
+    for (int idx1 = 0; idx1 < n1; idx1++)
+        if (n_left1 != -1 && idx1 >= n_left1) v1[idx1] = 0;
+    for (int idx2 = 0; idx2 < n2; idx2++)
+        if (n_left2 != -1 && idx2 >= n_left2) a2[idx2] = 0;
+    return orc_search_by_bow(n1, n2, desc1, desc2, v1.data(), a2.data(), nn1, node1, begin1, feat1, nn2, node2, begin2, feat2, angle1, angle2,
+                             th_low, inclusive, nnratio, check_orientation, match12, match21);
 }
 
 // ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) on a two-camera frame (F.Nleft != -1), ORBmatcher.cc:223-421 statement by

@@ -620,6 +620,29 @@ def search_by_bow(desc1, desc2, valid1, avail2, fv1, fv2, angle1, angle2, th_low
     return nm, m12[:n1], m21[:n2]
 
 
+def search_by_bow_keyframes(desc1, desc2, valid1, avail2, fv1, fv2, angle1, angle2, n_left1, n_left2, th_low=50, inclusive=False,
+                            nnratio=0.6, check_orientation=True):
+    """orc_search_by_bow_keyframes: the KeyFrame-to-KeyFrame forms (ORBmatcher.cc:872-1016, 1018-1166) with the two-camera rule of
+    :907-909 / :929-931 (n_left = NLeft, -1 for a one-camera KeyFrame) -> (nmatches, match12, match21)"""
+    Lb = _mlib()
+    Lb.orc_search_by_bow_keyframes.argtypes = ([C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int] +
+                                               [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p])
+    Lb.orc_search_by_bow_keyframes.restype = C.c_int
+    d1, d2 = _c(desc1, np.uint8).reshape(-1, 32), _c(desc2, np.uint8).reshape(-1, 32)
+    n1, n2 = len(d1), len(d2)
+    v1 = _c(valid1, np.uint8)
+    a2 = None if avail2 is None else _c(avail2, np.uint8)
+    f1 = [_c(a, np.int32) for a in fv1]
+    f2 = [_c(a, np.int32) for a in fv2]
+    g1, g2 = _c(angle1, np.float32), _c(angle2, np.float32)
+    m12, m21 = np.zeros(max(n1, 1), np.int32), np.zeros(max(n2, 1), np.int32)
+    nm = Lb.orc_search_by_bow_keyframes(n1, n2, int(n_left1), int(n_left2), _ptr(d1), _ptr(d2), _ptr(v1), None if a2 is None else _ptr(a2),
+                                        len(f1[0]), _ptr(f1[0]), _ptr(f1[1]), _ptr(f1[2]), len(f2[0]), _ptr(f2[0]), _ptr(f2[1]), _ptr(f2[2]),
+                                        _ptr(g1), _ptr(g2), int(th_low), int(bool(inclusive)), float(nnratio), int(bool(check_orientation)),
+                                        _ptr(m12), _ptr(m21))
+    return nm, m12[:n1], m21[:n2]
+
+
 def search_by_bow_rig(p, n_left, th_low=50, nnratio=0.7, check_orientation=True):
     """orc_search_by_bow_rig (ORBmatcher.cc:223-421, F.Nleft != -1); p as for search_by_bow -> (nmatches, match21)"""
     Lb = _mlib()

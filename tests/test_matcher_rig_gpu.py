@@ -710,3 +710,149 @@ def test_search_by_projection_last_frame_two_camera_tables(msorb_mod, oracle, se
                 assert new[:n_left].sum() > 100 and new[n_left:].sum() > 40
     finally:
         dfl.close(); dfr.close()
+
+
+# ---- the KeyFrame searches of the drop-in CLASS on two-camera KeyFrames (tests/dropin_rig_kf_search_main.cc) ----------------------
+def _rig_kf_search_scene(oracle, seed):
+    rng = np.random.Generator(np.random.PCG64(seed))
+    NL1, NR1, NL2, NR2 = 700, 650, 650, 750
+    N1, N2 = NL1 + NR1, NL2 + NR2
+    k2l, k2r = _kf_cam(rng, oracle, NL2), _kf_cam(rng, oracle, NR2)
+    k2 = np.concatenate([k2l, k2r])
+    d2 = rng.integers(0, 256, (N2, 32), dtype=np.uint8)
+    node2 = (rng.integers(0, 40, N2) * 3 + 5).astype(np.int32)
+    # KeyFrame 1: noisy copies of KeyFrame 2's features (any camera to any camera) turned by 40 degrees, so that the reference keeps
+    # right-camera matches in its dominant histogram bins
+    k1 = np.concatenate([_kf_cam(rng, oracle, NL1), _kf_cam(rng, oracle, NR1)])
+    src = rng.integers(0, N2, N1)
+    d1 = mc.flip_bits(rng, d2[src], 20)
+    node1 = np.where(rng.random(N1) < 0.05, rng.integers(0, 40, N1) * 3 + 6, node2[src]).astype(np.int32)
+    k1["angle"] = (k2["angle"][src] + 40 + rng.normal(0, 4, N1)) % 360
+    held1 = (rng.random(N1) < 0.85).astype(np.uint8); held2 = (rng.random(N2) < 0.85).astype(np.uint8)
+    # decoys of the KeyFrame-to-KeyFrame rule (ORBmatcher.cc:929-931): right-camera features of KeyFrame 2 that beat the left twin of a
+    # left-camera query of KeyFrame 1 in its own node
+    q = np.flatnonzero((np.arange(N1) < NL1) & (src < NL2) & (held1 == 1))[:120]
+    r = NL2 + rng.permutation(NR2)[:len(q)]
+    d2[r] = mc.flip_bits(rng, d1[q], 3); node2[r] = node1[q]; held2[r] = 1
+    k2["angle"][r] = (k1["angle"][q] - 40) % 360
+    return dict(rng=rng, NL1=NL1, NR1=NR1, NL2=NL2, NR2=NR2, N1=N1, N2=N2, k1=k1, k2=k2, d1=d1, d2=d2, node1=node1, node2=node2,
+                held1=held1, held2=held2, src=src, decoy=(q, r))
+
+
+@pytest.mark.parametrize("seed", [41, 42])
+def test_class_keyframe_searches_on_two_camera_keyframes(msorb_mod, oracle, tmp_path, seed):
+    """ORBmatcher::SearchByBoW(pKF, F) (two-camera KeyFrame and frame), SearchByBoW(pKF1, pKF2, vpMatches12), its loop form and
+    SearchByProjection(F, pKF, sAlreadyFound, th, ORBdist) on KeyFrames of a two-camera rig, against the oracle: the KeyFrame angle of a
+    feature is GetKeyPoint(idx).angle (ORBmatcher.cc:335, :359), the KeyFrame-to-KeyFrame forms skip every right-camera feature
+    (:907-909, :929-931, :1054-1056, :1078-1080), and the relocalisation search reads GetKeyPoint(i).angle where the reference's
+    GetKeyUn(i) is past the end of mvKeysUn (:2238)."""
+    exe = str(tmp_path / "dropin_rig_kf_search")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", f"-I{ROOT}/tests/slam_stub", f"-I{ROOT}/tests/cv_stub", f"-I{ROOT}/ms-slam_amd/host",
+                           f"-I{ROOT}/include", f"{ROOT}/tests/dropin_rig_kf_search_main.cc", f"{ROOT}/ms-slam_amd/host/ORBmatcher.cc",
+                           f"-L{ROOT}/ms-slam_amd", "-lmsorb", f"-Wl,-rpath,{ROOT}/ms-slam_amd", "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib",
+                           "-lpthread", "-o", exe])
+    s = _rig_kf_search_scene(oracle, seed)
+    rng = s["rng"]
+    NL1, NR1, NL2, NR2, N1, N2 = (s[k] for k in ("NL1", "NR1", "NL2", "NR2", "N1", "N2"))
+    k1, k2, d1, d2, held1, held2 = s["k1"], s["k2"], s["d1"], s["d2"], s["held1"], s["held2"]
+    cam0 = np.array(CAM, np.float32); cam1 = np.array([CAM[0] * 1.01, CAM[1] * 0.99, CAM[2] + 3.0, CAM[3] - 2.0], np.float32)
+    sigma2 = (SCALE * SCALE).astype(np.float32)
+    th, orb_dist, nnratio, n_current = 10.0, 64, 0.75, 9
+    loop1 = ((rng.random(N1) < 0.15) & (held1 == 1)).astype(np.uint8); loop2 = ((rng.random(N2) < 0.15) & (held2 == 1)).astype(np.uint8)
+    # relocalisation: KeyFrame 1's map points (both cameras) in front of the frame's left camera, each near a left-camera frame keypoint
+    tF = np.array([0.2, -0.1, 0.3])
+    tgt = np.where(s["src"] < NL2, s["src"], rng.integers(0, NL2, N1))
+    z = rng.uniform(5, 40, N1)
+    px = k2["x"][tgt] + rng.normal(0, 1.0, N1); py = k2["y"][tgt] + rng.normal(0, 1.0, N1)
+    Xc = np.stack([(px - CAM[2]) / CAM[0] * z, (py - CAM[3]) / CAM[1] * z, z], 1)
+    Xw = (Xc - tF).astype(np.float32)
+    dist = np.linalg.norm(Xc, axis=1)
+    maxd = (dist * SCALE[k2["octave"][tgt]] * rng.uniform(0.97, 1.03, N1)).astype(np.float32)
+    mind = (maxd / SCALE[7] * 0.5).astype(np.float32)
+    mdesc = mc.flip_bits(rng, d2[tgt], 12)
+    found = ((rng.random(N1) < 0.05) & (held1 == 1)).astype(np.uint8)
+    eye = np.eye(3)
+    pose = lambda t: np.concatenate([eye.reshape(9), t, eye.reshape(9), [-0.12, 0.013, 0.004]]).astype(np.float32)
+    with open(tmp_path / "in.bin", "wb") as f:
+        f.write(struct.pack("<6i", NL1, NR1, NL2, NR2, 0, 8))
+        f.write(struct.pack("<16f", *cam0, *cam1, *BOUNDS, th, orb_dist, nnratio, n_current))
+        f.write(SCALE.tobytes()); f.write(sigma2.tobytes())
+        for (k, d, node, held, t) in ((k1, d1, s["node1"], held1, np.zeros(3)), (k2, d2, s["node2"], held2, np.array([0.1, 0.0, 0.0]))):
+            for a in (k, d, node, held, np.ones(len(k), np.int32), pose(t)):
+                f.write(np.ascontiguousarray(a).tobytes())
+        for a in (loop1, loop2, Xw, maxd, mind, mdesc, found, np.concatenate([eye.reshape(9), tF]).astype(np.float32)):
+            f.write(np.ascontiguousarray(a).tobytes())
+    p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    blob = (tmp_path / "out.bin").read_bytes()
+    pos = 0
+
+    def take(dt, n):
+        nonlocal pos
+        a = np.frombuffer(blob, dt, n, pos)
+        pos += a.nbytes
+        return a
+    fv1, fv2 = bmc.feature_vector_from_nodes(s["node1"]), bmc.feature_vector_from_nodes(s["node2"])
+    a1, a2 = k1["angle"].astype(np.float32), k2["angle"].astype(np.float32)   # GetKeyPoint(i).angle: left keypoints, then the right camera's
+    q, r = s["decoy"]
+    for ori in (True, False):
+        # ---- SearchByBoW(pKF, F): orc_search_by_bow_rig with the KeyFrame's angles of both cameras
+        nb = int(take(np.int32, 1)[0]); ids = take(np.int32, int(take(np.int32, 1)[0]))
+        pb = dict(desc1=d1, desc2=d2, valid1=held1, fv1=fv1, fv2=fv2, angle1=a1, angle2=a2)
+        wn, w21 = oracle.search_by_bow_rig(pb, NL2, 50, nnratio, ori)
+        assert nb == wn and np.array_equal(ids, w21), (ori, nb, wn, int((ids != w21).sum()))
+        matched = w21[w21 >= 0]
+        assert len(matched) > 300 and (matched >= NL1).mean() >= 0.2, (len(matched), (matched >= NL1).mean())   # right-camera KeyFrame features
+        if ori:   # the angle of a right-camera KeyFrame feature decides: the left keypoint of the same number in its place changes the answer
+            wrong = a1.copy(); wrong[NL1:] = a1[np.arange(NR1) % NL1]
+            assert not np.array_equal(oracle.search_by_bow_rig(dict(pb, angle1=wrong), NL2, 50, nnratio, ori)[1], w21)
+        # ---- SearchByBoW(pKF1, pKF2, vpMatches12): the rule of :907-909 / :929-931
+        nk = int(take(np.int32, 1)[0]); m12 = take(np.int32, int(take(np.int32, 1)[0]))
+        wn, w12, _ = oracle.search_by_bow_keyframes(d1, d2, held1, held2, fv1, fv2, a1, a2, NL1, NL2, 50, False, nnratio, ori)
+        assert nk == wn and np.array_equal(m12, w12), (ori, nk, wn, int((m12 != w12).sum()))
+        assert nk > 150 and np.all(w12[NL1:] == -1) and np.all(w12[w12 >= 0] < NL2)
+        _, free12, _ = oracle.search_by_bow_keyframes(d1, d2, held1, held2, fv1, fv2, a1, a2, -1, -1, 50, False, nnratio, ori)
+        assert (free12[NL1:] >= 0).sum() > 50 and (free12[q] == r).sum() > 30      # without the rule: right-camera queries, decoys win
+        assert not np.array_equal(free12, w12)
+    # ---- the loop form: histogram always on, mnLoopPointForKF == nCurrentId excluded, survivors in histogram-bin order
+    nw = int(take(np.int32, 1)[0]); nc = int(take(np.int32, 1)[0])
+    cids = take(np.int32, nc); lids = take(np.int32, nc); consistent = int(take(np.int32, 1)[0])
+    v1 = ((held1 == 1) & (loop1 == 0)).astype(np.uint8); av2 = ((held2 == 1) & (loop2 == 0)).astype(np.uint8)
+    wn, w12, _ = oracle.search_by_bow_keyframes(d1, d2, v1, av2, fv1, fv2, a1, a2, NL1, NL2, 50, False, nnratio, True)
+    hist = [[] for _ in range(30)]
+    nodes2 = set(fv2[0].tolist())
+    for node, b, e in zip(fv1[0], fv1[1][:-1], fv1[1][1:]):
+        if node not in nodes2:
+            continue
+        for idx1 in fv1[2][b:e]:
+            if w12[idx1] >= 0:
+                rot = np.float32(a1[idx1]) - np.float32(a2[w12[idx1]])
+                if rot < 0:
+                    rot = np.float32(rot + np.float32(360.0))
+                bn = int(np.round(np.float32(rot * np.float32(1.0 / 30))))
+                hist[0 if bn == 30 else bn].append(int(idx1))
+    order = [i for h in hist for i in h]
+    assert nw == wn == nc == len(order) and nw > 100 and consistent == 1
+    assert cids.tolist() == order and lids.tolist() == [int(w12[i]) for i in order]
+    _, free12, _ = oracle.search_by_bow_keyframes(d1, d2, v1, av2, fv1, fv2, a1, a2, -1, -1, 50, False, nnratio, True)
+    assert (free12[NL1:] >= 0).sum() > 50 and not np.array_equal(free12, w12)
+    # ---- SearchByProjection(F, pKF1, sAlreadyFound, th, ORBdist): the frame's left camera is searched; KeyFrame angles GetKeyPoint(i)
+    of = oracle.OracleFrame(k2[:NL2], d2[:NL2], None, BOUNDS, SCALE)
+    for ori in (True, False):
+        npr = int(take(np.int32, 1)[0]); ids = take(np.int32, N2)
+        valid = take(np.uint8, N1); u = take(np.float32, N1); v = take(np.float32, N1); level = take(np.int32, N1); ang = take(np.float32, N1)
+        expect_valid = (held1 == 1) & (found == 0)
+        assert np.array_equal(valid > 0, expect_valid)                 # every point projects inside, within its distance band
+        assert np.allclose(u[expect_valid], px[expect_valid], atol=2e-2) and np.allclose(v[expect_valid], py[expect_valid], atol=2e-2)
+        assert np.array_equal(ang[expect_valid], a1[expect_valid])      # GetKeyPoint(i).angle, right camera included
+        cur = np.full(NL2, -1, np.int32)
+        pts = dict(valid=valid, u=u, v=v, level=level, angle=a1, desc=mdesc, mp=np.arange(N1, dtype=np.int32))
+        wn = of.SearchByProjection_kf(pts, cur, th, orb_dist, ori)
+        assert npr == wn and np.array_equal(ids[:NL2], cur) and np.all(ids[NL2:] == -1), (ori, npr, wn, int((ids[:NL2] != cur).sum()))
+        assert wn > 250 and (cur[cur >= 0] >= NL1).mean() >= 0.2      # right-camera map points of the KeyFrame matched
+        if ori:
+            wrong = a1.copy(); wrong[NL1:] = a1[np.arange(NR1) % NL1]
+            alt = np.full(NL2, -1, np.int32)
+            of.SearchByProjection_kf(dict(pts, angle=wrong), alt, th, orb_dist, ori)
+            assert not np.array_equal(alt, cur)
+    assert pos == len(blob)
