@@ -26,26 +26,16 @@
 #include <vector>
 
 #include "../../include/msorb.h"
+#include "hip_host.h"
 #include "lds_limit.h"
 
 namespace msorb {
 // pinned host <-> device on a stream by the copy kernel (orb_kernels.hip; hipMemcpyAsync for unaligned pointers / MSORB_FRAME_COPIES=sdma)
 hipError_t small_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s);
 }
-
-namespace msorb {
-void set_last_error(const std::string& s);
-}
+using msorb::DevBuf;
+using msorb::PinBuf;
 using msorb::set_last_error;
-
-#define HIPCHK(expr)                                                           \
-    do {                                                                       \
-        hipError_t _e = (expr);                                                \
-        if (_e != hipSuccess) {                                                \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-            return MSORB_E_HIP;                                                \
-        }                                                                      \
-    } while (0)
 
 namespace {
 
@@ -327,26 +317,6 @@ __global__ __launch_bounds__(kAsmThreads) void bow_assemble_kernel(
     }
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 }  // namespace
 
 struct msorb_vocabulary {
@@ -363,16 +333,7 @@ struct msorb_vocabulary {
     DevBuf<uint8_t> d_desc;
     DevBuf<int> d_out_i;
     DevBuf<double> d_out_d;
-    uint8_t* h_pin = nullptr;   // pinned staging of the single-frame call: descriptors in, every output out, one synchronisation
-    size_t h_pin_cap = 0;
-    hipError_t ensure_pin(size_t n) {
-        if (n <= h_pin_cap) return hipSuccess;
-        if (h_pin) (void)hipHostFree(h_pin);
-        h_pin = nullptr; h_pin_cap = 0;
-        const hipError_t e = hipHostMalloc((void**)&h_pin, n, hipHostMallocDefault);
-        if (e == hipSuccess) h_pin_cap = n;
-        return e;
-    }
+    PinBuf<uint8_t> h_pin;   // pinned staging of the single-frame call: descriptors in, every output out, one synchronisation
 };
 
 extern "C" {
@@ -392,11 +353,7 @@ int msorb_vocabulary_create(int device, int k, int L, int scoring, int weighting
             set_last_error("vocabulary: parent id out of range");
             return MSORB_E_INVALID;
         }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
+    if (int rc = msorb::require_device(device)) return rc;
     // children CSR by parent, children in ascending node id (= push_back order of the loader)
     std::vector<int> cnt(n_nodes, 0), begin(n_nodes + 1, 0), fill(n_nodes, 0), word(n_nodes, 0);
     for (int i = 1; i < n_nodes; i++) cnt[parent[i]]++;
@@ -502,7 +459,7 @@ void msorb_vocabulary_destroy(msorb_vocabulary* v) {
     if (v->d_cweight) (void)hipFree(v->d_cweight);
     v->d_counts.release(); v->d_feat_word.release(); v->d_feat_node.release(); v->d_feat_weight.release();
     v->d_desc.release(); v->d_out_i.release(); v->d_out_d.release();
-    if (v->h_pin) (void)hipHostFree(v->h_pin);
+    v->h_pin.release();
     if (v->e0) (void)hipEventDestroy(v->e0);
     if (v->e1) (void)hipEventDestroy(v->e1);
     if (v->s) (void)hipStreamDestroy(v->s);
@@ -564,11 +521,10 @@ static int bow_transform_enqueue(msorb_vocabulary* v, const uint8_t* d_descripto
         return MSORB_OK;
     }
     const size_t total = (size_t)n_frames * stride;
-    HIPCHK(v->d_counts.ensure(n_frames));
+    int rc;
+    if ((rc = v->d_counts.ensure(n_frames))) return rc;
     if (!d_fw) {
-        HIPCHK(v->d_feat_word.ensure(total));
-        HIPCHK(v->d_feat_node.ensure(total));
-        HIPCHK(v->d_feat_weight.ensure(total));
+        if ((rc = v->d_feat_word.ensure(total)) || (rc = v->d_feat_node.ensure(total)) || (rc = v->d_feat_weight.ensure(total))) return rc;
         d_fw = v->d_feat_word.p; d_fn = v->d_feat_node.p; d_fwt = v->d_feat_weight.p;
     }
     HIPCHK(hipMemcpyAsync(v->d_counts.p, h_counts, (size_t)n_frames * sizeof(int), hipMemcpyHostToDevice, s));
@@ -626,10 +582,10 @@ int msorb_bow_transform(msorb_vocabulary* v, const uint8_t* descriptors, int n, 
     const size_t o_int = ((size_t)n * 32 + 15) & ~(size_t)15, o_val = (o_int + n_int * sizeof(int) + 7) & ~(size_t)7,
                  o_fw = o_val + (size_t)stride * sizeof(double), o_fn = o_fw + (size_t)n * sizeof(int),
                  o_fwt = (o_fn + (size_t)n * sizeof(int) + 7) & ~(size_t)7, blk_bytes = o_fwt + (size_t)n * sizeof(double);
-    HIPCHK(v->d_desc.ensure(blk_bytes));
-    HIPCHK(v->ensure_pin(blk_bytes));
+    if (int rc = v->d_desc.ensure(blk_bytes)) return rc;
+    if (int rc = v->h_pin.ensure(blk_bytes)) return rc;
     uint8_t* const db = v->d_desc.p;
-    uint8_t* const hp = v->h_pin;
+    uint8_t* const hp = v->h_pin.p;
     int* d_i = reinterpret_cast<int*>(db + o_int);
     double* d_d = reinterpret_cast<double*>(db + o_val);
     hipStream_t s = v->s;

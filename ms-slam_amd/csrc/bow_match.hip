@@ -26,16 +26,18 @@
 #include <vector>
 
 #include "../../include/msorb.h"
+#include "hip_host.h"
 #include "matcher_device.h"
 
 namespace msorb {
-void set_last_error(const std::string& s);
 // pinned host <-> device on a stream by the copy kernel (orb_kernels.hip; hipMemcpyAsync for unaligned pointers / MSORB_FRAME_COPIES=sdma):
 // a block of 100-300 KB is across before an SDMA copy has started
 hipError_t small_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s);
 }
 using msorb::set_last_error;
 using msorb::kHistoLength;
+using msorb::ThreadScratch;
+using msorb::up16;
 
 namespace {
 
@@ -328,43 +330,6 @@ __global__ __launch_bounds__(256) void pair_histogram_kernel(const PairPost* __r
     if (t == 0) nmatches[blockIdx.x] = total;
 }
 
-struct Scratch {
-    int device = -1;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    char *d = nullptr, *h = nullptr;
-    size_t cap = 0;
-    void release() {
-        if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (s) (void)hipStreamDestroy(s);
-        d = h = nullptr; s = nullptr; e0 = e1 = nullptr; cap = 0; device = -1;
-    }
-    hipError_t acquire(int dev, size_t total) {
-        hipError_t e = hipSetDevice(dev);
-        if (e == hipSuccess && device != dev) {
-            release();
-            device = dev;
-            e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreate(&e0);
-            if (e == hipSuccess) e = hipEventCreate(&e1);
-        }
-        if (e == hipSuccess && total > cap) {
-            if (d) (void)hipFree(d);
-            if (h) (void)hipHostFree(h);
-            d = h = nullptr; cap = 0;
-            e = hipMalloc((void**)&d, total + total / 2);
-            if (e == hipSuccess) e = hipHostMalloc((void**)&h, total + total / 2, hipHostMallocDefault);
-            if (e == hipSuccess) cap = total + total / 2;
-        }
-        return e;
-    }
-    ~Scratch() { release(); }
-};
-
 struct FeatVec {  // DBoW2::FeatureVector as CSR
     int nodes;
     const int *node, *begin, *feat;
@@ -467,13 +432,7 @@ int replay_histogram(const FeatVec& a, const std::vector<Common>& common, const 
     return nm;
 }
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-int no_device() {
-    set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-    return MSORB_E_NO_DEVICE;
-}
-int hip_fail(Scratch& scr, const char* what, hipError_t e) {
+int hip_fail(ThreadScratch& scr, const char* what, hipError_t e) {
     set_last_error(std::string(what) + ": " + hipGetErrorString(e));
     scr.release();
     return MSORB_E_HIP;
@@ -519,17 +478,15 @@ int search_by_bow_impl(int device, msorb_bow_pair* pairs, int n_pairs, int th_lo
     }
     if (n_items == 0) return MSORB_OK;
     if (tot1 > (size_t)INT32_MAX / 2 || tot2 > (size_t)INT32_MAX / 2) return MSORB_E_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return no_device();
+    if (int rc = msorb::require_device(device)) return rc;
     // ---- staging: [desc1 | desc2 | feat1 | feat2 | items | valid1 | avail2] in, [match12] out ----
     const size_t o_d1 = 0, o_d2 = o_d1 + tot1 * 32, o_f1 = o_d2 + tot2 * 32, o_f2 = o_f1 + up16(totf1 * 4),
                  o_it = o_f2 + up16(totf2 * 4), o_v1 = o_it + up16(n_items * sizeof(BowItem)), o_a2 = o_v1 + up16(tot1),
                  in_bytes = o_a2 + up16(tot2), o_m = in_bytes, o_b = o_m + up16(tot1 * 4), total = o_b + (best1 ? up16(tot1 * 4) : 0);
-    static thread_local Scratch scr;
-    hipError_t e = scr.acquire(device, total);
-    if (e != hipSuccess) return hip_fail(scr, "search_by_bow", e);
+    static thread_local ThreadScratch scr(true, 2);
+    if (int rc = scr.acquire(device, total, total)) return rc;
     {
-        char* h = scr.h;
+        uint8_t* h = scr.h.p;
         size_t r1 = 0, r2 = 0, k1 = 0, k2 = 0, ni = 0;
         for (int pi = 0; pi < n_pairs; pi++) {
             const msorb_bow_pair& P = pairs[pi];
@@ -547,10 +504,10 @@ int search_by_bow_impl(int device, msorb_bow_pair* pairs, int n_pairs, int th_lo
         }
     }
     hipStream_t s = scr.s;
-    char* d = scr.d;
-    e = msorb::small_copy(d, scr.h, in_bytes, hipMemcpyHostToDevice, s);
+    uint8_t* d = scr.d.p;
+    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, tot1 * 4, s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e0, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(bow_match_kernel, dim3((unsigned)n_items), dim3(64), (size_t)max_chunks * 8, s,
                            (const BowItem*)(d + o_it), (const uint4*)(d + o_d1), (const uint4*)(d + o_d2),
@@ -558,15 +515,15 @@ int search_by_bow_impl(int device, msorb_bow_pair* pairs, int n_pairs, int th_lo
                            (const int*)(d + o_f2), th_low, inclusive, nnratio, (int*)(d + o_m), best1 ? (int*)(d + o_b) : nullptr);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e1, s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h + o_m, d + o_m, (best1 ? o_b - o_m : 0) + tot1 * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
+    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, (best1 ? o_b - o_m : 0) + tot1 * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.e0, scr.e1);
+    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
     if (e != hipSuccess) return hip_fail(scr, "search_by_bow", e);
     if (best1) {   // (features of nodes the two vectors do not share were never visited: they keep 256)
         size_t r = 0;
         for (int pi = 0; pi < n_pairs; pi++) {
-            const int* b = (const int*)(scr.h + o_b) + r;
+            const int* b = (const int*)(scr.h.p + o_b) + r;
             for (const Common& c : common[pi])
                 for (int k = fa[pi].begin[c.r1]; k < fa[pi].begin[c.r1 + 1]; k++) {
                     const int i1 = fa[pi].feat[k];
@@ -579,7 +536,7 @@ int search_by_bow_impl(int device, msorb_bow_pair* pairs, int n_pairs, int th_lo
     // reads of pinned host memory cost ~10 ns each, 0.8 ms for a 32-pair batch
     static thread_local std::vector<int> m_local;
     m_local.resize(tot1);
-    std::memcpy(m_local.data(), scr.h + o_m, tot1 * 4);
+    std::memcpy(m_local.data(), scr.h.p + o_m, tot1 * 4);
     const int* m_all = m_local.data();
     size_t r1 = 0;
     for (int pi = 0; pi < n_pairs; pi++) {
@@ -718,17 +675,15 @@ extern "C" int msorb_search_for_triangulation_cb(int device, msorb_bow_pair* pai
     if (P.match21) for (int j = 0; j < P.n2; j++) P.match21[j] = -1;
     const size_t n_items = common.size(), tot1 = (size_t)P.n1, tot2 = (size_t)P.n2;
     if (n_items == 0) return MSORB_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return no_device();
+    if (int rc = msorb::require_device(device)) return rc;
     // ---- staging: [desc1 | desc2 | feat1 | feat2 | items | valid1 | avail2 | begin] in, [count] out; the lists in their own block ----
     const size_t o_d1 = 0, o_d2 = o_d1 + tot1 * 32, o_f1 = o_d2 + tot2 * 32, o_f2 = o_f1 + up16(totf1 * 4), o_it = o_f2 + up16(totf2 * 4),
                  o_v1 = o_it + up16(n_items * sizeof(BowItem)), o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2), o_cnt = in_bytes,
                  o_beg = o_cnt + up16(n_items * 4), total = o_beg + up16(n_items * 4);
-    static thread_local Scratch scr, lists;
-    hipError_t e = scr.acquire(device, total);
-    if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_cb", e);
+    static thread_local ThreadScratch scr(true, 2), lists(true, 2);
+    if (int rc = scr.acquire(device, total, total)) return rc;
     {
-        char* h = scr.h;
+        uint8_t* h = scr.h.p;
         size_t k1 = 0, k2 = 0, ni = 0;
         if (P.n1) { std::memcpy(h + o_d1, P.desc1, tot1 * 32); std::memcpy(h + o_v1, P.valid1, tot1); }
         if (P.n2) {
@@ -739,38 +694,37 @@ extern "C" int msorb_search_for_triangulation_cb(int device, msorb_bow_pair* pai
         stage_lists(fa, fb, common, 0, 0, 0, (int*)(h + o_f1), (int*)(h + o_f2), k1, k2, (BowItem*)(h + o_it), ni);
     }
     hipStream_t s = scr.s;
-    char* d = scr.d;
-    e = msorb::small_copy(d, scr.h, in_bytes, hipMemcpyHostToDevice, s);
+    uint8_t* d = scr.d.p;
+    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(node_candidates_kernel<false>, dim3((unsigned)n_items), dim3(64), 0, s, (const BowItem*)(d + o_it), (const uint4*)(d + o_d1),
                            (const uint4*)(d + o_d2), (const uint8_t*)(d + o_v1), (const uint8_t*)(d + o_a2), (const int*)(d + o_f1),
                            (const int*)(d + o_f2), th_low, (int*)(d + o_cnt), (const int*)nullptr, (int4*)nullptr);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = msorb::small_copy(scr.h + o_cnt, d + o_cnt, n_items * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_cnt, d + o_cnt, n_items * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_cb", e);
-    const int* cnt = (const int*)(scr.h + o_cnt);
-    int* beg = (int*)(scr.h + o_beg);
+    const int* cnt = (const int*)(scr.h.p + o_cnt);
+    int* beg = (int*)(scr.h.p + o_beg);
     size_t n_cand = 0;
     for (size_t i = 0; i < n_items; i++) { beg[i] = (int)n_cand; n_cand += (size_t)cnt[i]; }
     std::vector<int> raw(tot1, -1);
     if (n_cand > 0) {
         if (n_cand > (size_t)INT32_MAX / 16) { set_last_error("search_for_triangulation_cb: too many candidates"); return MSORB_E_CAPACITY; }
-        e = lists.acquire(device, n_cand * sizeof(int4));
-        if (e != hipSuccess) return hip_fail(lists, "search_for_triangulation_cb", e);
+        if (int rc = lists.acquire(device, n_cand * sizeof(int4), n_cand * sizeof(int4))) return rc;
         e = msorb::small_copy(d + o_beg, beg, n_items * 4, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(node_candidates_kernel<true>, dim3((unsigned)n_items), dim3(64), 0, s, (const BowItem*)(d + o_it), (const uint4*)(d + o_d1),
                                (const uint4*)(d + o_d2), (const uint8_t*)(d + o_v1), (const uint8_t*)(d + o_a2), (const int*)(d + o_f1),
-                               (const int*)(d + o_f2), th_low, (int*)nullptr, (const int*)(d + o_beg), (int4*)lists.d);
+                               (const int*)(d + o_f2), th_low, (int*)nullptr, (const int*)(d + o_beg), (int4*)lists.d.p);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = msorb::small_copy(lists.h, lists.d, n_cand * sizeof(int4), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = msorb::small_copy(lists.h.p, lists.d.p, n_cand * sizeof(int4), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_cb", e);
         // ---- the replay: nodes ascending, a node's queries in list order (:1230-1358) ----
-        std::vector<int4> all((const int4*)lists.h, (const int4*)lists.h + n_cand);   // (out of the pinned block: read repeatedly below)
+        std::vector<int4> all((const int4*)lists.h.p, (const int4*)lists.h.p + n_cand);   // (out of the pinned block: read repeatedly below)
         std::vector<uint8_t> matched2(tot2, 0);                                        // vbMatched2 (:1212)
         std::vector<int4> group;
         size_t k = 0;
@@ -831,18 +785,16 @@ extern "C" int msorb_search_for_triangulation(int device, msorb_triangulation_pa
         for (int i = 0; i < pairs[pi].n1; i++) pairs[pi].match12[i] = -1;
     if (n_items == 0) return MSORB_OK;
     if (tot1 > (size_t)INT32_MAX / 2 || tot2 > (size_t)INT32_MAX / 2) return MSORB_E_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return no_device();
+    if (int rc = msorb::require_device(device)) return rc;
     // ---- staging: [desc1 | desc2 | tr2 (x, y, 100*scale, sigma2) | xy1 | feat1 | feat2 | items | consts | flags1 | flags2] ----
     const size_t o_d1 = 0, o_d2 = o_d1 + tot1 * 32, o_t2 = o_d2 + tot2 * 32, o_x1 = o_t2 + tot2 * 16, o_f1 = o_x1 + up16(tot1 * 8),
                  o_f2 = o_f1 + up16(totf1 * 4), o_it = o_f2 + up16(totf2 * 4), o_c = o_it + up16(n_items * sizeof(BowItem)),
                  o_v1 = o_c + up16((size_t)n_pairs * sizeof(TriConst)), o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2),
                  o_m = in_bytes, total = o_m + up16(tot1 * 4);
-    static thread_local Scratch scr;
-    hipError_t e = scr.acquire(device, total);
-    if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation", e);
+    static thread_local ThreadScratch scr(true, 2);
+    if (int rc = scr.acquire(device, total, total)) return rc;
     {
-        char* h = scr.h;
+        uint8_t* h = scr.h.p;
         size_t r1 = 0, r2 = 0, k1 = 0, k2 = 0, ni = 0;
         TriConst* consts = (TriConst*)(h + o_c);
         for (int pi = 0; pi < n_pairs; pi++) {
@@ -876,10 +828,10 @@ extern "C" int msorb_search_for_triangulation(int device, msorb_triangulation_pa
         }
     }
     hipStream_t s = scr.s;
-    char* d = scr.d;
-    e = msorb::small_copy(d, scr.h, in_bytes, hipMemcpyHostToDevice, s);
+    uint8_t* d = scr.d.p;
+    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, tot1 * 4, s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e0, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(triangulation_match_kernel, dim3((unsigned)n_items), dim3(64), (size_t)max_chunks * 8, s,
                            (const BowItem*)(d + o_it), (const TriConst*)(d + o_c), (const uint4*)(d + o_d1),
@@ -888,16 +840,16 @@ extern "C" int msorb_search_for_triangulation(int device, msorb_triangulation_pa
                            coarse, (int*)(d + o_m));
         e = hipGetLastError();
     }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e1, s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h + o_m, d + o_m, tot1 * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
+    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, tot1 * 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.e0, scr.e1);
+    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
     if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation", e);
     // the raw matches are read feature by feature below: out of the pinned block first (one streaming copy) — scattered 4-byte
     // reads of pinned host memory cost ~10 ns each, 0.8 ms for a 32-pair batch
     static thread_local std::vector<int> m_local;
     m_local.resize(tot1);
-    std::memcpy(m_local.data(), scr.h + o_m, tot1 * 4);
+    std::memcpy(m_local.data(), scr.h.p + o_m, tot1 * 4);
     const int* m_all = m_local.data();
     size_t r1 = 0;
     for (int pi = 0; pi < n_pairs; pi++) {
@@ -994,8 +946,7 @@ hipError_t grow(T*& p, size_t used, size_t& cap, size_t need, size_t unit) {
 extern "C" int msorb_kf_store_create(int device, msorb_kf_store** out) {
     if (!out) return MSORB_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return no_device();
+    if (int rc = msorb::require_device(device)) return rc;
     msorb_kf_store* s = new msorb_kf_store();
     s->device = device;
     *out = s;
@@ -1201,11 +1152,10 @@ extern "C" int msorb_search_by_bow_kf(msorb_kf_store* st, msorb_bow_kf_pair* pai
                  o_po = o_it + up16(n_items * sizeof(BowItem)), o_v1 = o_po + up16((size_t)n_pairs * sizeof(PairPost)),
                  o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2), o_m = in_bytes, o_m21 = o_m + up16(tot1 * 4),
                  o_nm = o_m21 + up16(tot2 * 4), total = o_nm + up16((size_t)n_pairs * 4), out_bytes = total - o_m;
-    static thread_local Scratch scr;
-    hipError_t e = scr.acquire(st->device, total);
-    if (e != hipSuccess) return hip_fail(scr, "search_by_bow_kf", e);
+    static thread_local ThreadScratch scr(true, 2);
+    if (int rc = scr.acquire(st->device, total, total)) return rc;
     {
-        char* h = scr.h;
+        uint8_t* h = scr.h.p;
         if (fr_rows) std::memcpy(h + o_fd, frame->desc, fr_rows * 32);
         if (fr_feats) std::memcpy(h + o_ff, frame->fv_feat + fr_feat_lo, fr_feats * 4);
         if (fr_rows && frame->angle) std::memcpy(h + o_fa, frame->angle, fr_rows * 4);
@@ -1224,10 +1174,10 @@ extern "C" int msorb_search_by_bow_kf(msorb_kf_store* st, msorb_bow_kf_pair* pai
         }
     }
     hipStream_t s = scr.s;
-    char* d = scr.d;
-    e = msorb::small_copy(d, scr.h, in_bytes, hipMemcpyHostToDevice, s);
+    uint8_t* d = scr.d.p;
+    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, o_nm - o_m, s);   // match12 and match21 = -1
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e0, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
     if (e == hipSuccess) {
         const uint4* desc2 = frame ? (const uint4*)(d + o_fd) : st->d_desc;
         const int* feat2 = frame ? (const int*)(d + o_ff) : st->d_feat;
@@ -1239,17 +1189,17 @@ extern "C" int msorb_search_by_bow_kf(msorb_kf_store* st, msorb_bow_kf_pair* pai
                            (int*)(d + o_nm));
         e = hipGetLastError();
     }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e1, s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h + o_m, d + o_m, out_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
+    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, out_bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.e0, scr.e1);
+    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
     if (e != hipSuccess) return hip_fail(scr, "search_by_bow_kf", e);
     for (int pi = 0; pi < n_pairs; pi++) {
         msorb_bow_kf_pair& P = pairs[pi];
         const int n1 = st->kf[P.kf1].n, n2 = P.kf2 < 0 ? frame->n : st->kf[P.kf2].n;
-        if (n1) std::memcpy(P.match12, scr.h + o_m + (size_t)m1[pi] * 4, (size_t)n1 * 4);
-        if (P.match21 && n2) std::memcpy(P.match21, scr.h + o_m21 + (size_t)m2[pi] * 4, (size_t)n2 * 4);
-        P.nmatches = ((const int*)(scr.h + o_nm))[pi];
+        if (n1) std::memcpy(P.match12, scr.h.p + o_m + (size_t)m1[pi] * 4, (size_t)n1 * 4);
+        if (P.match21 && n2) std::memcpy(P.match21, scr.h.p + o_m21 + (size_t)m2[pi] * 4, (size_t)n2 * 4);
+        P.nmatches = ((const int*)(scr.h.p + o_nm))[pi];
     }
     return MSORB_OK;
 }
@@ -1296,11 +1246,10 @@ extern "C" int msorb_search_for_triangulation_kf(msorb_kf_store* st, msorb_trian
     const size_t o_it = 0, o_c = o_it + up16(n_items * sizeof(BowItem)), o_po = o_c + up16((size_t)n_pairs * sizeof(TriConst)),
                  o_v1 = o_po + up16((size_t)n_pairs * sizeof(PairPost)), o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2),
                  o_m = in_bytes, o_nm = o_m + up16(tot1 * 4), total = o_nm + up16((size_t)n_pairs * 4), out_bytes = total - o_m;
-    static thread_local Scratch scr;
-    hipError_t e = scr.acquire(st->device, total);
-    if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_kf", e);
+    static thread_local ThreadScratch scr(true, 2);
+    if (int rc = scr.acquire(st->device, total, total)) return rc;
     {
-        char* h = scr.h;
+        uint8_t* h = scr.h.p;
         std::memcpy(h + o_it, items.data(), n_items * sizeof(BowItem));
         TriConst* consts = (TriConst*)(h + o_c);
         PairPost* posts = (PairPost*)(h + o_po);
@@ -1318,10 +1267,10 @@ extern "C" int msorb_search_for_triangulation_kf(msorb_kf_store* st, msorb_trian
         }
     }
     hipStream_t s = scr.s;
-    char* d = scr.d;
-    e = msorb::small_copy(d, scr.h, in_bytes, hipMemcpyHostToDevice, s);
+    uint8_t* d = scr.d.p;
+    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, tot1 * 4, s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e0, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(triangulation_match_kernel, dim3((unsigned)n_items), dim3(64), (size_t)max_chunks * 8, s,
                            (const BowItem*)(d + o_it), (const TriConst*)(d + o_c), st->d_desc, st->d_desc, (const uint8_t*)(d + o_v1),
@@ -1330,16 +1279,16 @@ extern "C" int msorb_search_for_triangulation_kf(msorb_kf_store* st, msorb_trian
                            st->d_angle, check_orientation, (int*)(d + o_m), (int*)nullptr, (int*)(d + o_nm));
         e = hipGetLastError();
     }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.e1, s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h + o_m, d + o_m, out_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
+    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, out_bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.e0, scr.e1);
+    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
     if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_kf", e);
     for (int pi = 0; pi < n_pairs; pi++) {
         msorb_triangulation_kf_pair& P = pairs[pi];
         const int n1 = st->kf[P.kf1].n;
-        if (n1) std::memcpy(P.match12, scr.h + o_m + (size_t)m1[pi] * 4, (size_t)n1 * 4);
-        P.nmatches = ((const int*)(scr.h + o_nm))[pi];
+        if (n1) std::memcpy(P.match12, scr.h.p + o_m + (size_t)m1[pi] * 4, (size_t)n1 * 4);
+        P.nmatches = ((const int*)(scr.h.p + o_nm))[pi];
     }
     return MSORB_OK;
 }

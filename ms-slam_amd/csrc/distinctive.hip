@@ -15,62 +15,15 @@
 #include <vector>
 
 #include "../../include/msorb.h"
+#include "hip_host.h"
 
 namespace msorb {
-void set_last_error(const std::string& s);
 // pinned host <-> device on a stream by the copy kernel (orb_kernels.hip)
 hipError_t small_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s);
 }
 using msorb::set_last_error;
 
-#define HIPCHK(expr)                                                           \
-    do {                                                                       \
-        hipError_t _e = (expr);                                                \
-        if (_e != hipSuccess) {                                                \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-            cleanup();                                                         \
-            return MSORB_E_HIP;                                                \
-        }                                                                      \
-    } while (0)
-
 namespace {
-
-struct DistinctScratch {   // grow-only, per calling thread; released at thread exit (a dead runtime is tolerated)
-    int device = -1;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    char *d = nullptr, *h = nullptr;
-    size_t cap = 0;
-    void release() {
-        if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (s) (void)hipStreamDestroy(s);
-        d = h = nullptr; s = nullptr; e0 = e1 = nullptr; cap = 0; device = -1;
-    }
-    hipError_t acquire(int dev, size_t total) {
-        hipError_t e = hipSetDevice(dev);
-        if (e == hipSuccess && device != dev) {
-            release();
-            device = dev;
-            e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreate(&e0);
-            if (e == hipSuccess) e = hipEventCreate(&e1);
-        }
-        if (e == hipSuccess && total > cap) {
-            if (d) (void)hipFree(d);
-            if (h) (void)hipHostFree(h);
-            d = h = nullptr; cap = 0;
-            e = hipMalloc((void**)&d, total + total / 2 + 64);
-            if (e == hipSuccess) e = hipHostMalloc((void**)&h, total + total / 2 + 64, hipHostMallocDefault);
-            if (e == hipSuccess) cap = total + total / 2;
-        }
-        return e;
-    }
-    ~DistinctScratch() { release(); }
-};
 
 __device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
     return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
@@ -177,11 +130,7 @@ extern "C" int msorb_distinctive_descriptors(int device, const uint8_t* descript
         }
     const int total = obs_begin[n_points];
     if (total > 0 && !descriptors) return MSORB_E_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
+    if (int rc = msorb::require_device(device)) return rc;
     // classes by segment width; points without descriptors are answered here (:393-394: early return)
     std::vector<int> lists[5];
     for (int p = 0; p < n_points; p++) {
@@ -206,26 +155,24 @@ extern "C" int msorb_distinctive_descriptors(int device, const uint8_t* descript
     // ([descriptors | obs_begin | point lists]), the kernels, one read-back ([best | median]).  (Rounds 1-5 created the stream and the
     // events, hipMalloc'ed five arrays and freed them again in EVERY call, and copied from pageable memory: 0.5 ms for 2 000 points
     // where the kernels take 20 us — and every hipFree synchronises the device under the other SLAM threads.)
-    static thread_local DistinctScratch scr;
-    auto cleanup = [&] {};
-    const size_t o_beg = ((size_t)total * 32 + 15) & ~(size_t)15, o_pts = o_beg + (((size_t)(n_points + 1) * 4 + 15) & ~(size_t)15),
-                 in_bytes = o_pts + ((all.size() * 4 + 15) & ~(size_t)15), o_best = in_bytes, o_med = o_best + (((size_t)n_points * 4 + 15) & ~(size_t)15),
-                 bytes = o_med + (((size_t)n_points * 4 + 15) & ~(size_t)15);
-    {
-        const hipError_t e = scr.acquire(device, bytes);
-        if (e != hipSuccess) { set_last_error(std::string("distinctive_descriptors: ") + hipGetErrorString(e)); scr.release(); return MSORB_E_HIP; }
-    }
+    static thread_local msorb::ThreadScratch scr(true, 2);
+    using msorb::up16;
+    const size_t o_beg = up16((size_t)total * 32), o_pts = o_beg + up16((size_t)(n_points + 1) * 4), in_bytes = o_pts + up16(all.size() * 4),
+                 o_best = in_bytes, o_med = o_best + up16((size_t)n_points * 4), bytes = o_med + up16((size_t)n_points * 4);
+    if (int rc = scr.acquire(device, bytes, bytes)) return rc;
     hipStream_t s = scr.s;
-    if (total) std::memcpy(scr.h, descriptors, (size_t)total * 32);
-    std::memcpy(scr.h + o_beg, obs_begin, (size_t)(n_points + 1) * sizeof(int));
-    std::memcpy(scr.h + o_pts, all.data(), all.size() * sizeof(int));
-    HIPCHK(msorb::small_copy(scr.d, scr.h, in_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(scr.e0, s));
-    const uint4* dd = reinterpret_cast<const uint4*>(scr.d);
-    const int* d_begin = reinterpret_cast<const int*>(scr.d + o_beg);
-    const int* d_points = reinterpret_cast<const int*>(scr.d + o_pts);
-    int* d_best = reinterpret_cast<int*>(scr.d + o_best);
-    int* d_med = reinterpret_cast<int*>(scr.d + o_med);
+    uint8_t* const h = scr.h.p;
+    uint8_t* const d = scr.d.p;
+    if (total) std::memcpy(h, descriptors, (size_t)total * 32);
+    std::memcpy(h + o_beg, obs_begin, (size_t)(n_points + 1) * sizeof(int));
+    std::memcpy(h + o_pts, all.data(), all.size() * sizeof(int));
+    HIPCHK(msorb::small_copy(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(scr.ev[0], s));
+    const uint4* dd = reinterpret_cast<const uint4*>(d);
+    const int* d_begin = reinterpret_cast<const int*>(d + o_beg);
+    const int* d_points = reinterpret_cast<const int*>(d + o_pts);
+    int* d_best = reinterpret_cast<int*>(d + o_best);
+    int* d_med = reinterpret_cast<int*>(d + o_med);
     auto launch_small = [&](auto kernel, int W, int c) {
         const int n = off[c + 1] - off[c];
         if (n == 0) return;
@@ -240,13 +187,13 @@ extern "C" int msorb_distinctive_descriptors(int device, const uint8_t* descript
     if (off[5] > off[4])
         hipLaunchKernelGGL(distinct_big_kernel, dim3(off[5] - off[4]), dim3(64), 0, s, dd, d_begin, d_points + off[4], d_best,
                            d_med);
-    HIPCHK(hipEventRecord(scr.e1, s));
-    HIPCHK(msorb::small_copy(scr.h + o_best, scr.d + o_best, bytes - o_best, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(scr.ev[1], s));
+    HIPCHK(msorb::small_copy(h + o_best, d + o_best, bytes - o_best, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
-    if (elapsed_ms) HIPCHK(hipEventElapsedTime(elapsed_ms, scr.e0, scr.e1));
-    const int* hb = reinterpret_cast<const int*>(scr.h + o_best);
-    const int* hm = reinterpret_cast<const int*>(scr.h + o_med);
+    if (elapsed_ms) HIPCHK(hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]));
+    const int* hb = reinterpret_cast<const int*>(h + o_best);
+    const int* hm = reinterpret_cast<const int*>(h + o_med);
     for (int p : all) {
         best_idx[p] = hb[p];
         if (best_median) best_median[p] = hm[p];

@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "hip_host.h"
 #include "orb_device.h"
 #include "gauss7_stream_device.h"
 #include "matcher_device.h"
@@ -33,16 +34,6 @@ using namespace msorb;
 namespace {
 
 thread_local std::string g_last_error;
-void set_error(const std::string& s) { g_last_error = s; }
-
-#define HIPCHK(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) {                                                                       \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                             \
-            return MSORB_E_HIP;                                                                       \
-        }                                                                                             \
-    } while (0)
 
 const int8_t kPattern[1024] = {
 #include "orb_pattern.inc"
@@ -117,35 +108,6 @@ private:
     std::shared_ptr<Job> cur_;
     unsigned gen_ = 0;
     bool stop_ = false;
-};
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t count) {
-        if (count <= n) return MSORB_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        HIPCHK(hipMalloc((void**)&p, count * sizeof(T) + 16));   // + 16: small_copy moves whole 16-byte units
-        n = count;
-        return MSORB_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-template <typename T>
-struct PinBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t count) {
-        if (count <= n) return MSORB_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; n = 0;
-        HIPCHK(hipHostMalloc((void**)&p, count * sizeof(T) + 16, hipHostMallocDefault));
-        n = count;
-        return MSORB_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
 };
 
 }  // namespace
@@ -261,11 +223,11 @@ int ensure_geometry(msorb_extractor* h, int rows, int cols) {
     h->geom_valid = false;
     FrameGeom g;
     if (!g.build(h->P, rows, cols)) {
-        set_error("image too small for the reference's 35-px cell grid at some pyramid level");
+        set_last_error("image too small for the reference's 35-px cell grid at some pyramid level");
         return MSORB_E_GEOMETRY;
     }
     for (const CellDesc& c : g.cells)
-        if (c.rw > 76 || c.rh > 76) { set_error("cell ROI larger than 76 px"); return MSORB_E_GEOMETRY; }
+        if (c.rw > 76 || c.rh > 76) { set_last_error("cell ROI larger than 76 px"); return MSORB_E_GEOMETRY; }
     h->G = g;
     h->small_cells = true;
     for (const CellDesc& c : g.cells) h->small_cells = h->small_cells && c.rw <= 46 && c.rh <= 57;
@@ -324,7 +286,7 @@ int ensure_geometry(msorb_extractor* h, int rows, int cols) {
     const bool fits_lds = (long long)quadtree_lds_bytes(h->qt) + 10 * 1024 <= (long long)h->lds_per_block;
     const bool fits_labels = 4 * max_quota + 16 <= 65535;   // (the 16-bit rank tables of the workspace; labels are 32 bits in the global form)
     if (!h->knobs.quadtree_host && !fits_lds && !fits_labels) {
-        set_error("a level quota of " + std::to_string(max_quota) + " keypoints is beyond the device selection (16 379 per level); MSORB_QUADTREE=host runs it on the host twin");
+        set_last_error("a level quota of " + std::to_string(max_quota) + " keypoints is beyond the device selection (16 379 per level); MSORB_QUADTREE=host runs it on the host twin");
         return MSORB_E_CAPACITY;
     }
     h->device_quadtree = !h->knobs.quadtree_host;
@@ -458,7 +420,7 @@ int finish_groups(msorb_extractor* h, int n_images, int* h_counts, int* h_mono) 
     for (int gi = 0; gi < ng; gi++) HIPCHK(hipStreamSynchronize(h->grp[gi].s));
     HIPCHK(hipGetLastError());
     for (int i = 0; i < n_images; i++) {
-        if (h->h_sel_count.p[i] < 0) { set_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+        if (h->h_sel_count.p[i] < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
         h_counts[i] = h->h_sel_count.p[i];
         if (h_mono) h_mono[i] = h->h_mono.p[i];
     }
@@ -686,7 +648,7 @@ int run_pipeline(msorb_extractor* h, const LevelView& level0, int n_images, int 
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipGetLastError());
         for (int i = 0; i < n_images; i++) {
-            if (h->h_sel_count.p[i] < 0) { set_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+            if (h->h_sel_count.p[i] < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
             h_counts[i] = h->h_sel_count.p[i];
             if (h_mono) h_mono[i] = h->h_mono.p[i];
         }
@@ -735,7 +697,7 @@ int run_pipeline(msorb_extractor* h, const LevelView& level0, int n_images, int 
             h->pool.reset(new Pool(std::max(1, std::min(nthreads, 64))));
         }
         h->pool->parallel_for(n_images, task);
-        if (overflow.load()) { set_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+        if (overflow.load()) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
         int max_sel = 0;
         for (int i = 0; i < n_images; i++) max_sel = std::max(max_sel, h->h_sel_count.p[i]);
         HIPCHK(hipMemcpyAsync(h->d_sel.p, h->h_sel.p, (size_t)n_images * sel_stride * sizeof(SelRec), hipMemcpyHostToDevice, s));
@@ -775,7 +737,7 @@ void set_last_error(const std::string& s) { g_last_error = s; }
 int extractor_last_view(msorb_extractor* h, PyramidView* pyr, LevelScale* sc, float* inv_scale, int* device,
                         hipStream_t* stream, int* n_images) {
     if (!h || !h->geom_valid || h->last_n_images < 1) {
-        set_error("extractor has no pyramid yet (call msorb_extract first)");
+        set_last_error("extractor has no pyramid yet (call msorb_extract first)");
         return MSORB_E_INVALID;
     }
     *pyr = h->last_pyr;
@@ -841,14 +803,10 @@ int msorb_extractor_create(int nfeatures, float scale_factor, int nlevels, int i
     *out = nullptr;
     if (nfeatures <= 0 || nlevels < 1 || nlevels > MSORB_MAX_LEVELS || !(scale_factor > 1.0f) || ini_th < 0 ||
         min_th < 0 || ini_th > 255 || min_th > ini_th) {
-        set_error("invalid extractor parameters");
+        set_last_error("invalid extractor parameters");
         return MSORB_E_INVALID;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
+    if (int rc = require_device(device)) return rc;
     HIPCHK(hipSetDevice(device));
     msorb_extractor* h = new msorb_extractor();
     h->device = device;
@@ -869,7 +827,7 @@ int msorb_extractor_create(int nfeatures, float scale_factor, int nlevels, int i
         hipEventCreateWithFlags(&h->ev_compact, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_pyramid, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_blur, hipEventDisableTiming) != hipSuccess) {
-        set_error("stream/event creation failed");
+        set_last_error("stream/event creation failed");
         delete h;
         return MSORB_E_HIP;
     }
@@ -956,19 +914,19 @@ int msorb_extractor_set_overlap(msorb_extractor* h, int sub_batches, int blur_on
 }
 int msorb_extractor_set_semantics(msorb_extractor* h, const msorb_semantics* sem) {
     if (!h) return MSORB_E_INVALID;
-    if (h->pending_batch) { set_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
+    if (h->pending_batch) { set_last_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
     Semantics s;
     if (sem) {
         int sum = 0;
         for (int i = 0; i < 7; i++) {
-            if (sem->gauss_taps[i] < 0 || sem->gauss_taps[i] > 255) { set_error("gauss tap outside 0..255"); return MSORB_E_INVALID; }
+            if (sem->gauss_taps[i] < 0 || sem->gauss_taps[i] > 255) { set_last_error("gauss tap outside 0..255"); return MSORB_E_INVALID; }
             s.gauss_taps[i] = sem->gauss_taps[i];
             sum += sem->gauss_taps[i];
         }
-        if (sum < 1 || sum > 257) { set_error("gauss taps: the 16-bit horizontal sums need sum(taps) <= 257"); return MSORB_E_INVALID; }
+        if (sum < 1 || sum > 257) { set_last_error("gauss taps: the 16-bit horizontal sums need sum(taps) <= 257"); return MSORB_E_INVALID; }
         s.resize_single_stage = sem->resize_rounding != 0;
         s.atan2_fma = sem->atan2_fma != 0;
-        if (sem->brief_tap < 0 || sem->brief_tap > 2) { set_error("brief_tap must be 0 (first product fused), 1 (second product fused) or 2 (no contraction)"); return MSORB_E_INVALID; }
+        if (sem->brief_tap < 0 || sem->brief_tap > 2) { set_last_error("brief_tap must be 0 (first product fused), 1 (second product fused) or 2 (no contraction)"); return MSORB_E_INVALID; }
         s.brief_tap = sem->brief_tap;
     }
     h->sem = s;
@@ -989,16 +947,16 @@ int msorb_extractor_stage_ms(const msorb_extractor* h, float* ms) {
 static int extract_batch_common(msorb_extractor* h, const uint8_t* d_images, int n_images, int rows, int cols, size_t row_stride,
                                 size_t image_stride, int lap0, int lap1, msorb_keypoint* d_kps, uint8_t* d_desc, int capacity,
                                 int* h_counts, int* h_mono, bool submit_only) {
-    if (!h || !d_kps || !d_desc || (!submit_only && !h_counts) || n_images < 0) { set_error("null argument"); return MSORB_E_INVALID; }
-    if (h->pending_batch) { set_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
+    if (!h || !d_kps || !d_desc || (!submit_only && !h_counts) || n_images < 0) { set_last_error("null argument"); return MSORB_E_INVALID; }
+    if (h->pending_batch) { set_last_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
     if (!d_images || rows <= 0 || cols <= 0) return MSORB_E_EMPTY;
     if (n_images == 0) return MSORB_OK;
     if ((int)row_stride < cols || (n_images > 1 && image_stride < row_stride * (size_t)rows)) {
-        set_error("bad strides");
+        set_last_error("bad strides");
         return MSORB_E_INVALID;
     }
     if (submit_only && (!h->device_quadtree || h->knobs.serial_pipeline)) {
-        set_error("msorb_extract_batch_submit needs the device pipeline");
+        set_last_error("msorb_extract_batch_submit needs the device pipeline");
         return MSORB_E_INVALID;
     }
     HIPCHK(hipSetDevice(h->device));
@@ -1041,8 +999,8 @@ int msorb_extract_batch_submit(msorb_extractor* h, const uint8_t* d_images, int 
                                 nullptr, nullptr, true);
 }
 int msorb_extract_batch_wait(msorb_extractor* h, int* h_counts, int* h_mono) {
-    if (!h || !h_counts) { set_error("null argument"); return MSORB_E_INVALID; }
-    if (!h->pending_batch) { set_error("no submitted batch to wait for"); return MSORB_E_INVALID; }
+    if (!h || !h_counts) { set_last_error("null argument"); return MSORB_E_INVALID; }
+    if (!h->pending_batch) { set_last_error("no submitted batch to wait for"); return MSORB_E_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     const int n = h->pending_batch;
     h->pending_batch = 0;
@@ -1051,7 +1009,7 @@ int msorb_extract_batch_wait(msorb_extractor* h, int* h_counts, int* h_mono) {
 
 int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, size_t stride, int lap0, int lap1,
                   msorb_keypoint* keypoints, uint8_t* descriptors, int capacity, int* n_keypoints, int* mono_index) {
-    if (h && h->pending_batch) { set_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
+    if (h && h->pending_batch) { set_last_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
     if (!h || !n_keypoints || !mono_index) return MSORB_E_INVALID;
     *n_keypoints = 0;
     *mono_index = -1;
@@ -1097,13 +1055,13 @@ int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, 
         HIPCHK(hipGetLastError());
         n = h->h_sel_count.p[0];
         mono = h->h_mono.p[0];
-        if (n < 0) { set_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-        if (n > capacity) { set_error("caller capacity too small"); return MSORB_E_CAPACITY; }
+        if (n < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+        if (n > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
     } else {
         HIPCHK(hipMemcpyAsync(h->d_pyr.p + g0.plane_off, h->h_img_pin.p, (size_t)g0.pitch * rows, hipMemcpyHostToDevice,
                               h->stream));
         if ((rc = run_pipeline(h, l0, 1, lap0, lap1, h->d_kps1.p, h->d_desc1.p, cap, &n, &mono))) return rc;
-        if (n > capacity) { set_error("caller capacity too small"); return MSORB_E_CAPACITY; }
+        if (n > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
         if (n > 0) {
             HIPCHK(hipMemcpyAsync(pk, h->d_kps1.p, (size_t)n * sizeof(msorb_keypoint), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipMemcpyAsync(pd, h->d_desc1.p, (size_t)n * 32, hipMemcpyDeviceToHost, h->stream));
@@ -1122,13 +1080,13 @@ int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, 
 int msorb_extract_pair(msorb_extractor* h, const uint8_t* image_a, const uint8_t* image_b, int rows, int cols, size_t stride_a,
                        size_t stride_b, int lap0, int lap1, msorb_keypoint* kps_a, uint8_t* desc_a, int* n_a, int* mono_a,
                        msorb_keypoint* kps_b, uint8_t* desc_b, int* n_b, int* mono_b, int capacity, int staged) {
-    if (h && h->pending_batch) { set_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
+    if (h && h->pending_batch) { set_last_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
     if (!h || !n_a || !n_b || !mono_a || !mono_b) return MSORB_E_INVALID;
     *n_a = *n_b = 0;
     *mono_a = *mono_b = -1;
     if (!image_a || !image_b || rows <= 0 || cols <= 0) return MSORB_E_EMPTY;
     if (!kps_a || !desc_a || !kps_b || !desc_b || (int)stride_a < cols || (int)stride_b < cols) return MSORB_E_INVALID;
-    if (!h->device_quadtree || h->knobs.serial_pipeline || h->profiling) { set_error("msorb_extract_pair needs the device pipeline"); return MSORB_E_INVALID; }
+    if (!h->device_quadtree || h->knobs.serial_pipeline || h->profiling) { set_last_error("msorb_extract_pair needs the device pipeline"); return MSORB_E_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     int rc;
     if ((rc = ensure_geometry(h, rows, cols))) return rc;
@@ -1149,10 +1107,10 @@ int msorb_extract_pair(msorb_extractor* h, const uint8_t* image_a, const uint8_t
     int own_plane[2] = {-1, -1};   // plane of h_img_pin a staged image occupies (overlaps), -1: memory of another handle
     for (int i = 0; i < 2; i++) {
         if (!(staged & (1 << i))) continue;
-        if (stride[i] != (size_t)g0.pitch) { set_error("msorb_extract_pair: a staged image must have the staging pitch"); return MSORB_E_INVALID; }
+        if (stride[i] != (size_t)g0.pitch) { set_last_error("msorb_extract_pair: a staged image must have the staging pitch"); return MSORB_E_INVALID; }
         const uint8_t* lo = h->h_img_pin.p;
         if (src[i] + plane > lo && src[i] < lo + 2 * plane) {
-            if (src[i] != lo && src[i] != lo + plane) { set_error("msorb_extract_pair: a staged pointer inside this handle's staging block must be a plane msorb_stage_image returned"); return MSORB_E_INVALID; }
+            if (src[i] != lo && src[i] != lo + plane) { set_last_error("msorb_extract_pair: a staged pointer inside this handle's staging block must be a plane msorb_stage_image returned"); return MSORB_E_INVALID; }
             own_plane[i] = src[i] == lo ? 0 : 1;
         }
     }
@@ -1184,8 +1142,8 @@ int msorb_extract_pair(msorb_extractor* h, const uint8_t* image_a, const uint8_t
     if (h->h_pyr_async) HIPCHK(hipStreamSynchronize(h->pyr_stream));
     HIPCHK(hipGetLastError());
     const int na = h->h_sel_count.p[0], nb = h->h_sel_count.p[1];
-    if (na < 0 || nb < 0) { set_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-    if (na > capacity || nb > capacity) { set_error("caller capacity too small"); return MSORB_E_CAPACITY; }
+    if (na < 0 || nb < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+    if (na > capacity || nb > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
     memcpy(kps_a, o, (size_t)na * sizeof(msorb_keypoint));
     memcpy(kps_b, o + kp_bytes, (size_t)nb * sizeof(msorb_keypoint));
     memcpy(desc_a, o + o_desc, (size_t)na * 32);
@@ -1197,7 +1155,7 @@ int msorb_extract_pair(msorb_extractor* h, const uint8_t* image_a, const uint8_t
 
 int msorb_stage_image(msorb_extractor* h, const uint8_t* image, int rows, int cols, size_t stride, const uint8_t** pinned, size_t* pitch) {
     if (!h || !pinned || !image || rows <= 0 || cols <= 0 || (int)stride < cols) return MSORB_E_INVALID;
-    if (h->pending_batch) { set_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
+    if (h->pending_batch) { set_last_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     int rc;
     if ((rc = ensure_geometry(h, rows, cols))) return rc;
@@ -1255,7 +1213,7 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
                                size_t stride_right, float mb, float mbf, msorb_keypoint* kps_left, uint8_t* desc_left, int* n_left,
                                msorb_keypoint* kps_right, uint8_t* desc_right, int* n_right, int capacity, float* u_right,
                                float* depth, int* n_oob, StereoSinkFn sink, void* ctx) {
-    if (h && h->pending_batch) { set_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
+    if (h && h->pending_batch) { set_last_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
     if (!h || !n_left || !n_right) return MSORB_E_INVALID;
     *n_left = *n_right = 0;
     if (n_oob) *n_oob = 0;
@@ -1264,7 +1222,7 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
         (int)stride_right < cols)
         return MSORB_E_INVALID;
     if (!h->device_quadtree || h->knobs.serial_pipeline) {
-        set_error("msorb_extract_stereo needs the device pipeline");
+        set_last_error("msorb_extract_stereo needs the device pipeline");
         return MSORB_E_INVALID;
     }
     HIPCHK(hipSetDevice(h->device));
@@ -1278,7 +1236,7 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
     for (int l = 0; l < g.nlevels; l++) smax = std::max(smax, h->scales.scale[l]);
     const int row_cap = cap * ((int)std::ceil(4.0f * smax) + 3);
     const bool bands = rows <= 4095;   // (a band record holds 12-bit rows; taller images — none of the BASELINE configs — take the row table)
-    if (!bands && (size_t)(2 * rows + 1) * sizeof(int) > 60000) { set_error("image too tall for the stereo row table"); return MSORB_E_INVALID; }
+    if (!bands && (size_t)(2 * rows + 1) * sizeof(int) > 60000) { set_last_error("image too tall for the stereo row table"); return MSORB_E_INVALID; }
     // one device block for everything that travels back: [kps 2*cap][desc 2*cap*32][u_right cap][depth cap][n_oob], and
     // one device block for the two level-0 planes (read in place by the pipeline): one copy each way
     const size_t kp_bytes = (size_t)cap * sizeof(msorb_keypoint);
@@ -1364,8 +1322,8 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     const int nl = reinterpret_cast<const int*>(o + o_cnt)[0], nr = reinterpret_cast<const int*>(o + o_cnt)[1];
-    if (nl < 0 || nr < 0) { set_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-    if (nl > capacity || nr > capacity) { set_error("caller capacity too small"); return MSORB_E_CAPACITY; }
+    if (nl < 0 || nr < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+    if (nl > capacity || nr > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
     memcpy(kps_left, o, (size_t)nl * sizeof(msorb_keypoint));
     memcpy(kps_right, o + kp_bytes, (size_t)nr * sizeof(msorb_keypoint));
     memcpy(desc_left, o + o_desc, (size_t)nl * 32);
@@ -1390,7 +1348,7 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
                                int cols, size_t stride_left, size_t stride_right, float mb, float mbf,
                                msorb_keypoint* kps_left, uint8_t* desc_left, int* n_left, msorb_keypoint* kps_right,
                                uint8_t* desc_right, int* n_right, int capacity, float* u_right, float* depth, int* n_oob) {
-    if ((L && L->pending_batch) || (R && R->pending_batch)) { set_error("a submitted batch of a handle has not been waited for"); return MSORB_E_INVALID; }
+    if ((L && L->pending_batch) || (R && R->pending_batch)) { set_last_error("a submitted batch of a handle has not been waited for"); return MSORB_E_INVALID; }
     if (!L || !R || L == R || !n_left || !n_right) return MSORB_E_INVALID;
     *n_left = *n_right = 0;
     if (n_oob) *n_oob = 0;
@@ -1399,24 +1357,24 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
         (int)stride_right < cols)
         return MSORB_E_INVALID;
     if (L->P.nfeatures != R->P.nfeatures || L->P.nlevels != R->P.nlevels || L->P.scale_factor_f != R->P.scale_factor_f) {
-        set_error("msorb_extract_stereo_split: the two extractors differ in their parameters");
+        set_last_error("msorb_extract_stereo_split: the two extractors differ in their parameters");
         return MSORB_E_INVALID;
     }
-    if (L->knobs.serial_pipeline || R->knobs.serial_pipeline) { set_error("msorb_extract_stereo_split needs the device pipeline"); return MSORB_E_INVALID; }
+    if (L->knobs.serial_pipeline || R->knobs.serial_pipeline) { set_last_error("msorb_extract_stereo_split needs the device pipeline"); return MSORB_E_INVALID; }
     const int cap = capacity_of(L);
     int rc;
     // geometry / buffers of both handles (each on its own device)
     for (msorb_extractor* h : {R, L}) {
         HIPCHK(hipSetDevice(h->device));
         if ((rc = ensure_geometry(h, rows, cols))) return rc;
-        if (!h->device_quadtree) { set_error("msorb_extract_stereo_split needs the device pipeline"); return MSORB_E_INVALID; }
+        if (!h->device_quadtree) { set_last_error("msorb_extract_stereo_split needs the device pipeline"); return MSORB_E_INVALID; }
         if ((rc = ensure_batch(h, 1))) return rc;
         if ((rc = h->h_img_pin.ensure((size_t)h->G.lv[0].pitch * rows))) return rc;
     }
     const FrameGeom& g = L->G;
     const LevelGeom& g0 = g.lv[0];
     const size_t plane = (size_t)g0.pitch * rows;
-    if ((size_t)(2 * rows + 1) * sizeof(int) > 60000) { set_error("image too tall for the stereo row table"); return MSORB_E_INVALID; }
+    if ((size_t)(2 * rows + 1) * sizeof(int) > 60000) { set_last_error("image too tall for the stereo row table"); return MSORB_E_INVALID; }
     float smax = 0;
     for (int l = 0; l < g.nlevels; l++) smax = std::max(smax, L->scales.scale[l]);
     const int row_cap = cap * ((int)std::ceil(4.0f * smax) + 3);
@@ -1540,8 +1498,8 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     const int nl = reinterpret_cast<const int*>(o + o_cnt)[0], nr = reinterpret_cast<const int*>(o + o_cnt)[1];
-    if (nl < 0 || nr < 0) { set_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-    if (nl > capacity || nr > capacity) { set_error("caller capacity too small"); return MSORB_E_CAPACITY; }
+    if (nl < 0 || nr < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+    if (nl > capacity || nr > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
     memcpy(kps_left, o, (size_t)nl * sizeof(msorb_keypoint));
     memcpy(kps_right, o + kp_bytes, (size_t)nr * sizeof(msorb_keypoint));
     memcpy(desc_left, o + o_desc, (size_t)nl * 32);
@@ -1559,11 +1517,11 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
 // association, when only its keypoints / descriptors were gathered from another device.  Asynchronous on the handle's stream.
 int msorb_pyramid_batch(msorb_extractor* h, const uint8_t* d_images, int n_images, int rows, int cols, size_t row_stride,
                         size_t image_stride) {
-    if (h && h->pending_batch) { set_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
+    if (h && h->pending_batch) { set_last_error("a submitted batch of this handle has not been waited for"); return MSORB_E_INVALID; }
     if (!h || n_images < 0) return MSORB_E_INVALID;
     if (!d_images || rows <= 0 || cols <= 0) return MSORB_E_EMPTY;
     if (n_images == 0) return MSORB_OK;
-    if ((int)row_stride < cols || (n_images > 1 && image_stride < row_stride * (size_t)rows)) { set_error("bad strides"); return MSORB_E_INVALID; }
+    if ((int)row_stride < cols || (n_images > 1 && image_stride < row_stride * (size_t)rows)) { set_last_error("bad strides"); return MSORB_E_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     int rc;
     if ((rc = ensure_geometry(h, rows, cols))) return rc;
@@ -1613,7 +1571,7 @@ int msorb_debug_std_sort(int device, const uint32_t* keys, int n, int frame_form
     if (!keys || !order || n < 0) return MSORB_E_INVALID;
     HIPCHK(hipSetDevice(device));
     const int rc = launch_debug_sort(keys, n, frame_form, order, sorted_keys, sort_us);
-    if (rc == MSORB_E_HIP) set_error(std::string("msorb_debug_std_sort: ") + hipGetErrorString(hipGetLastError()));
+    if (rc == MSORB_E_HIP) set_last_error(std::string("msorb_debug_std_sort: ") + hipGetErrorString(hipGetLastError()));
     return rc;
 }
 
@@ -1651,7 +1609,7 @@ int msorb_debug_candidates(msorb_extractor* h, int image, int level, int* xyscor
     if (!h || !n || !h->geom_valid || image < 0 || image >= h->last_n_images || level < 0 || level >= h->G.nlevels)
         return MSORB_E_INVALID;
     const int nl = h->G.nlevels;
-    if (h->last_groups != 1) { set_error("candidate inspection needs a single sub-batch (n_images < 16, or msorb_extractor_set_overlap(h, 1, ...) before the call)"); return MSORB_E_INVALID; }
+    if (h->last_groups != 1) { set_last_error("candidate inspection needs a single sub-batch (n_images < 16, or msorb_extractor_set_overlap(h, 1, ...) before the call)"); return MSORB_E_INVALID; }
     if (!h->compact_on_host) {
         HIPCHK(hipSetDevice(h->device));
         int rc;

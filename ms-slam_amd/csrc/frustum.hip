@@ -13,14 +13,11 @@
 
 #include "../../include/msorb.h"
 #include "frustum_device.h"
+#include "hip_host.h"
 
 namespace msorb {
 // pinned host <-> device on a stream by the copy kernel (orb_kernels.hip; hipMemcpyAsync for unaligned pointers / MSORB_FRAME_COPIES=sdma)
 hipError_t small_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s);
-}
-
-namespace msorb {
-void set_last_error(const std::string& s);
 }
 using msorb::set_last_error;
 
@@ -59,87 +56,49 @@ extern "C" int msorb_is_in_frustum(int device, const msorb_frustum* f, float vie
                    !proj_xr || !track_depth || !scale_level || !view_cos)))
         return MSORB_E_INVALID;
     if (n == 0) return MSORB_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
+    if (int rc = msorb::require_device(device)) return rc;
     // Called once per frame (Tracking::SearchLocalPoints): stream, events, device buffer and pinned staging are kept per
     // calling thread and device.  One buffer: inputs (8 floats / point) then outputs (6 x 4 B + 1 B / point).
-    struct Scratch {
-        int device = -1;
-        hipStream_t s = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        char *d = nullptr, *h = nullptr;
-        size_t cap = 0;
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            if (d) (void)hipFree(d);
-            if (h) (void)hipHostFree(h);
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            if (s) (void)hipStreamDestroy(s);
-            d = h = nullptr; s = nullptr; e0 = e1 = nullptr; cap = 0; device = -1;
-        }
-        ~Scratch() { release(); }
-    };
-    static thread_local Scratch scr;
+    static thread_local msorb::ThreadScratch scr(true, 2);
     const size_t N = (size_t)n;
     const size_t in_bytes = N * 8 * sizeof(float), out_bytes = N * 6 * 4 + N, total = in_bytes + out_bytes;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess && scr.device != device) {
-        scr.release();
-        scr.device = device;
-        e = hipStreamCreateWithFlags(&scr.s, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreate(&scr.e0);
-        if (e == hipSuccess) e = hipEventCreate(&scr.e1);
-    }
-    if (e == hipSuccess && total > scr.cap) {
-        if (scr.d) (void)hipFree(scr.d);
-        if (scr.h) (void)hipHostFree(scr.h);
-        scr.d = scr.h = nullptr; scr.cap = 0;
-        e = hipMalloc((void**)&scr.d, total + total / 2);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&scr.h, total + total / 2, hipHostMallocDefault);
-        if (e == hipSuccess) scr.cap = total + total / 2;
-    }
+    if (int rc = scr.acquire(device, total, total)) return rc;
+    hipStream_t s = scr.s;
+    float* d_pos = (float*)scr.d.p;
+    float* d_nrm = d_pos + 3 * N;
+    float* d_max = d_nrm + 3 * N;
+    float* d_min = d_max + N;
+    float* d_px = d_min + N;
+    float* d_py = d_px + N;
+    float* d_pxr = d_py + N;
+    float* d_depth = d_pxr + N;
+    int* d_level = (int*)(d_depth + N);
+    float* d_vc = (float*)(d_level + N);
+    uint8_t* d_in = (uint8_t*)(d_vc + N);
+    float* h_f = (float*)scr.h.p;
+    std::memcpy(h_f, pos_w, N * 12);
+    std::memcpy(h_f + 3 * N, normal, N * 12);
+    std::memcpy(h_f + 6 * N, max_distance, N * 4);
+    std::memcpy(h_f + 7 * N, min_distance, N * 4);
+    hipError_t e = msorb::small_copy(scr.d.p, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipEventRecord(scr.ev[0], s);
+    if (e == hipSuccess)
+        hipLaunchKernelGGL(frustum_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, *f, viewing_cos_limit, n, d_pos,
+                           d_nrm, d_max, d_min, d_in, d_px, d_py, d_pxr, d_depth, d_level, d_vc);
+    if (e == hipSuccess) e = hipEventRecord(scr.ev[1], s);
+    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + in_bytes, scr.d.p + in_bytes, out_bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
     if (e == hipSuccess) {
-        hipStream_t s = scr.s;
-        float* d_pos = (float*)scr.d;
-        float* d_nrm = d_pos + 3 * N;
-        float* d_max = d_nrm + 3 * N;
-        float* d_min = d_max + N;
-        float* d_px = d_min + N;
-        float* d_py = d_px + N;
-        float* d_pxr = d_py + N;
-        float* d_depth = d_pxr + N;
-        int* d_level = (int*)(d_depth + N);
-        float* d_vc = (float*)(d_level + N);
-        uint8_t* d_in = (uint8_t*)(d_vc + N);
-        float* h_f = (float*)scr.h;
-        std::memcpy(h_f, pos_w, N * 12);
-        std::memcpy(h_f + 3 * N, normal, N * 12);
-        std::memcpy(h_f + 6 * N, max_distance, N * 4);
-        std::memcpy(h_f + 7 * N, min_distance, N * 4);
-        e = msorb::small_copy(scr.d, scr.h, in_bytes, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipEventRecord(scr.e0, s);
-        if (e == hipSuccess)
-            hipLaunchKernelGGL(frustum_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, *f, viewing_cos_limit, n, d_pos,
-                               d_nrm, d_max, d_min, d_in, d_px, d_py, d_pxr, d_depth, d_level, d_vc);
-        if (e == hipSuccess) e = hipEventRecord(scr.e1, s);
-        if (e == hipSuccess) e = msorb::small_copy(scr.h + in_bytes, scr.d + in_bytes, out_bytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.e0, scr.e1);
-        if (e == hipSuccess) {
-            const char* ho = scr.h + in_bytes;
-            std::memcpy(proj_x, ho, N * 4);
-            std::memcpy(proj_y, ho + N * 4, N * 4);
-            std::memcpy(proj_xr, ho + N * 8, N * 4);
-            std::memcpy(track_depth, ho + N * 12, N * 4);
-            std::memcpy(scale_level, ho + N * 16, N * 4);
-            std::memcpy(view_cos, ho + N * 20, N * 4);
-            std::memcpy(track_in_view, ho + N * 24, N);
-        }
+        const uint8_t* ho = scr.h.p + in_bytes;
+        std::memcpy(proj_x, ho, N * 4);
+        std::memcpy(proj_y, ho + N * 4, N * 4);
+        std::memcpy(proj_xr, ho + N * 8, N * 4);
+        std::memcpy(track_depth, ho + N * 12, N * 4);
+        std::memcpy(scale_level, ho + N * 16, N * 4);
+        std::memcpy(view_cos, ho + N * 20, N * 4);
+        std::memcpy(track_in_view, ho + N * 24, N);
     }
     if (e != hipSuccess) {
         set_last_error(std::string("is_in_frustum: ") + hipGetErrorString(e));

@@ -1,5 +1,5 @@
 // Internals shared by the host-side matcher sources (matcher_host.hip, track.hip): the frame handle (features + 64x48
-// grid on the device), grow-only device / pinned buffers, the error macro.  Not part of the C ABI.
+// grid on the device) and the claiming window search.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,11 +12,11 @@
 #include <string>
 #include <vector>
 
+#include "hip_host.h"
 #include "matcher_device.h"
 #include "orb_device.h"
 
 namespace msorb {
-void set_last_error(const std::string& s);
 int extractor_last_view(msorb_extractor* h, PyramidView* pyr, LevelScale* sc, float* inv_scale, int* device,
                         hipStream_t* stream, int* n_images);
 int extractor_device(const msorb_extractor* h);
@@ -41,47 +41,6 @@ int enqueue_frame_from_device(msorb_frame* f, hipStream_t s, const msorb_keypoin
                               float min_y, float max_y, const float* scale_factors, int nlevels, const LastFrameProjector* proj = nullptr);
 }  // namespace msorb
 
-#define HIPCHK(expr)                                                               \
-    do {                                                                           \
-        hipError_t _e = (expr);                                                    \
-        if (_e != hipSuccess) {                                                    \
-            msorb::set_last_error(std::string(#expr) + ": " + hipGetErrorString(_e));     \
-            return MSORB_E_HIP;                                                    \
-        }                                                                          \
-    } while (0)
-
-namespace msorb {
-template <typename T>
-struct DBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t count) {
-        if (count <= n) return MSORB_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        HIPCHK(hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T) + 16));   // + 16: small_copy moves whole 16-byte units
-        n = std::max<size_t>(count, 1);
-        return MSORB_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-// pinned host staging: hipMemcpyAsync from / to pageable memory makes the driver stage and synchronise per call
-template <typename T>
-struct HBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    int ensure(size_t count) {
-        if (count <= n) return MSORB_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; n = 0;
-        HIPCHK(hipHostMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T) + 16, hipHostMallocDefault));
-        n = std::max<size_t>(count, 1);
-        return MSORB_OK;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
-};
-}  // namespace msorb
-
 struct msorb_frame {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -90,20 +49,20 @@ struct msorb_frame {
     std::vector<msorb_keypoint> kps;
     std::vector<float> u_right, scale;
     std::vector<int> cell_begin, cell_idx;
-    msorb::DBuf<msorb::KpLite> d_kp;
-    msorb::DBuf<uint8_t> d_desc, d_occ, d_qdesc, d_stage, d_win;   // d_win: queries | descriptors | occupancy of a host-fed window search, one upload
-    msorb::DBuf<int> d_cell_begin, d_cell_idx, d_n;
-    msorb::DBuf<int> d_init_cnt, d_init_beg;   // msorb_search_for_initialization: candidate counts / list offsets / lists
-    msorb::DBuf<int2> d_init_list;
+    msorb::DevBuf<msorb::KpLite> d_kp;
+    msorb::DevBuf<uint8_t> d_desc, d_occ, d_qdesc, d_stage, d_win;   // d_win: queries | descriptors | occupancy of a host-fed window search, one upload
+    msorb::DevBuf<int> d_cell_begin, d_cell_idx, d_n;
+    msorb::DevBuf<int> d_init_cnt, d_init_beg;   // msorb_search_for_initialization: candidate counts / list offsets / lists
+    msorb::DevBuf<int2> d_init_list;
     int last_rounds = 0;                // device rounds of the last claim-replaying search (msorb_frame_search_rounds)
     long long total_rounds = 0, total_searches = 0;
     bool host_grid_valid = false;       // cell_begin / cell_idx (host) mirror the device grid
     std::mutex grid_mu;                 // the lazy fetch of that mirror (msorb_frame_features_in_area is a const query)
     msorb_frame_track* track = nullptr;  // staging of the local-points chain (track.hip)
-    msorb::DBuf<msorb::WinQuery> d_q;
-    msorb::DBuf<msorb::TopK> d_topk;
-    msorb::HBuf<uint8_t> h_in;    // queries + query descriptors + occupancy, staged
-    msorb::HBuf<msorb::TopK> h_topk;
+    msorb::DevBuf<msorb::WinQuery> d_q;
+    msorb::DevBuf<msorb::TopK> d_topk;
+    msorb::PinBuf<uint8_t> h_in;    // queries + query descriptors + occupancy, staged
+    msorb::PinBuf<msorb::TopK> h_topk;
     msorb::FrameView view() const {
         msorb::FrameView v;
         v.kp = d_kp.p; v.desc = d_desc.p; v.cell_begin = d_cell_begin.p; v.cell_idx = d_cell_idx.p;

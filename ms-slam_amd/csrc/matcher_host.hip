@@ -30,11 +30,7 @@ extern "C" {
 int msorb_frame_create(int device, msorb_frame** out) {
     if (!out) return MSORB_E_INVALID;
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
+    if (int rc = require_device(device)) return rc;
     HIPCHK(hipSetDevice(device));
     msorb_frame* f = new msorb_frame();
     f->device = device;
@@ -824,8 +820,8 @@ int init_full_lists(msorb_frame* f1, msorb_frame* f2, std::vector<WinQuery> q, i
     int rc;
     // grow-only scratch on the train frame's handle (a per-call hipMalloc / hipFree pair synchronises the whole device
     // while the other SLAM threads have kernels in flight, and leaked on the early returns)
-    DBuf<int>&d_cnt = f2->d_init_cnt, &d_beg = f2->d_init_beg;
-    DBuf<int2>& d_list = f2->d_init_list;
+    DevBuf<int>&d_cnt = f2->d_init_cnt, &d_beg = f2->d_init_beg;
+    DevBuf<int2>& d_list = f2->d_init_list;
     if ((rc = f2->d_q.ensure(N1)) || (rc = f2->d_qdesc.ensure((size_t)N1 * 32)) || (rc = d_cnt.ensure(N1)) ||
         (rc = d_beg.ensure(N1 + 1)))
         return rc;
@@ -986,42 +982,17 @@ int msorb_hamming_top2(int device, const uint8_t* qdesc, int nq, const uint8_t* 
                        const int* cand_idx, int* best_idx, int* best_dist, int* second_idx, int* second_dist) {
     if (nq < 0 || nt < 0 || (nq > 0 && (!qdesc || !cand_begin || !best_idx || !best_dist || !second_idx || !second_dist)))
         return MSORB_E_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
+    if (int rc = require_device(device)) return rc;
     if (nq == 0) return MSORB_OK;
-    HIPCHK(hipSetDevice(device));
     const int total = cand_begin[nq];
     for (int i = 0; i < total; i++)
         if (cand_idx[i] < 0 || cand_idx[i] >= nt) { set_last_error("candidate index out of range"); return MSORB_E_INVALID; }
     // per-thread grow-only scratch, one staged block up ([queries | trains | list offsets | list]) and one down (rounds 1-5: five
     // hipMalloc / hipFree and eight synchronous copies on the null stream per call)
-    struct Scratch {
-        int device = -1;
-        hipStream_t s = nullptr;
-        DBuf<uint8_t> d;
-        HBuf<uint8_t> h;
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            d.release(); h.release();
-            if (s) (void)hipStreamDestroy(s);
-            s = nullptr; device = -1;
-        }
-        ~Scratch() { release(); }
-    };
-    static thread_local Scratch S;
-    if (S.device != device) {
-        S.release();
-        S.device = device;
-        HIPCHK(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
-    }
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    static thread_local ThreadScratch S(true, 0);
     const size_t o_t = up16((size_t)nq * 32), o_cb = o_t + up16((size_t)nt * 32), o_ci = o_cb + up16((size_t)(nq + 1) * 4),
                  in_bytes = o_ci + up16((size_t)total * 4), o_out = in_bytes, bytes = o_out + up16((size_t)4 * nq * 4);
-    int rc;
-    if ((rc = S.d.ensure(bytes)) || (rc = S.h.ensure(bytes))) return rc;
+    if (int rc = S.acquire(device, bytes, bytes)) return rc;
     std::memcpy(S.h.p, qdesc, (size_t)nq * 32);
     if (nt) std::memcpy(S.h.p + o_t, tdesc, (size_t)nt * 32);
     std::memcpy(S.h.p + o_cb, cand_begin, (size_t)(nq + 1) * sizeof(int));
@@ -1052,54 +1023,35 @@ int msorb_knn_match2(int device, const uint8_t* query, int n_query, const uint8_
         return MSORB_E_INVALID;
     for (int i = 0; i < n_query; i++) { best_idx[i] = -1; best_dist[i] = 256; if (second_idx) second_idx[i] = -1; second_dist[i] = 256; }
     if (n_query == 0 || n_train == 0) return MSORB_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
-    HIPCHK(hipSetDevice(device));
-    struct Scratch {
-        int device = -1;
-        hipStream_t s = nullptr;
-        DBuf<uint8_t> q, t;
-        DBuf<int> out, n;
-        HBuf<int> h;
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            q.release(); t.release(); out.release(); n.release(); h.release();
-            if (s) (void)hipStreamDestroy(s);
-            s = nullptr; device = -1;
-        }
-        ~Scratch() { release(); }
-    };
-    static thread_local Scratch S;
-    if (S.device != device) {
-        S.release();
-        S.device = device;
-        HIPCHK(hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking));
-    }
+    if (int rc = require_device(device)) return rc;
+    // per-thread grow-only scratch: device [queries | one chunk of trains | best, best distance, second distance | the two counts],
+    // pinned [best, best distance, second distance | the two counts]
     constexpr int kChunk = 2048;
     const int tc = std::min(n_train, kChunk);
-    int rc;
-    if ((rc = S.q.ensure((size_t)n_query * 32)) || (rc = S.t.ensure((size_t)tc * 32)) || (rc = S.out.ensure((size_t)3 * n_query)) ||
-        (rc = S.n.ensure(2)) || (rc = S.h.ensure((size_t)3 * n_query + 2)))
-        return rc;
+    const size_t nq = (size_t)n_query, o_t = up16(nq * 32), o_out = o_t + up16((size_t)tc * 32), o_n = o_out + up16(3 * nq * 4),
+                 dev_bytes = o_n + 16, pin_bytes = 3 * nq * 4 + 8;
+    static thread_local ThreadScratch S(true, 0);
+    if (int rc = S.acquire(device, dev_bytes, pin_bytes)) return rc;
+    uint8_t* const d_q = S.d.p;
+    uint8_t* const d_t = S.d.p + o_t;
+    int* const d_out = reinterpret_cast<int*>(S.d.p + o_out);
+    int* const d_n = reinterpret_cast<int*>(S.d.p + o_n);
+    int* const h_out = reinterpret_cast<int*>(S.h.p);
     hipStream_t s = S.s;
-    HIPCHK(hipMemcpyAsync(S.q.p, query, (size_t)n_query * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_q, query, nq * 32, hipMemcpyHostToDevice, s));
     // the kernel reports best (index, distance) and the second DISTANCE; the second index is recovered on the host from the
     // train rows only when the caller asks for it
     for (int t0 = 0; t0 < n_train; t0 += kChunk) {
         const int nt = std::min(kChunk, n_train - t0);
-        int* hn = S.h.p + 3 * (size_t)n_query;
+        int* hn = h_out + 3 * nq;
         hn[0] = n_query; hn[1] = nt;
-        HIPCHK(hipMemcpyAsync(S.n.p, hn, 2 * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(S.t.p, train + (size_t)t0 * 32, (size_t)nt * 32, hipMemcpyHostToDevice, s));
-        launch_dense_top2(S.q.p, S.t.p, S.n.p, S.n.p + 1, 1, n_query, nt, n_query, nt, S.out.p, S.out.p + n_query, S.out.p + 2 * (size_t)n_query, s,
-                          MSORB_DENSE_POPCOUNT);
-        HIPCHK(hipMemcpyAsync(S.h.p, S.out.p, (size_t)3 * n_query * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(d_n, hn, 2 * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_t, train + (size_t)t0 * 32, (size_t)nt * 32, hipMemcpyHostToDevice, s));
+        launch_dense_top2(d_q, d_t, d_n, d_n + 1, 1, n_query, nt, n_query, nt, d_out, d_out + nq, d_out + 2 * nq, s, MSORB_DENSE_POPCOUNT);
+        HIPCHK(hipMemcpyAsync(h_out, d_out, 3 * nq * sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         HIPCHK(hipGetLastError());
-        const int *bi = S.h.p, *bd = bi + n_query, *sd = bd + n_query;
+        const int *bi = h_out, *bd = bi + n_query, *sd = bd + n_query;
         for (int i = 0; i < n_query; i++) {
             // merge {best, second} of this chunk into the running pair: all of a later chunk's indices are larger, so on equal
             // distances the earlier chunk's entries stay in front
@@ -1147,48 +1099,20 @@ int msorb_hamming_dense_top2_batch_ex(int device, const uint8_t* d_query, const 
     if (n_frames < 0 || query_stride < max_query || train_stride < max_train || max_train > 2048 || max_query < 0 ||
         (n_frames > 0 && (!d_query || !d_train || !d_n_query || !d_n_train || !d_best_idx || !d_best_dist || !d_second_dist)))
         return MSORB_E_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
-    HIPCHK(hipSetDevice(device));
+    if (int rc = require_device(device)) return rc;
     // stream and timing events live with the calling thread (created once per device, released with the thread)
-    struct Ctx {
-        int device = -1;
-        hipStream_t s = nullptr;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        void release() {
-            if (device >= 0 && hipSetDevice(device) == hipSuccess) {
-                if (e0) (void)hipEventDestroy(e0);
-                if (e1) (void)hipEventDestroy(e1);
-                if (s) (void)hipStreamDestroy(s);
-            }
-            s = nullptr; e0 = e1 = nullptr; device = -1;
-        }
-        ~Ctx() { release(); }
-    };
-    static thread_local Ctx ctx;
-    if (ctx.device != device) {
-        ctx.release();
-        ctx.device = device;
-        if (hipStreamCreateWithFlags(&ctx.s, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&ctx.e0) != hipSuccess ||
-            hipEventCreate(&ctx.e1) != hipSuccess) {
-            ctx.release();
-            set_last_error("stream / event creation failed");
-            return MSORB_E_HIP;
-        }
-    }
+    static thread_local ThreadScratch ctx(true, 2);
+    if (int rc = ctx.acquire(device, 0, 0)) return rc;
     hipStream_t s = ctx.s;
-    hipError_t e = hipEventRecord(ctx.e0, s);
+    hipError_t e = hipEventRecord(ctx.ev[0], s);
     for (int r = 0; e == hipSuccess && r < (repeats > 0 ? repeats : 1); r++)
         launch_dense_top2(d_query, d_train, d_n_query, d_n_train, n_frames, query_stride, train_stride, max_query, max_train,
                           d_best_idx, d_best_dist, d_second_dist, s, formulation);
-    if (e == hipSuccess) e = hipEventRecord(ctx.e1, s);
+    if (e == hipSuccess) e = hipEventRecord(ctx.ev[1], s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) e = hipGetLastError();
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx.e0, ctx.e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ctx.ev[0], ctx.ev[1]);
     if (elapsed_ms) *elapsed_ms = ms;
     if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return MSORB_E_HIP; }
     return MSORB_OK;
@@ -1221,22 +1145,16 @@ int msorb_stereo_matches(msorb_extractor* left, msorb_extractor* right, const ms
     // MSORB_FORCE_PEER_PYRAMID takes this path with both handles on one device (test hook: a peer copy device -> same device is
     // an ordinary copy).
     if (devL != devR || extractor_force_peer_pyramid(left)) {
-        struct PeerPyr {
-            int device = -1;
-            DBuf<uint8_t> buf;
-            ~PeerPyr() { if (device >= 0 && hipSetDevice(device) == hipSuccess) buf.release(); }
-        };
-        static thread_local PeerPyr pp;
-        if (pp.device != devL) { pp.buf.release(); pp.device = devL; }
+        static thread_local ThreadScratch pp(false, 0);
         size_t off[MSORB_MAX_LEVELS], total = 0;
         for (int l = 0; l < pr.nlevels; l++) { off[l] = total; total += ((size_t)pr.lv[l].pitch * pr.lv[l].h + 255) & ~(size_t)255; }
-        if ((rc = pp.buf.ensure(total + 256))) return rc;
+        if ((rc = pp.acquire(devL, total + 256, 0))) return rc;
         HIPCHK(hipSetDevice(devR));
         HIPCHK(hipStreamSynchronize(s2));          // the right eye's extraction (its own thread has returned, normally a no-op)
         HIPCHK(hipSetDevice(devL));
         for (int l = 0; l < pr.nlevels; l++) {
-            HIPCHK(hipMemcpyPeerAsync(pp.buf.p + off[l], devL, pr.lv[l].base, devR, (size_t)pr.lv[l].pitch * pr.lv[l].h, s));
-            pr.lv[l].base = pp.buf.p + off[l];
+            HIPCHK(hipMemcpyPeerAsync(pp.d.p + off[l], devL, pr.lv[l].base, devR, (size_t)pr.lv[l].pitch * pr.lv[l].h, s));
+            pr.lv[l].base = pp.d.p + off[l];
         }
     }
     for (int i = 0; i < nL; i++)
@@ -1245,38 +1163,30 @@ int msorb_stereo_matches(msorb_extractor* left, msorb_extractor* right, const ms
         if (kpsR[i].octave < 0 || kpsR[i].octave >= pl.nlevels) return MSORB_E_INVALID;
     // scratch kept per calling thread and device (this runs once per frame: allocating and freeing six device buffers per
     // call cost more than the kernel); inputs and outputs go through pinned staging
-    struct Scratch {
-        int device = -1;
-        DBuf<uint8_t> d_in, d_out;
-        HBuf<uint8_t> h_in, h_out;
-        ~Scratch() {
-            if (device >= 0 && hipSetDevice(device) == hipSuccess) { d_in.release(); d_out.release(); h_in.release(); h_out.release(); }
-        }
-    };
-    static thread_local Scratch scr;
-    if (scr.device != devL) { scr.d_in.release(); scr.d_out.release(); scr.h_in.release(); scr.h_out.release(); scr.device = devL; }
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    static thread_local ThreadScratch scr(false, 0);
     const size_t o_kl = 0, o_dl = up16(o_kl + (size_t)nL * sizeof(msorb_keypoint)), o_kr = up16(o_dl + (size_t)nL * 32),
                  o_dr = up16(o_kr + (size_t)nR * sizeof(msorb_keypoint)), in_bytes = up16(o_dr + (size_t)nR * 32);
     const size_t out_bytes = (size_t)(3 * nL + 1) * 4;  // u_right, depth, sad[nL] + n_oob
-    if ((rc = scr.d_in.ensure(in_bytes)) || (rc = scr.h_in.ensure(in_bytes)) || (rc = scr.d_out.ensure(out_bytes)) ||
-        (rc = scr.h_out.ensure(out_bytes)))
-        return rc;
-    std::memcpy(scr.h_in.p + o_kl, kpsL, (size_t)nL * sizeof(msorb_keypoint));
-    std::memcpy(scr.h_in.p + o_dl, descL, (size_t)nL * 32);
+    if ((rc = scr.acquire(devL, in_bytes + up16(out_bytes), in_bytes + up16(out_bytes)))) return rc;
+    uint8_t* const d_in = scr.d.p;
+    uint8_t* const h_in = scr.h.p;
+    uint8_t* const d_out = scr.d.p + in_bytes;
+    uint8_t* const h_out = scr.h.p + in_bytes;
+    std::memcpy(h_in + o_kl, kpsL, (size_t)nL * sizeof(msorb_keypoint));
+    std::memcpy(h_in + o_dl, descL, (size_t)nL * 32);
     if (nR) {
-        std::memcpy(scr.h_in.p + o_kr, kpsR, (size_t)nR * sizeof(msorb_keypoint));
-        std::memcpy(scr.h_in.p + o_dr, descR, (size_t)nR * 32);
+        std::memcpy(h_in + o_kr, kpsR, (size_t)nR * sizeof(msorb_keypoint));
+        std::memcpy(h_in + o_dr, descR, (size_t)nR * 32);
     }
-    float* d_ur = reinterpret_cast<float*>(scr.d_out.p);
-    int* d_sad = reinterpret_cast<int*>(scr.d_out.p) + 2 * nL;
-    hipError_t e = small_copy(scr.d_in.p, scr.h_in.p, in_bytes, hipMemcpyHostToDevice, s);   // (pinned blocks: the copy kernel, as for the frames)
+    float* d_ur = reinterpret_cast<float*>(d_out);
+    int* d_sad = reinterpret_cast<int*>(d_out) + 2 * nL;
+    hipError_t e = small_copy(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s);   // (pinned blocks: the copy kernel, as for the frames)
     if (e == hipSuccess) e = hipMemsetAsync(d_sad + nL, 0, sizeof(int), s);
     if (e == hipSuccess) {
         StereoArgs a{};
-        a.kpL = reinterpret_cast<const msorb_keypoint*>(scr.d_in.p + o_kl);
-        a.kpR = reinterpret_cast<const msorb_keypoint*>(scr.d_in.p + o_kr);
-        a.descL = scr.d_in.p + o_dl; a.descR = scr.d_in.p + o_dr;
+        a.kpL = reinterpret_cast<const msorb_keypoint*>(d_in + o_kl);
+        a.kpR = reinterpret_cast<const msorb_keypoint*>(d_in + o_kr);
+        a.descL = d_in + o_dl; a.descR = d_in + o_dr;
         a.nL = nL; a.nR = nR; a.rows0 = pl.lv[0].h;
         for (int l = 0; l < pl.nlevels; l++) {
             a.pyrL[l] = pl.lv[l].base; a.pyrR[l] = pr.lv[l].base;
@@ -1287,13 +1197,13 @@ int msorb_stereo_matches(msorb_extractor* left, msorb_extractor* right, const ms
         a.mb = mb; a.mbf = mbf;
         a.u_right = d_ur; a.depth = d_ur + nL; a.sad = d_sad; a.n_oob = d_sad + nL;
         launch_stereo_match(a, s);
-        e = small_copy(scr.h_out.p, scr.d_out.p, out_bytes, hipMemcpyDeviceToHost, s);
+        e = small_copy(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
     if (e != hipSuccess) { set_last_error(hipGetErrorString(e)); return MSORB_E_HIP; }
-    std::memcpy(u_right, scr.h_out.p, (size_t)nL * sizeof(float));
-    std::memcpy(depth, scr.h_out.p + (size_t)nL * 4, (size_t)nL * sizeof(float));
-    const int* sad = reinterpret_cast<const int*>(scr.h_out.p) + 2 * nL;
+    std::memcpy(u_right, h_out, (size_t)nL * sizeof(float));
+    std::memcpy(depth, h_out + (size_t)nL * 4, (size_t)nL * sizeof(float));
+    const int* sad = reinterpret_cast<const int*>(h_out) + 2 * nL;
     if (n_oob) *n_oob = sad[nL];
     // median-based rejection, Frame.cc:899-912 (serial; vDistIdx is built in ascending iL order)
     std::vector<std::pair<int, int>> vDistIdx;
@@ -1342,27 +1252,6 @@ static int stereo_batch_impl(msorb_extractor* left, msorb_extractor* right, int 
         set_last_error("stereo_matches_batch: the last extract call of the handle(s) holds fewer images than n_pairs needs");
         return MSORB_E_INVALID;
     }
-    HIPCHK(hipSetDevice(dev));
-    struct Scratch {
-        int device = -1;
-        DBuf<int> sad, oob, row_begin, row_list;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            sad.release(); oob.release(); row_begin.release(); row_list.release();
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            e0 = e1 = nullptr; device = -1;
-        }
-        ~Scratch() { release(); }
-    };
-    static thread_local Scratch scr;
-    if (scr.device != dev) {
-        scr.release();
-        scr.device = dev;
-        HIPCHK(hipEventCreate(&scr.e0));
-        HIPCHK(hipEventCreate(&scr.e1));
-    }
     // a right keypoint enters rows floor(y - r) .. ceil(y + r), r = 2*scale[octave] (:762-768): at most 2r + 3 rows
     float smax = 0;
     for (int l = 0; l < pv.nlevels; l++) smax = std::max(smax, sc.scale[l]);
@@ -1372,10 +1261,13 @@ static int stereo_batch_impl(msorb_extractor* left, msorb_extractor* right, int 
         set_last_error("stereo_matches_batch: image too tall for the row table in LDS");
         return MSORB_E_INVALID;
     }
-    if ((rc = scr.sad.ensure((size_t)n_pairs * capacity)) || (rc = scr.oob.ensure((size_t)n_pairs)) ||
-        (rc = scr.row_begin.ensure((size_t)n_pairs * (rows0 + 1))) || (rc = scr.row_list.ensure((size_t)n_pairs * row_cap * 2)))
-        return rc;
-    int* oob = d_n_oob ? d_n_oob : scr.oob.p;
+    // per-thread grow-only scratch: [sad | oob | row_begin | row_list] and the two timing events (the launches go on the handle's stream)
+    const size_t o_oob = up16((size_t)n_pairs * capacity * 4), o_rb = o_oob + up16((size_t)n_pairs * 4),
+                 o_rl = o_rb + up16((size_t)n_pairs * (rows0 + 1) * 4), bytes = o_rl + (size_t)n_pairs * row_cap * 2 * 4;
+    static thread_local ThreadScratch scr(false, 2);
+    if ((rc = scr.acquire(dev, bytes, 0))) return rc;
+    int* const d_sad = reinterpret_cast<int*>(scr.d.p);
+    int* const oob = d_n_oob ? d_n_oob : reinterpret_cast<int*>(scr.d.p + o_oob);
     StereoBatchArgs b{};
     b.pair_step = step;
     b.A.kpL = d_kps_left;
@@ -1396,17 +1288,17 @@ static int stereo_batch_impl(msorb_extractor* left, msorb_extractor* right, int 
         b.img_strideR[l] = right ? pr.lv[l].img_stride : pv.lv[l].img_stride;
     }
     b.A.mb = mb; b.A.mbf = mbf;
-    b.A.u_right = d_u_right; b.A.depth = d_depth; b.A.sad = scr.sad.p; b.A.n_oob = oob;
+    b.A.u_right = d_u_right; b.A.depth = d_depth; b.A.sad = d_sad; b.A.n_oob = oob;
     b.capacity = capacity;
-    b.row_begin = scr.row_begin.p; b.row_list = reinterpret_cast<int2*>(scr.row_list.p); b.row_cap = row_cap;
+    b.row_begin = reinterpret_cast<int*>(scr.d.p + o_rb); b.row_list = reinterpret_cast<int2*>(scr.d.p + o_rl); b.row_cap = row_cap;
     if (right) HIPCHK(hipStreamSynchronize(s_r));  // the right handle's pyramid was built on its own stream
     HIPCHK(hipMemsetAsync(oob, 0, (size_t)n_pairs * sizeof(int), s));
-    HIPCHK(hipEventRecord(scr.e0, s));
+    HIPCHK(hipEventRecord(scr.ev[0], s));
     launch_stereo_match_batch(b, n_pairs, max_left, s);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(scr.e1, s));
+    HIPCHK(hipEventRecord(scr.ev[1], s));
     HIPCHK(hipStreamSynchronize(s));
-    if (elapsed_ms) HIPCHK(hipEventElapsedTime(elapsed_ms, scr.e0, scr.e1));
+    if (elapsed_ms) HIPCHK(hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]));
     return MSORB_OK;
 }
 

@@ -335,13 +335,13 @@ struct MpLayout {
 
 // state the local-points chain keeps on the frame handle
 struct msorb_frame_track {
-    DBuf<uint8_t> d_in, d_out;
-    DBuf<msorb_frustum> d_frustum;
-    HBuf<uint8_t> h_in, h_out;
+    DevBuf<uint8_t> d_in, d_out;
+    DevBuf<msorb_frustum> d_frustum;
+    PinBuf<uint8_t> h_in, h_out;
     hipEvent_t ev_in = nullptr;
     // TrackWithMotionModel's search: the last frame's points, resident between calls (msorb_frame_set_last_points)
-    DBuf<uint8_t> d_last, d_last_out;
-    HBuf<uint8_t> h_last, h_last_out;
+    DevBuf<uint8_t> d_last, d_last_out;
+    PinBuf<uint8_t> h_last, h_last_out;
     std::vector<float> last_angle;   // host copies the replay reads
     int last_n = -1;                 // -1: no table set
     hipEvent_t ev_last = nullptr;
@@ -988,56 +988,27 @@ int msorb_track_batch(int device, int n_frames, const msorb_keypoint* d_keypoint
     if (n_frames == 0) return MSORB_OK;
     for (int b = 0; b < n_frames; b++)
         if (frusta[b].n_scale_levels < 1 || frusta[b].n_scale_levels > nlevels) { set_last_error("frustum scale levels out of range"); return MSORB_E_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
-    HIPCHK(hipSetDevice(device));
-    struct Scratch {
-        int device = -1;
-        hipStream_t s = nullptr;
-        hipEvent_t ev[4] = {};
-        DBuf<KpLite> kp;
-        DBuf<uint8_t> desc, occ, in_view;
-        DBuf<int> cell_begin, cell_idx, level;
-        DBuf<WinQuery> q;
-        DBuf<float> proj;
-        DBuf<msorb_frustum> fr;
-        DBuf<unsigned long long> cnt;
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            kp.release(); desc.release(); occ.release(); in_view.release(); cell_begin.release(); cell_idx.release(); level.release();
-            q.release(); proj.release(); fr.release(); cnt.release();
-            for (auto& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-            if (s) (void)hipStreamDestroy(s);
-            s = nullptr; device = -1;
-        }
-        ~Scratch() { release(); }
-    };
-    static thread_local Scratch S;
-    if (S.device != device) {
-        S.release();
-        S.device = device;   // release() frees on this device; a failure below releases again and leaves device == -1
-        hipError_t e = hipStreamCreateWithFlags(&S.s, hipStreamNonBlocking);
-        for (auto& ev : S.ev)
-            if (e == hipSuccess) e = hipEventCreate(&ev);
-        if (e != hipSuccess) {
-            S.release();
-            set_last_error(std::string("msorb_track_batch: stream / event creation: ") + hipGetErrorString(e));
-            return MSORB_E_HIP;
-        }
-    }
+    if (int rc = require_device(device)) return rc;
+    // per-thread grow-only scratch: one device block [kp | desc | occ | cell_begin | cell_idx | frusta | queries | projections | levels |
+    // in_view | pair count], a stream and four timing events
     const size_t B = (size_t)n_frames, cap = (size_t)capacity, M = (size_t)m;
+    const size_t o_desc = up16(B * cap * sizeof(KpLite)), o_occ = o_desc + up16(B * cap * 32), o_cb = o_occ + up16(B * cap),
+                 o_ci = o_cb + up16(B * (kNCell + 1) * 4), o_fr = o_ci + up16(B * cap * 4), o_q = o_fr + up16(B * sizeof(msorb_frustum)),
+                 o_proj = o_q + up16(B * M * sizeof(WinQuery)), o_level = o_proj + up16(5 * B * M * 4), o_iv = o_level + up16(B * M * 4),
+                 o_cnt = o_iv + up16(B * M), bytes = o_cnt + sizeof(unsigned long long);
+    static thread_local ThreadScratch S(true, 4);
     int rc;
-    if ((rc = S.kp.ensure(B * cap)) || (rc = S.desc.ensure(B * cap * 32)) || (rc = S.occ.ensure(B * cap)) ||
-        (rc = S.cell_begin.ensure(B * (kNCell + 1))) || (rc = S.cell_idx.ensure(B * cap)) || (rc = S.fr.ensure(B)) ||
-        (rc = S.q.ensure(B * M)) || (rc = S.proj.ensure(5 * B * M)) || (rc = S.level.ensure(B * M)) ||
-        (rc = S.in_view.ensure(B * M)) || (rc = S.cnt.ensure(1)))
-        return rc;
+    if ((rc = S.acquire(device, bytes, 0))) return rc;
+    KpLite* const d_kp = reinterpret_cast<KpLite*>(S.d.p);
+    uint8_t* const d_desc = S.d.p + o_desc;
+    uint8_t* const d_occ = S.d.p + o_occ;
+    msorb_frustum* const d_fr = reinterpret_cast<msorb_frustum*>(S.d.p + o_fr);
+    WinQuery* const d_q = reinterpret_cast<WinQuery*>(S.d.p + o_q);
+    float* const d_proj = reinterpret_cast<float*>(S.d.p + o_proj);
+    unsigned long long* const d_cnt = reinterpret_cast<unsigned long long*>(S.d.p + o_cnt);
     hipStream_t s = S.s;
-    HIPCHK(hipMemcpyAsync(S.fr.p, frusta, B * sizeof(msorb_frustum), hipMemcpyHostToDevice, s));
-    if (n_pairs) HIPCHK(hipMemsetAsync(S.cnt.p, 0, sizeof(unsigned long long), s));
+    HIPCHK(hipMemcpyAsync(d_fr, frusta, B * sizeof(msorb_frustum), hipMemcpyHostToDevice, s));
+    if (n_pairs) HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), s));
     GridArgs G{};
     G.kps = d_keypoints; G.desc = d_descriptors; G.u_right = d_u_right;
     G.src_stride = (size_t)frame_step * cap; G.ur_stride = cap;
@@ -1045,36 +1016,36 @@ int msorb_track_batch(int device, int n_frames, const msorb_keypoint* d_keypoint
     G.minX = min_x; G.minY = min_y;
     G.gridWInv = static_cast<float>(kGridCols) / (max_x - min_x);
     G.gridHInv = static_cast<float>(kGridRows) / (max_y - min_y);
-    G.kp = S.kp.p; G.desc_out = S.desc.p; G.occ = S.occ.p;
-    G.cell_begin = d_cell_begin ? d_cell_begin : S.cell_begin.p;
-    G.cell_idx = d_cell_idx ? d_cell_idx : S.cell_idx.p;
+    G.kp = d_kp; G.desc_out = d_desc; G.occ = d_occ;
+    G.cell_begin = d_cell_begin ? d_cell_begin : reinterpret_cast<int*>(S.d.p + o_cb);
+    G.cell_idx = d_cell_idx ? d_cell_idx : reinterpret_cast<int*>(S.d.p + o_ci);
     G.n_out = nullptr; G.dst_stride = capacity;
     HIPCHK(hipEventRecord(S.ev[0], s));
     if ((rc = launch_frame_grid(G, n_frames, s))) return rc;
     HIPCHK(hipEventRecord(S.ev[1], s));
     if (m > 0) {
         LocalPointsArgs A{};
-        A.frustum = S.fr.p; A.cos_limit = viewing_cos_limit; A.m = m;
+        A.frustum = d_fr; A.cos_limit = viewing_cos_limit; A.m = m;
         A.pos_w = d_pos_w; A.normal = d_normal; A.max_d = d_max_distance; A.min_d = d_min_distance; A.flags = d_flags;
         for (int l = 0; l < MSORB_MAX_LEVELS; l++) A.scale[l] = l < nlevels ? scale_factors[l] : 0.0f;
         A.th = th; A.far_points = far_points; A.th_far = th_far_points;
-        A.q = S.q.p;
-        A.proj_x = S.proj.p; A.proj_y = S.proj.p + B * M; A.proj_xr = S.proj.p + 2 * B * M; A.depth = S.proj.p + 3 * B * M;
-        A.view_cos = S.proj.p + 4 * B * M; A.level = S.level.p;
-        A.in_view = d_track_in_view ? d_track_in_view : S.in_view.p;
+        A.q = d_q;
+        A.proj_x = d_proj; A.proj_y = d_proj + B * M; A.proj_xr = d_proj + 2 * B * M; A.depth = d_proj + 3 * B * M;
+        A.view_cos = d_proj + 4 * B * M; A.level = reinterpret_cast<int*>(S.d.p + o_level);
+        A.in_view = d_track_in_view ? d_track_in_view : S.d.p + o_iv;
         hipLaunchKernelGGL(local_points_kernel, dim3((unsigned)((M + 255) / 256), (unsigned)n_frames), dim3(256), 0, s, A);
         HIPCHK(hipEventRecord(S.ev[2], s));
         FrameView V{};
-        V.kp = S.kp.p; V.desc = S.desc.p; V.cell_begin = G.cell_begin; V.cell_idx = G.cell_idx; V.occupied = S.occ.p;
+        V.kp = d_kp; V.desc = d_desc; V.cell_begin = G.cell_begin; V.cell_idx = G.cell_idx; V.occupied = d_occ;
         V.minX = min_x; V.minY = min_y; V.gridWInv = G.gridWInv; V.gridHInv = G.gridHInv; V.n = capacity;
         for (int l = 0; l < MSORB_MAX_LEVELS; l++) V.inv_sigma2[l] = 0.0f;
         static_assert(sizeof(TopK) == 16 * sizeof(int), "d_topk layout");
         const float mid = scale_factors[nlevels / 2];
-        launch_window_topk(V, S.q.p, d_mp_desc, 0, m, reinterpret_cast<TopK*>(d_topk), s, n_frames, capacity, m,
-                           n_pairs ? S.cnt.p : nullptr, window_lanes_for(4.0f * th * mid, G.gridWInv, G.gridHInv));
+        launch_window_topk(V, d_q, d_mp_desc, 0, m, reinterpret_cast<TopK*>(d_topk), s, n_frames, capacity, m,
+                           n_pairs ? d_cnt : nullptr, window_lanes_for(4.0f * th * mid, G.gridWInv, G.gridHInv));
         HIPCHK(hipEventRecord(S.ev[3], s));
     }
-    if (n_pairs) HIPCHK(hipMemcpyAsync(n_pairs, S.cnt.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (n_pairs) HIPCHK(hipMemcpyAsync(n_pairs, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     HIPCHK(hipGetLastError());
     if (elapsed_ms) {

@@ -14,9 +14,9 @@
 #include <vector>
 
 #include "../../include/msorb.h"
+#include "hip_host.h"
 
 namespace msorb {
-void set_last_error(const std::string& s);
 
 // exclusive scan of one int per thread over a workgroup of up to 1024 threads (wave scans + the wave totals in LDS)
 __device__ __forceinline__ int block_exclusive_scan(int v, int* wave_tot /* [16] shared */, int* total) {
@@ -353,11 +353,7 @@ extern "C" int msorb_visibility_csr(int device, int n_window_kf, const int* kf_s
         set_last_error("msorb_visibility_csr: null argument");
         return MSORB_E_INVALID;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
-        set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
-        return MSORB_E_NO_DEVICE;
-    }
+    if (int rc = require_device(device)) return rc;
     static const bool vis_timing = getenv("MSORB_VIS_TIMING") != nullptr;   // read once per process: wall-clock breakdown on stderr
     auto now = [] { return std::chrono::steady_clock::now(); };
     std::chrono::steady_clock::time_point t1, t2, t3, t4;
@@ -374,52 +370,6 @@ extern "C" int msorb_visibility_csr(int device, int n_window_kf, const int* kf_s
     }
     t1 = now();
     int rc = MSORB_OK;
-    if (hipSetDevice(device) != hipSuccess) return MSORB_E_HIP;
-    // Scratch kept per calling thread (grow-only), a private non-blocking stream, pinned staging.  Shape of a call: the
-    // inputs are packed into ONE pinned block and uploaded with one copy; every kernel takes the sizes it depends on (columns,
-    // rows / non-zeros of the window part) from device scalars and is launched over host-side upper bounds, so nothing
-    // waits for the host; the six scalars come back with the first synchronisation, the six output arrays (exact sizes)
-    // with the second.  (Round 2: nine pageable uploads and about ten synchronous read-backs, 0.74 ms for a 30-keyframe window.)
-    struct Scratch {
-        int device = -1;
-        hipStream_t s = nullptr;
-        void* p[2] = {nullptr, nullptr};
-        size_t cap[2] = {0, 0};
-        void* h = nullptr;
-        size_t hcap = 0;
-        void release() {
-            if (device < 0 || hipSetDevice(device) != hipSuccess) return;
-            for (int i = 0; i < 2; i++) { if (p[i]) (void)hipFree(p[i]); p[i] = nullptr; cap[i] = 0; }
-            if (h) (void)hipHostFree(h);
-            h = nullptr; hcap = 0;
-            if (s) (void)hipStreamDestroy(s);
-            s = nullptr; device = -1;
-        }
-        hipError_t ensure(int i, size_t bytes) {
-            if (bytes <= cap[i]) return hipSuccess;
-            if (p[i]) (void)hipFree(p[i]);
-            p[i] = nullptr; cap[i] = 0;
-            const hipError_t e = hipMalloc(&p[i], bytes + bytes / 4);
-            if (e == hipSuccess) cap[i] = bytes + bytes / 4;
-            return e;
-        }
-        hipError_t ensure_host(size_t bytes) {
-            if (bytes <= hcap) return hipSuccess;
-            if (h) (void)hipHostFree(h);
-            h = nullptr; hcap = 0;
-            const hipError_t e = hipHostMalloc(&h, bytes + bytes / 4, hipHostMallocDefault);
-            if (e == hipSuccess) hcap = bytes + bytes / 4;
-            return e;
-        }
-        ~Scratch() { release(); }
-    };
-    static thread_local Scratch scr;
-    if (scr.device != device) {
-        scr.release();
-        if (hipStreamCreateWithFlags(&scr.s, hipStreamNonBlocking) != hipSuccess) { set_last_error("stream creation failed"); return MSORB_E_HIP; }
-        scr.device = device;
-    }
-    hipStream_t const st = scr.s;
     // host-side upper bounds of the result sizes
     int n_outside = 0;   // keyframes outside the window: bound of the kind-2 rows
     for (int k = 0; k < n_kf_total; k++) n_outside += !kf_in_window[k];
@@ -445,12 +395,19 @@ extern "C" int msorb_visibility_csr(int device, int n_window_kf, const int* kf_s
                  o_pack = take((size_t)8 + 4 * rows_max + cols_max + nnz_max);
     const size_t bitmap_bytes = (size_t)n_outside * words * sizeof(unsigned);
     const size_t pack_max = (size_t)8 + 4 * rows_max + cols_max + nnz_max;
-    VCHK(scr.ensure(0, std::max<size_t>(off, 1) * sizeof(int)));
-    VCHK(scr.ensure(1, std::max<size_t>(bitmap_bytes, 4)));
-    VCHK(scr.ensure_host(std::max<size_t>(std::max(n_in, pack_max), 1) * sizeof(int)));
-    d = static_cast<int*>(scr.p[0]);
+    // Scratch kept per calling thread (grow-only), a private non-blocking stream, pinned staging.  Shape of a call: the
+    // inputs are packed into ONE pinned block and uploaded with one copy; every kernel takes the sizes it depends on (columns,
+    // rows / non-zeros of the window part) from device scalars and is launched over host-side upper bounds, so nothing
+    // waits for the host; the six scalars come back with the first synchronisation, the six output arrays (exact sizes)
+    // with the second.  (Round 2: nine pageable uploads and about ten synchronous read-backs, 0.74 ms for a 30-keyframe window.)
+    // Device block: [the int arrays above | the outside-keyframe bitmaps].
+    static thread_local ThreadScratch scr(true, 0);
+    const size_t o_bitmap = up16(off * sizeof(int));
+    if ((rc = scr.acquire(device, o_bitmap + std::max<size_t>(bitmap_bytes, 4), std::max(n_in, pack_max) * sizeof(int)))) return rc;
+    hipStream_t const st = scr.s;
+    d = reinterpret_cast<int*>(scr.d.p);
     {
-        int* h = static_cast<int*>(scr.h);
+        int* h = reinterpret_cast<int*>(scr.h.p);
         std::memcpy(h + o_slot_begin, kf_slot_begin, (size_t)(n_window_kf + 1) * sizeof(int));
         if (S) {
             std::memcpy(h + o_slot_point, slot_point, (size_t)S * sizeof(int));
@@ -473,7 +430,7 @@ extern "C" int msorb_visibility_csr(int device, int n_window_kf, const int* kf_s
     {
         const uint8_t* d_inwin = reinterpret_cast<const uint8_t*>(d + o_inwin);
         float* d_rhs = reinterpret_cast<float*>(d + o_rhs);
-        unsigned* d_bitmap = static_cast<unsigned*>(scr.p[1]);
+        unsigned* d_bitmap = reinterpret_cast<unsigned*>(scr.d.p + o_bitmap);
         // 9 launches (round 2: 12 kernels + 3 memsets): init | first + window-keyframe counts | first-flags per block | columns |
         // window-keyframe rows + outside-keyframe counts | their scan | their bitmaps | their rows | pack
         const size_t bitmap_words = (cols_max && n_outside) ? bitmap_bytes / sizeof(unsigned) : 0;
@@ -512,7 +469,7 @@ extern "C" int msorb_visibility_csr(int device, int n_window_kf, const int* kf_s
                                d + o_kfrow, d + o_kfoff, d + o_num_mps, N, words, d_bitmap, d + o_scal, d + o_rowbegin,
                                d + o_rowkind, d + o_rowowner, d_rhs, d + o_colidx);
         }
-        int* h = static_cast<int*>(scr.h);
+        int* h = reinterpret_cast<int*>(scr.h.p);
         hipLaunchKernelGGL(vis_pack_kernel, dim3((unsigned)std::min<size_t>((pack_max + 255) / 256, 1024)), dim3(256), 0, st, d + o_scal,
                            d + o_rowbegin, d + o_rowkind, d + o_rowowner, reinterpret_cast<const int*>(d_rhs), d + o_colpoint,
                            d + o_colidx, d + o_pack);
