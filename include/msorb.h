@@ -46,7 +46,7 @@ int msorb_device_memory(int device, size_t* free_bytes, size_t* total_bytes);
  * minor only appends entry points (or appends `_ex` forms with more parameters), a new major changes or removes one.  The host
  * classes (host/ORBextractor.cc, host/ORBmatcher_device.h) and the Python mirror compare msorb_abi_version() with the header
  * they were compiled against and refuse a library with another major or an older minor (msorb_abi_compatible). */
-#define MSORB_ABI_VERSION 6001
+#define MSORB_ABI_VERSION 6002
 int msorb_abi_version(void);
 /* 1 if a caller compiled against `header_version` may use this library (same major, library minor >= header minor). */
 int msorb_abi_compatible(int header_version);
@@ -63,6 +63,30 @@ void msorb_set_fatal_callback(msorb_fatal_fn fn, void* user);
 void msorb_notify_fatal(int code, const char* what);
 
 /* ------------------------------------------------------------------------------------------------
+ * Host-memory admission — images the per-frame entries read IN PLACE.  Since ABI 6002.
+ *
+ * The reference reads the caller's cv::Mat where it lies (ORBextractor.cc:1190).  Here a per-frame entry (msorb_extract,
+ * msorb_extract_pair, msorb_extract_stereo and the frame / tracking entries on it, msorb_extract_stereo_split) looks each image's
+ * byte range [image, image + (rows-1)*stride + cols) up in a process-wide table of pinned host memory.  A range wholly inside ONE
+ * entry is read by the upload kernel straight from the caller's memory: no staging copy, and both eyes of a stereo frame in one
+ * launch.  Anything else — pageable memory, a range that overhangs its entry by one byte, an entry that has left the table — takes
+ * the staged path, with identical results.  The decision is per image.  The table is the only source of host addresses a kernel
+ * dereferences: nothing is remembered by raw pointer, so memory that was freed and handed out again never looks pinned.
+ * An entry is in use from a call's lookup until that call has synchronised its stream: msorb_host_free / msorb_host_unregister
+ * of an entry in use return MSORB_E_INVALID and free nothing.  Thread safe; usable before any handle exists; without a HIP
+ * device the alloc / register entries return MSORB_E_NO_DEVICE.  MSORB_INPUT_DIRECT=0 (read when a handle is created) sends
+ * every image of that handle down the staged path.
+ * ---------------------------------------------------------------------------------------------- */
+int msorb_host_alloc(size_t bytes, void** out);        /* hipHostMalloc, portable + mapped; enters the table */
+int msorb_host_free(void* p);                          /* leaves the table, then hipHostFree */
+/* Pageable memory: hipHostRegister (portable + mapped), owned by the table and unpinned by msorb_host_unregister.  Memory the
+ * application pinned itself: verified once, here, with hipPointerGetAttributes, and adopted (never unpinned by the library).
+ * A range that overlaps an entry is refused. */
+int msorb_host_register(void* p, size_t bytes);
+int msorb_host_unregister(void* p);
+int msorb_host_admitted(const void* p, size_t bytes);  /* 1: [p, p+bytes) lies wholly inside one table entry; else 0 */
+
+/* ------------------------------------------------------------------------------------------------
  * Extractor — replaces ORB_SLAM3::ORBextractor (include/ORBextractor.h:43-109, src/ORBextractor.cc)
  * ---------------------------------------------------------------------------------------------- */
 typedef struct msorb_extractor msorb_extractor;
@@ -74,6 +98,17 @@ typedef struct msorb_extractor msorb_extractor;
 int msorb_extractor_create(int nfeatures, float scale_factor, int nlevels, int ini_th_fast, int min_th_fast,
                            int device, msorb_extractor** out);
 void msorb_extractor_destroy(msorb_extractor* h);
+
+/* Where the level-0 images of the per-frame entries came from (host-memory admission above).  Since ABI 6002. */
+typedef struct msorb_input_stats {   /* since the handle was created */
+    uint64_t images_direct;    /* level-0 images uploaded straight from the caller's memory */
+    uint64_t images_staged;    /* level-0 images copied by the host into the handle's staging plane (msorb_stage_image counts here, at
+                                  stage time) */
+    uint64_t bytes_staged;     /* bytes those host copies moved (the copies that refill the host's level 0 behind a direct upload —
+                                  msorb_pyramid_level — are not in front of the upload and are not counted) */
+    uint64_t upload_launches;  /* kernel launches / hipMemcpyAsync calls that moved level-0 images to the device */
+} msorb_input_stats;
+int msorb_extractor_input_stats(const msorb_extractor* h, msorb_input_stats* out);
 
 /* GetScaleFactors / GetInverseScaleFactors / GetScaleSigmaSquares / GetInverseScaleSigmaSquares
  * (ORBextractor.h:61-81) and mnFeaturesPerLevel; each array has nlevels entries; NULL = skip. */
@@ -129,7 +164,9 @@ int msorb_pyramid_batch(msorb_extractor* h, const uint8_t* d_images, int n_image
 /* mvImagePyramid[level] (ORBextractor.h:83) of the last msorb_extract() call as a host-visible plane
  * (interior pixels; the 19-px border of ORBextractor.cc:1185-1191 is not materialised).  The memory
  * is owned by the handle and valid until the next extract call.  Without msorb_extractor_set_host_pyramid the first
- * call after an extraction copies the whole pyramid synchronously (8 x hipMemcpy2D). */
+ * call after an extraction copies the whole pyramid synchronously (8 x hipMemcpy2D).  Level 0 is the handle's copy also when the
+ * image was read in place from admitted memory (never the caller's pointer): with msorb_extractor_set_host_pyramid the host
+ * copies it while the device works, otherwise it comes back from the device with the other levels. */
 int msorb_pyramid_level(msorb_extractor* h, int level, const uint8_t** data, int* rows, int* cols, size_t* stride);
 
 /* enable != 0: every msorb_extract() call also brings levels 1.. of the pyramid to pinned host memory, with ONE asynchronous

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "hip_host.h"
+#include "host_admission.h"
 #include "orb_device.h"
 #include "gauss7_stream_device.h"
 #include "matcher_device.h"
@@ -194,6 +195,9 @@ struct msorb_extractor {
     PinBuf<SelRec> h_sel;
     PinBuf<uint8_t> h_pyr, h_img_pin, h_out_pin, h_gather;
     bool h_pyr_valid = false;
+    // level-0 input (msorb_extractor_input_stats): images read in place from admitted host memory against images staged by the host
+    bool input_direct = true;   // MSORB_INPUT_DIRECT=0 (read once, at creation): every image takes the staged path
+    msorb_input_stats in_stats{};
 
     // last call
     PyramidView last_pyr{}, last_blur{};
@@ -217,6 +221,115 @@ int frame_copy(msorb_extractor*, void* dst, const void* src, size_t bytes, hipMe
     return MSORB_OK;
 }
 int capacity_of(const msorb_extractor* h) { return h->P.nfeatures + (3 + 16) * h->P.nlevels; }
+
+// ---- the process's host-memory admission table (host_admission.h) on the HIP runtime
+bool have_hip_device() {
+    int n = 0;
+    if (hipGetDeviceCount(&n) == hipSuccess && n > 0) return true;
+    (void)hipGetLastError();
+    set_last_error("no usable HIP device (libmsorb has no CPU fallback)");
+    return false;
+}
+int hip_pin_error(const char* what, hipError_t e) {
+    (void)hipGetLastError();
+    set_last_error(std::string(what) + ": " + hipGetErrorString(e));
+    return e == hipErrorInvalidValue || e == hipErrorHostMemoryAlreadyRegistered ? MSORB_E_INVALID : MSORB_E_HIP;
+}
+int adm_alloc(size_t bytes, void** out) {
+    if (!have_hip_device()) return MSORB_E_NO_DEVICE;
+    const hipError_t e = hipHostMalloc(out, bytes, hipHostMallocPortable | hipHostMallocMapped);
+    return e == hipSuccess ? MSORB_OK : hip_pin_error("hipHostMalloc", e);
+}
+int adm_free(void* p) {
+    const hipError_t e = hipHostFree(p);
+    return e == hipSuccess ? MSORB_OK : hip_pin_error("hipHostFree", e);
+}
+// Pageable memory is pinned here and owned; memory its owner pinned already (hipHostMalloc / hipHostRegister of the application) is
+// verified now, once, and adopted: both ends of the range must be pinned host memory of one allocation.
+int adm_pin(void* p, size_t bytes, int* adopted) {
+    *adopted = 0;
+    if (!have_hip_device()) return MSORB_E_NO_DEVICE;
+    hipPointerAttribute_t first{}, last{};
+    hipError_t e = hipPointerGetAttributes(&first, p);
+    if (e != hipSuccess) (void)hipGetLastError();   // (older runtimes answer pageable memory with an error instead of "unregistered")
+    if (e == hipSuccess && first.type == hipMemoryTypeHost) {
+        void* base = nullptr;
+        size_t size = 0;
+        const bool ranged = hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, first.devicePointer) == hipSuccess;
+        if (!ranged) (void)hipGetLastError();
+        e = hipPointerGetAttributes(&last, static_cast<uint8_t*>(p) + bytes - 1);
+        const bool inside = !ranged || (static_cast<uint8_t*>(first.devicePointer) >= static_cast<uint8_t*>(base) &&
+                                        static_cast<uint8_t*>(first.devicePointer) + bytes <= static_cast<uint8_t*>(base) + size);
+        if (e != hipSuccess || last.type != hipMemoryTypeHost || !inside) {
+            (void)hipGetLastError();
+            set_last_error("msorb_host_register: the range starts in pinned memory and does not lie wholly inside that allocation");
+            return MSORB_E_INVALID;
+        }
+        *adopted = 1;
+        return MSORB_OK;
+    }
+    if (e == hipSuccess && first.type != hipMemoryTypeUnregistered) {
+        set_last_error("msorb_host_register: not host memory");
+        return MSORB_E_INVALID;
+    }
+    e = hipHostRegister(p, bytes, hipHostRegisterPortable | hipHostRegisterMapped);
+    return e == hipSuccess ? MSORB_OK : hip_pin_error("hipHostRegister", e);
+}
+int adm_unpin(void* p) {
+    const hipError_t e = hipHostUnregister(p);
+    return e == hipSuccess ? MSORB_OK : hip_pin_error("hipHostUnregister", e);
+}
+HostAdmission& admission() {
+    static HostAdmission* const t = new HostAdmission(HostPinBackend{adm_alloc, adm_free, adm_pin, adm_unpin});   // (never destroyed: entries outlive static destructors)
+    return *t;
+}
+
+// The level-0 sources of one per-frame call.  admit() looks an image's byte range up in the admission table and, when it lies
+// wholly inside one entry, holds that entry and records the device-visible address of the image (hipHostGetDevicePointer of the
+// entry's base on the current device, asked once per entry and device and kept IN the entry, plus the image's offset).  The holds
+// last until the call's stream has been synchronised: done() after the call's own synchronisation; on an early return the
+// destructor synchronises the streams a kernel was launched on before it lets go.
+struct DirectInputs {
+    Level0Src src[2] = {};
+    HostAdmission::Entry* held[2] = {nullptr, nullptr};
+    hipStream_t launched[2] = {nullptr, nullptr};
+    int n_launched = 0;
+    bool admit(const msorb_extractor* h, int i, const uint8_t* image, int rows, int cols, size_t stride) {
+        if (!h->input_direct) return false;
+        HostAdmission::Entry* e = admission().hold(image, (size_t)(rows - 1) * stride + (size_t)cols);
+        if (!e) return false;
+        uintptr_t dev = h->device < HostAdmission::kMaxDevices ? e->device_base[h->device].load(std::memory_order_relaxed) : 0;
+        if (!dev) {
+            void* d = nullptr;
+            if (hipHostGetDevicePointer(&d, reinterpret_cast<void*>(e->base), 0) != hipSuccess || !d) {   // not mapped on this device: staged
+                (void)hipGetLastError();
+                HostAdmission::release(e);
+                return false;
+            }
+            dev = reinterpret_cast<uintptr_t>(d);
+            if (h->device < HostAdmission::kMaxDevices) e->device_base[h->device].store(dev, std::memory_order_relaxed);
+        }
+        held[i] = e;
+        src[i] = Level0Src{reinterpret_cast<const uint8_t*>(dev + (reinterpret_cast<uintptr_t>(image) - e->base)), stride};
+        return true;
+    }
+    bool direct(int i) const { return held[i] != nullptr; }
+    void upload(int n_images, uint8_t* dst, size_t dst_image_stride, int dst_pitch, int rows, int cols, hipStream_t s) {
+        launch_upload_level0(src, n_images, dst, dst_image_stride, dst_pitch, rows, cols, s);
+        if (n_launched < 2) launched[n_launched++] = s;
+    }
+    void done() {   // the streams have been synchronised
+        n_launched = 0;
+        for (auto& e : held) { HostAdmission::release(e); e = nullptr; }
+    }
+    ~DirectInputs() {
+        for (int k = 0; k < n_launched; k++) (void)hipStreamSynchronize(launched[k]);
+        done();
+    }
+};
+void copy_rows(uint8_t* dst, size_t dst_pitch, const uint8_t* src, size_t stride, int rows, int cols) {
+    for (int y = 0; y < rows; y++) memcpy(dst + (size_t)y * dst_pitch, src + (size_t)y * stride, cols);
+}
 
 int ensure_geometry(msorb_extractor* h, int rows, int cols) {
     if (h->geom_valid && h->G.rows == rows && h->G.cols == cols) return MSORB_OK;
@@ -784,6 +897,34 @@ void msorb_notify_fatal(int code, const char* what) {
     if (fn) fn(code, what ? what : "", user);
 }
 
+int msorb_host_alloc(size_t bytes, void** out) {
+    const int rc = admission().alloc(bytes, out);
+    if (rc == MSORB_E_INVALID) set_last_error("msorb_host_alloc: bad arguments");
+    return rc;
+}
+int msorb_host_free(void* p) {
+    const int rc = admission().free(p);
+    if (rc == MSORB_E_INVALID) set_last_error("msorb_host_free: not a block of msorb_host_alloc, or a call that reads it is still running");
+    return rc;
+}
+int msorb_host_register(void* p, size_t bytes) {
+    set_last_error("");
+    const int rc = admission().add(p, bytes);
+    if (rc == MSORB_E_INVALID && !*msorb_last_error()) set_last_error("msorb_host_register: empty range, or it overlaps an admitted one");
+    return rc;
+}
+int msorb_host_unregister(void* p) {
+    const int rc = admission().remove(p);
+    if (rc == MSORB_E_INVALID) set_last_error("msorb_host_unregister: not a registered range, or a call that reads it is still running");
+    return rc;
+}
+int msorb_host_admitted(const void* p, size_t bytes) { return admission().admitted(p, bytes) ? 1 : 0; }
+int msorb_extractor_input_stats(const msorb_extractor* h, msorb_input_stats* out) {
+    if (!h || !out) return MSORB_E_INVALID;
+    *out = h->in_stats;
+    return MSORB_OK;
+}
+
 int msorb_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -847,6 +988,7 @@ int msorb_extractor_create(int nfeatures, float scale_factor, int nlevels, int i
         // launch, 1: inside FAST's launch, 0: side stream); MSORB_FRAME_COMPACT=0: candidate scan + gather as two launches
         h->knobs.frame_fuse = (e = getenv("MSORB_FRAME_FUSE")) ? std::max(0, std::min(2, atoi(e))) : 2;
         h->knobs.frame_compact = !((e = getenv("MSORB_FRAME_COMPACT")) && e[0] == '0');
+        h->input_direct = !((e = getenv("MSORB_INPUT_DIRECT")) && e[0] == '0');   // A/B switch of the direct level-0 upload
     }
     if (hipDeviceGetAttribute(&h->lds_per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || h->lds_per_block <= 0)
         h->lds_per_block = 64 * 1024;
@@ -1029,8 +1171,18 @@ int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, 
     const bool staged = h->h_img_pin.p && image == h->h_img_pin.p && stride == (size_t)g0.pitch;   // msorb_stage_image did the copy
     if ((rc = h->h_img_pin.ensure(staged ? 1 : (size_t)g0.pitch * rows))) return rc;
     if ((rc = h->h_out_pin.ensure((size_t)cap * (sizeof(msorb_keypoint) + 32)))) return rc;
-    if (!staged)
-        for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + (size_t)y * g0.pitch, image + (size_t)y * stride, cols);
+    // An image in admitted host memory (msorb_host_alloc / msorb_host_register) is read where it lies by the upload kernel: no copy
+    // in front of the upload.  Everything else is staged as before.
+    DirectInputs in;
+    const bool direct = !staged && in.admit(h, 0, image, rows, cols, stride);
+    if (direct) {
+        h->in_stats.images_direct++;
+    } else if (!staged) {
+        copy_rows(h->h_img_pin.p, g0.pitch, image, stride, rows, cols);
+        h->in_stats.images_staged++;
+        h->in_stats.bytes_staged += (uint64_t)rows * cols;
+    }
+    h->in_stats.upload_launches++;
     LevelView l0{h->d_pyr.p + g0.plane_off, h->G.pyramid_bytes, g0.pitch, cols, rows};
     msorb_keypoint* pk = reinterpret_cast<msorb_keypoint*>(h->h_out_pin.p);
     uint8_t* pd = h->h_out_pin.p + (size_t)cap * sizeof(msorb_keypoint);
@@ -1044,13 +1196,18 @@ int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, 
         if ((rc = h->h_out_pin.ensure(blk_bytes))) return rc;
         pk = reinterpret_cast<msorb_keypoint*>(h->h_out_pin.p);
         pd = h->h_out_pin.p + o_desc;
-        if ((rc = frame_copy(h, h->d_pyr.p + g0.plane_off, h->h_img_pin.p, (size_t)g0.pitch * rows, hipMemcpyHostToDevice, h->stream))) return rc;
+        if (direct) in.upload(1, h->d_pyr.p + g0.plane_off, 0, g0.pitch, rows, cols, h->stream);
+        else if ((rc = frame_copy(h, h->d_pyr.p + g0.plane_off, h->h_img_pin.p, (size_t)g0.pitch * rows, hipMemcpyHostToDevice, h->stream))) return rc;
         h->defer_sync = true;
         rc = run_pipeline(h, l0, 1, lap0, lap1, reinterpret_cast<msorb_keypoint*>(h->d_out1.p), h->d_out1.p + o_desc, cap, &n, &mono);
         h->defer_sync = false;
         if (rc) return rc;
         if ((rc = frame_copy(h, h->h_out_pin.p, h->d_out1.p, blk_bytes, hipMemcpyDeviceToHost, h->stream))) return rc;
+        // host level 0 (msorb_pyramid_level hands out the handle's plane, never the caller's pointer): the copy the staged path makes
+        // in front of the upload, made here while the host would wait for the device anyway
+        if (direct && h->h_pyr_async) copy_rows(h->h_img_pin.p, g0.pitch, image, stride, rows, cols);
         HIPCHK(hipStreamSynchronize(h->stream));
+        in.done();
         if (h->h_pyr_async) HIPCHK(hipStreamSynchronize(h->pyr_stream));
         HIPCHK(hipGetLastError());
         n = h->h_sel_count.p[0];
@@ -1058,9 +1215,11 @@ int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, 
         if (n < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
         if (n > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
     } else {
-        HIPCHK(hipMemcpyAsync(h->d_pyr.p + g0.plane_off, h->h_img_pin.p, (size_t)g0.pitch * rows, hipMemcpyHostToDevice,
-                              h->stream));
-        if ((rc = run_pipeline(h, l0, 1, lap0, lap1, h->d_kps1.p, h->d_desc1.p, cap, &n, &mono))) return rc;
+        if (direct) in.upload(1, h->d_pyr.p + g0.plane_off, 0, g0.pitch, rows, cols, h->stream);
+        else HIPCHK(hipMemcpyAsync(h->d_pyr.p + g0.plane_off, h->h_img_pin.p, (size_t)g0.pitch * rows, hipMemcpyHostToDevice, h->stream));
+        if ((rc = run_pipeline(h, l0, 1, lap0, lap1, h->d_kps1.p, h->d_desc1.p, cap, &n, &mono))) return rc;   // (synchronises the stream)
+        if (direct && h->h_pyr_async) copy_rows(h->h_img_pin.p, g0.pitch, image, stride, rows, cols);
+        in.done();
         if (n > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
         if (n > 0) {
             HIPCHK(hipMemcpyAsync(pk, h->d_kps1.p, (size_t)n * sizeof(msorb_keypoint), hipMemcpyDeviceToHost, h->stream));
@@ -1114,19 +1273,40 @@ int msorb_extract_pair(msorb_extractor* h, const uint8_t* image_a, const uint8_t
             own_plane[i] = src[i] == lo ? 0 : 1;
         }
     }
+    // An image without a `staged` bit that lies in admitted host memory is read in place; then ONE launch uploads both images, the
+    // other one from wherever it lies in pinned memory (its msorb_stage_image plane, or the plane it is staged into here).
+    DirectInputs in;
+    bool any_direct = false;
+    for (int i = 0; i < 2; i++) any_direct = (!(staged & (1 << i)) && in.admit(h, i, src[i], rows, cols, stride[i])) || any_direct;
+    uint8_t* late_l0[2] = {nullptr, nullptr};   // plane of h_img_pin a direct image's host level 0 goes to
     for (int i = 0; i < 2; i++) {
         const uint8_t* pin;
+        const int other = own_plane[1 - i];
+        const int dst_plane = other == i ? 1 - i : i;   // the partner's staged image sits in this image's usual plane: take the other one
+        uint8_t* d = h->h_img_pin.p + (size_t)dst_plane * plane;
         if (staged & (1 << i)) {   // already in pinned memory at the library's pitch (msorb_stage_image)
             pin = src[i];
+        } else if (in.direct(i)) {
+            pin = nullptr;   // (no host level 0 yet: see below)
+            late_l0[i] = d;
+            h->in_stats.images_direct++;
         } else {
-            const int other = own_plane[1 - i];
-            const int dst_plane = other == i ? 1 - i : i;   // the partner's staged image sits in this image's usual plane: take the other one
-            uint8_t* d = h->h_img_pin.p + (size_t)dst_plane * plane;
-            for (int y = 0; y < rows; y++) memcpy(d + (size_t)y * g0.pitch, src[i] + (size_t)y * stride[i], cols);
+            copy_rows(d, g0.pitch, src[i], stride[i], rows, cols);
+            h->in_stats.images_staged++;
+            h->in_stats.bytes_staged += (uint64_t)rows * cols;
             pin = d;
         }
         h->pair_l0[i] = pin;
-        if ((rc = frame_copy(h, h->d_st_img.p + (size_t)i * plane, pin, plane, hipMemcpyHostToDevice, s))) return rc;
+        if (any_direct) {
+            if (!in.direct(i)) in.src[i] = Level0Src{pin, (size_t)g0.pitch};
+        } else {
+            h->in_stats.upload_launches++;
+            if ((rc = frame_copy(h, h->d_st_img.p + (size_t)i * plane, pin, plane, hipMemcpyHostToDevice, s))) return rc;
+        }
+    }
+    if (any_direct) {
+        h->in_stats.upload_launches++;
+        in.upload(2, h->d_st_img.p, plane, g0.pitch, rows, cols, s);
     }
     LevelView l0{h->d_st_img.p, plane, g0.pitch, cols, rows};
     uint8_t* const blk = h->d_st_block.p;
@@ -1138,7 +1318,10 @@ int msorb_extract_pair(msorb_extractor* h, const uint8_t* image_a, const uint8_t
     if (rc) { h->pair_pyramids = 0; return rc; }
     uint8_t* o = h->h_out_pin.p;
     if ((rc = frame_copy(h, o, blk, out_bytes, hipMemcpyDeviceToHost, s))) return rc;
+    for (int i = 0; i < 2; i++)   // host level 0 of a direct image, copied while the device works (as in msorb_extract)
+        if (late_l0[i] && h->h_pyr_async) { copy_rows(late_l0[i], g0.pitch, src[i], stride[i], rows, cols); h->pair_l0[i] = late_l0[i]; }
     HIPCHK(hipStreamSynchronize(s));
+    in.done();
     if (h->h_pyr_async) HIPCHK(hipStreamSynchronize(h->pyr_stream));
     HIPCHK(hipGetLastError());
     const int na = h->h_sel_count.p[0], nb = h->h_sel_count.p[1];
@@ -1162,6 +1345,8 @@ int msorb_stage_image(msorb_extractor* h, const uint8_t* image, int rows, int co
     const LevelGeom& g0 = h->G.lv[0];
     if ((rc = h->h_img_pin.ensure(2 * (size_t)g0.pitch * rows))) return rc;   // (two planes: msorb_extract_pair stages here too)
     for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + (size_t)y * g0.pitch, image + (size_t)y * stride, cols);
+    h->in_stats.images_staged++;
+    h->in_stats.bytes_staged += (uint64_t)rows * cols;
     *pinned = h->h_img_pin.p;
     if (pitch) *pitch = (size_t)g0.pitch;
     return MSORB_OK;
@@ -1188,6 +1373,12 @@ int msorb_pyramid_level_image(msorb_extractor* h, int image, int level, const ui
         h->h_pyr_async = true;
     }
     HIPCHK(hipStreamSynchronize(h->pyr_stream));
+    if (level == 0 && !h->pair_l0[image]) {   // an image that was read in place and has no host copy yet: level 0 comes back from the device
+        const LevelView& v = h->last_pyr.lv[0];
+        uint8_t* const d = h->h_pyr.p + (size_t)image * g.pyramid_bytes + g.lv[0].plane_off;
+        HIPCHK(hipMemcpy2D(d, g.lv[0].pitch, v.base + (size_t)image * v.img_stride, v.pitch, v.w, v.h, hipMemcpyDeviceToHost));
+        h->pair_l0[image] = d;
+    }
     *data = level == 0 ? h->pair_l0[image] : h->h_pyr.p + (size_t)image * g.pyramid_bytes + g.lv[level].plane_off;
     if (rows) *rows = g.lv[level].h;
     if (cols) *cols = g.lv[level].w;
@@ -1249,10 +1440,31 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
         return rc;
     // pageable rows -> pinned planes -> device, one eye at a time: the left plane rides PCIe while the right one is staged
     hipStream_t s = h->stream;
-    for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + (size_t)y * g0.pitch, left + (size_t)y * stride_left, cols);
-    if ((rc = frame_copy(h, h->d_st_img.p, h->h_img_pin.p, plane, hipMemcpyHostToDevice, s))) return rc;
-    for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + plane + (size_t)y * g0.pitch, right + (size_t)y * stride_right, cols);
-    if ((rc = frame_copy(h, h->d_st_img.p + plane, h->h_img_pin.p + plane, plane, hipMemcpyHostToDevice, s))) return rc;
+    // An eye in admitted host memory is read in place; with at least one such eye ONE launch uploads both (a pageable eye is staged
+    // first and rides that launch from its staging plane).
+    DirectInputs in;
+    const bool direct_l = in.admit(h, 0, left, rows, cols, stride_left), direct_r = in.admit(h, 1, right, rows, cols, stride_right);
+    if (direct_l || direct_r) {
+        const uint8_t* const eye[2] = {left, right};
+        const size_t eye_stride[2] = {stride_left, stride_right};
+        for (int i = 0; i < 2; i++) {
+            if (in.direct(i)) { h->in_stats.images_direct++; continue; }
+            copy_rows(h->h_img_pin.p + (size_t)i * plane, g0.pitch, eye[i], eye_stride[i], rows, cols);
+            in.src[i] = Level0Src{h->h_img_pin.p + (size_t)i * plane, (size_t)g0.pitch};
+            h->in_stats.images_staged++;
+            h->in_stats.bytes_staged += (uint64_t)rows * cols;
+        }
+        h->in_stats.upload_launches++;
+        in.upload(2, h->d_st_img.p, plane, g0.pitch, rows, cols, s);
+    } else {
+        for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + (size_t)y * g0.pitch, left + (size_t)y * stride_left, cols);
+        if ((rc = frame_copy(h, h->d_st_img.p, h->h_img_pin.p, plane, hipMemcpyHostToDevice, s))) return rc;
+        for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + plane + (size_t)y * g0.pitch, right + (size_t)y * stride_right, cols);
+        if ((rc = frame_copy(h, h->d_st_img.p + plane, h->h_img_pin.p + plane, plane, hipMemcpyHostToDevice, s))) return rc;
+        h->in_stats.images_staged += 2;
+        h->in_stats.bytes_staged += 2 * (uint64_t)rows * cols;
+        h->in_stats.upload_launches += 2;
+    }
     LevelView l0{h->d_st_img.p, plane, g0.pitch, cols, rows};
     uint8_t* const blk = h->d_st_block.p;
     msorb_keypoint* const d_kps = reinterpret_cast<msorb_keypoint*>(blk);
@@ -1320,6 +1532,7 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
         else if ((rc = frame_copy(h, o, blk, out_bytes, hipMemcpyDeviceToHost, s))) return rc;
     }
     HIPCHK(hipStreamSynchronize(s));
+    in.done();
     HIPCHK(hipGetLastError());
     const int nl = reinterpret_cast<const int*>(o + o_cnt)[0], nr = reinterpret_cast<const int*>(o + o_cnt)[1];
     if (nl < 0 || nr < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
@@ -1423,8 +1636,17 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
     int counts[1] = {0}, mono[1] = {0};
     // ---- right eye: upload + chain on device B (enqueued first: the join waits for it)
     HIPCHK(hipSetDevice(R->device));
-    for (int y = 0; y < rows; y++) memcpy(R->h_img_pin.p + (size_t)y * g0.pitch, right + (size_t)y * stride_right, cols);
-    HIPCHK(hipMemcpyAsync(R->d_pyr.p + R->G.lv[0].plane_off, R->h_img_pin.p, plane, hipMemcpyHostToDevice, R->stream));
+    DirectInputs in_r, in_l;   // each eye is read in place by its own handle's device (portable pinning: one block, every device)
+    if (in_r.admit(R, 0, right, rows, cols, stride_right)) {
+        R->in_stats.images_direct++;
+        in_r.upload(1, R->d_pyr.p + R->G.lv[0].plane_off, 0, g0.pitch, rows, cols, R->stream);
+    } else {
+        for (int y = 0; y < rows; y++) memcpy(R->h_img_pin.p + (size_t)y * g0.pitch, right + (size_t)y * stride_right, cols);
+        HIPCHK(hipMemcpyAsync(R->d_pyr.p + R->G.lv[0].plane_off, R->h_img_pin.p, plane, hipMemcpyHostToDevice, R->stream));
+        R->in_stats.images_staged++;
+        R->in_stats.bytes_staged += (uint64_t)rows * cols;
+    }
+    R->in_stats.upload_launches++;
     {
         LevelView l0{R->d_pyr.p + R->G.lv[0].plane_off, R->G.pyramid_bytes, g0.pitch, cols, rows};
         R->defer_sync = R->skip_count_copies = true;
@@ -1448,9 +1670,17 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
     HIPCHK(hipEventRecord(R->ev_split, R->stream));
     // ---- left eye: upload + chain on device A
     HIPCHK(hipSetDevice(L->device));
-    for (int y = 0; y < rows; y++) memcpy(L->h_img_pin.p + (size_t)y * g0.pitch, left + (size_t)y * stride_left, cols);
     hipStream_t s = L->stream;
-    HIPCHK(hipMemcpyAsync(L->d_pyr.p + g0.plane_off, L->h_img_pin.p, plane, hipMemcpyHostToDevice, s));
+    if (in_l.admit(L, 0, left, rows, cols, stride_left)) {
+        L->in_stats.images_direct++;
+        in_l.upload(1, L->d_pyr.p + g0.plane_off, 0, g0.pitch, rows, cols, s);
+    } else {
+        for (int y = 0; y < rows; y++) memcpy(L->h_img_pin.p + (size_t)y * g0.pitch, left + (size_t)y * stride_left, cols);
+        HIPCHK(hipMemcpyAsync(L->d_pyr.p + g0.plane_off, L->h_img_pin.p, plane, hipMemcpyHostToDevice, s));
+        L->in_stats.images_staged++;
+        L->in_stats.bytes_staged += (uint64_t)rows * cols;
+    }
+    L->in_stats.upload_launches++;
     // (n_oob is zeroed by the row-table kernel of launch_stereo_match_batch)
     {
         LevelView l0{L->d_pyr.p + g0.plane_off, g.pyramid_bytes, g0.pitch, cols, rows};
@@ -1495,7 +1725,9 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
     launch_stereo_match_batch(b, 1, cap, s);
     uint8_t* o = L->h_out_pin.p;
     HIPCHK(hipMemcpyAsync(o, blk, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(s));   // (the left stream waited for the right eye's event: both chains are done)
+    in_l.done();
+    in_r.done();
     HIPCHK(hipGetLastError());
     const int nl = reinterpret_cast<const int*>(o + o_cnt)[0], nr = reinterpret_cast<const int*>(o + o_cnt)[1];
     if (nl < 0 || nr < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }

@@ -67,6 +67,12 @@ void launch_blit(void* dst, const void* src, size_t bytes, hipStream_t s);
 // pinned host <-> device on a stream: the copy kernel, or hipMemcpyAsync for unaligned pointers / MSORB_FRAME_COPIES=sdma
 hipError_t small_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s);
 void launch_stage_level0(const LevelView& src, uint8_t* dst, int dst_pitch, size_t dst_image_stride, int n_images, hipStream_t s);
+// Level-0 upload of a per-frame call straight from the caller's memory (orb_kernels.hip upload_level0_kernel): up to two source
+// images in MAPPED host memory — device-visible addresses from the admission table (host_admission.h) or the handle's own pinned
+// staging plane — each with its own base and row stride at any byte alignment, written as planes of dst_pitch (a multiple of 64)
+// at dst + i * dst_image_stride (16-byte aligned).  One launch for all of them.
+struct Level0Src { const uint8_t* base; size_t stride; };
+void launch_upload_level0(const Level0Src* src, int n_images, uint8_t* dst, size_t dst_image_stride, int dst_pitch, int rows, int cols, hipStream_t s);
 // The [OpenCV-recall] semantics that a real OpenCV build could turn out to differ in, as one table (msorb_semantics of the C
 // ABI, oracle/cvprims.h Semantics): non-default entries route to the kernels that take them at run time.
 struct Semantics {

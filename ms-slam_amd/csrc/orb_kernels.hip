@@ -1450,6 +1450,51 @@ void launch_blit(void* dst, const void* src, size_t bytes, hipStream_t s) {
     hipLaunchKernelGGL(blit16_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<uint4*>(dst), reinterpret_cast<const uint4*>(src), n16,
                        (unsigned)(bytes & 15));
 }
+// Level 0 of a frame's one or two images read IN PLACE from mapped host memory (the caller's pinned image, host_admission.h) and
+// written at the library's row pitch: the staging copy on the host and the second upload launch of a stereo frame go away.
+// One wave owns 1 KB of one row of one image (blockIdx.y), one lane one aligned 16-byte word of the DESTINATION; a KITTI stereo
+// frame is ~1500 waves with one or two loads each, so every PCIe read of the launch is in flight at once.  The source row starts
+// at any byte: a lane reads the aligned 16-byte word that holds its first byte and, when its bytes run on into it, the next one, and
+// funnel-shifts the pair (a dword select and v_alignbyte).  Only words that hold at least one byte of the image are read: an aligned
+// 16-byte word never crosses a page and pinning is by whole pages, so a read rounded outward stays inside pinned memory.  What
+// is stored depends on the image's bytes alone: the bytes of a word past `cols` — the row's tail and the pitch padding — are
+// stored as zero, whatever lay beside the image.
+struct Level0Pair { Level0Src s[2]; };
+__global__ __launch_bounds__(256) void upload_level0_kernel(Level0Pair src, uint8_t* __restrict__ dst, size_t dst_image_stride, int dst_pitch,
+                                                            int rows, int cols, int segs) {
+    const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int y = wave / segs, x0 = (wave - y * segs) * 1024 + (threadIdx.x & 63) * 16;
+    if (y >= rows || x0 >= dst_pitch) return;
+    const uint8_t* const base = blockIdx.y ? src.s[1].base : src.s[0].base;
+    const size_t stride = blockIdx.y ? src.s[1].stride : src.s[0].stride;
+    uint4 out = make_uint4(0, 0, 0, 0);
+    if (x0 < cols) {
+        const uint8_t* const p = base + (size_t)y * stride + (size_t)x0;
+        const unsigned need = (unsigned)min(16, cols - x0);   // image bytes of this word
+        const unsigned sh = (unsigned)(reinterpret_cast<uintptr_t>(p) & 15), ws = sh >> 2, bs = sh & 3;
+        const uint4* const w = reinterpret_cast<const uint4*>(p - sh);
+        const uint4 lo = w[0];
+        uint4 hi = make_uint4(0, 0, 0, 0);
+        if (sh + need > 16) hi = w[1];
+        auto pick = [ws](uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3) { return ws == 0 ? a0 : ws == 1 ? a1 : ws == 2 ? a2 : a3; };
+        const uint32_t t0 = pick(lo.x, lo.y, lo.z, lo.w), t1 = pick(lo.y, lo.z, lo.w, hi.x), t2 = pick(lo.z, lo.w, hi.x, hi.y),
+                       t3 = pick(lo.w, hi.x, hi.y, hi.z), t4 = pick(hi.x, hi.y, hi.z, hi.w);
+        auto keep = [need](unsigned first) { return need >= first + 4 ? 0xffffffffu : need <= first ? 0u : (1u << (8 * (need - first))) - 1u; };
+        out.x = __builtin_amdgcn_alignbyte(t1, t0, bs) & keep(0);
+        out.y = __builtin_amdgcn_alignbyte(t2, t1, bs) & keep(4);
+        out.z = __builtin_amdgcn_alignbyte(t3, t2, bs) & keep(8);
+        out.w = __builtin_amdgcn_alignbyte(t4, t3, bs) & keep(12);
+    }
+    *reinterpret_cast<uint4*>(dst + (size_t)blockIdx.y * dst_image_stride + (size_t)y * dst_pitch + x0) = out;
+}
+void launch_upload_level0(const Level0Src* src, int n_images, uint8_t* dst, size_t dst_image_stride, int dst_pitch, int rows, int cols, hipStream_t s) {
+    Level0Pair p;
+    p.s[0] = src[0];
+    p.s[1] = src[n_images > 1 ? 1 : 0];
+    const int segs = (dst_pitch + 1023) / 1024;
+    hipLaunchKernelGGL(upload_level0_kernel, dim3((unsigned)((rows * segs + 3) / 4), (unsigned)n_images), dim3(256), 0, s, p, dst, dst_image_stride, dst_pitch,
+                       rows, cols, segs);
+}
 void launch_stage_level0(const LevelView& src, uint8_t* dst, int dst_pitch, size_t dst_image_stride, int n_images, hipStream_t s) {
     hipLaunchKernelGGL(stage_level0_kernel, dim3((src.w + 1023) / 1024, src.h, n_images), dim3(256), 0, s, src.base, (size_t)src.pitch,
                        src.img_stride, dst, dst_pitch, dst_image_stride, src.w);

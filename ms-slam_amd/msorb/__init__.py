@@ -23,7 +23,7 @@ STAGES = ("pyramid", "fast", "compact", "blur", "select", "describe")
 OK, E_INVALID, E_NO_DEVICE, E_HIP, E_CAPACITY, E_GEOMETRY, E_EMPTY = 0, -1, -2, -3, -4, -5, -6
 
 # every symbol include/msorb.h declares (tests check the library exports them all)
-ABI_VERSION = 6001   # MSORB_ABI_VERSION of the include/msorb.h this mirror was written against (tests hold the two together)
+ABI_VERSION = 6002   # MSORB_ABI_VERSION of the include/msorb.h this mirror was written against (tests hold the two together)
 
 EXPORTS = (
     "msorb_last_error", "msorb_device_count", "msorb_device_memory", "msorb_abi_version", "msorb_abi_compatible", "msorb_set_fatal_callback", "msorb_notify_fatal", "msorb_extractor_create", "msorb_extractor_destroy",
@@ -239,6 +239,14 @@ class ORBextractor:
                "msorb_extract_stereo_split")
         a, b = nl.value, nr.value
         return kl[:a].copy(), dl[:a].copy(), kr[:b].copy(), dr[:b].copy(), ur[:a].copy(), dp[:a].copy(), oob.value
+
+    def input_stats(self):
+        """msorb_extractor_input_stats: where this handle's level-0 images came from since it was created, as a dict of
+        images_direct / images_staged / bytes_staged / upload_launches."""
+        st = InputStats()
+        self.L.msorb_extractor_input_stats.argtypes = [C.c_void_p, C.POINTER(InputStats)]
+        _check(self.L.msorb_extractor_input_stats(self.h, C.byref(st)), "msorb_extractor_input_stats")
+        return {k: int(getattr(st, k)) for k, _ in InputStats._fields_}
 
     def pyramid_batch(self, images):
         """msorb_pyramid_batch: ComputePyramid only, for a torch.uint8 CUDA tensor [n, rows, cols] (asynchronous)."""
@@ -1623,3 +1631,68 @@ def frame_search_rounds(frame):
     frame.L.msorb_frame_search_rounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     r = frame.L.msorb_frame_search_rounds(frame.h, C.addressof(tr), C.addressof(ts))
     return r, tr.value, ts.value
+
+
+# ---- host-memory admission (include/msorb.h, since ABI 6002): images the per-frame entries read in place
+EXPORTS = EXPORTS + ("msorb_host_alloc", "msorb_host_free", "msorb_host_register", "msorb_host_unregister", "msorb_host_admitted",
+                     "msorb_extractor_input_stats")
+
+
+class InputStats(C.Structure):   # msorb_input_stats
+    _fields_ = [("images_direct", C.c_uint64), ("images_staged", C.c_uint64), ("bytes_staged", C.c_uint64), ("upload_launches", C.c_uint64)]
+
+
+def _hlib():
+    L = lib()
+    if not getattr(L, "_msorb_host_ready", False):
+        L.msorb_host_alloc.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
+        L.msorb_host_free.argtypes = [C.c_void_p]
+        L.msorb_host_register.argtypes = [C.c_void_p, C.c_size_t]
+        L.msorb_host_unregister.argtypes = [C.c_void_p]
+        L.msorb_host_admitted.argtypes = [C.c_void_p, C.c_size_t]
+        L._msorb_host_ready = True
+    return L
+
+
+def host_empty(shape, dtype=np.uint8):
+    """An uninitialised ndarray in admitted pinned host memory (msorb_host_alloc): an image in it — the whole array or any view of
+    it — is read in place by the per-frame entries.  A finalizer frees the block when the last array over it is collected."""
+    import weakref
+    L = _hlib()
+    dtype = np.dtype(dtype)
+    shape = (shape,) if np.isscalar(shape) else tuple(shape)
+    n = int(np.prod(shape, dtype=np.int64))
+    p = C.c_void_p()
+    _check(L.msorb_host_alloc(max(n * dtype.itemsize, 1), C.byref(p)), "msorb_host_alloc")
+    root = np.frombuffer((C.c_uint8 * max(n * dtype.itemsize, 1)).from_address(p.value), dtype, n)   # every view keeps `root` alive
+    weakref.finalize(root, L.msorb_host_free, p.value)
+    return root.reshape(shape)
+
+
+def _extent(a):
+    """(address, bytes) of the smallest range that holds every element of ndarray a."""
+    lo, hi = np.lib.array_utils.byte_bounds(a) if hasattr(np.lib, "array_utils") else np.byte_bounds(a)
+    return lo, hi - lo
+
+
+def host_admitted(array):
+    """msorb_host_admitted over the bytes of an ndarray: True when a per-frame entry would read it in place."""
+    p, n = _extent(array)
+    return bool(n) and bool(_hlib().msorb_host_admitted(p, n))
+
+
+class host_registered:
+    """Context manager: msorb_host_register over the bytes of an existing (pageable) ndarray, msorb_host_unregister on exit.
+    Inside the context the per-frame entries read the array in place."""
+
+    def __init__(self, array):
+        self.array = array
+        self.ptr, self.nbytes = _extent(array)
+
+    def __enter__(self):
+        _check(_hlib().msorb_host_register(self.ptr, self.nbytes), "msorb_host_register")
+        return self.array
+
+    def __exit__(self, *exc):
+        _check(_hlib().msorb_host_unregister(self.ptr), "msorb_host_unregister")
+        return False
