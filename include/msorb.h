@@ -660,6 +660,51 @@ typedef struct msorb_triangulation_kf_pair {
 int msorb_search_for_triangulation_kf(msorb_kf_store* s, msorb_triangulation_kf_pair* pairs, int n_pairs, int coarse,
                                       int check_orientation, float* elapsed_ms);
 
+/* KeyFrameDatabase on the device (src/KeyFrameDatabase.cc; the BowVectors are msorb_bow_transform's).  Appended to ABI 6002:
+ * MSORB_ABI_VERSION is unchanged, so a caller that needs these entries asks the loader for them (a library built before them
+ * reports 6002 as well).
+ * An entry is one KeyFrame's BowVector: word ids strictly ascending and < n_words (= the vocabulary's size, the length of the
+ * reference's mvInvertedFile, :35), values as doubles.  The database keeps them on one device as a forward file, plus per
+ * entry its add sequence number: one `add` appends the KeyFrame to all the lists of the reference's inverted file at once
+ * (:39-45), so the order of two KeyFrames inside any list is their add order, and an erase followed by an add moves a
+ * KeyFrame to the back.  Thread-safe: queries may run concurrently with each other; add / erase / clear wait for running
+ * queries.  There is no CPU fallback: without a device msorb_kf_database_create returns MSORB_E_NO_DEVICE. */
+typedef struct msorb_kf_database msorb_kf_database;
+int msorb_kf_database_create(int device, int n_words, msorb_kf_database** out);
+void msorb_kf_database_destroy(msorb_kf_database* db);
+/* KeyFrameDatabase::add (:39-45).  *entry_id identifies the entry in later calls; ids of erased entries are handed out again.
+ * Unsorted / repeated / out-of-range words: MSORB_E_INVALID, the database is unchanged.  n == 0 is an entry no query meets. */
+int msorb_kf_database_add(msorb_kf_database* db, const int* word, const double* value, int n, int* entry_id);
+/* KeyFrameDatabase::erase (:47-66): removes exactly what the add entered (the reference walks the KeyFrame's CURRENT
+ * BowVector, which in MS-SLAM is the one it was added with).  The rows and the id go to the next add (first fit). */
+int msorb_kf_database_erase(msorb_kf_database* db, int entry_id);
+/* KeyFrameDatabase::clear (:68-72).  Every id is invalid afterwards; the device arrays stay reserved. */
+int msorb_kf_database_clear(msorb_kf_database* db);
+/* Live entries, the bound of the ids handed out so far (ids are < id_bound), BowVector elements in use / reserved on the
+ * device (12 bytes each over two arrays).  Any output may be NULL. */
+int msorb_kf_database_info(const msorb_kf_database* db, int* n_entries, int* id_bound, size_t* rows_in_use, size_t* rows_reserved);
+/* The place-recognition query up to the scores: DetectRelocalizationCandidates :746-792 (rule 0) and MS-SLAM's
+ * DetectNBestCandidates :612-668 (rule 1), with the L1 score of Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68.
+ * word / value [n]: the query BowVector (v1 of the score).  listed [id_bound] (NULL = all): which entries the reference's
+ * walk would put on lKFsSharingWords (rule 0: mnRelocQuery != F->mnId, :753; rule 1: mnPlaceRecognitionQuery != pKF->mnId &&
+ * mbSparsified && !spConnectedKF.count(pKFi), :620-625) - members of the caller's KeyFrames, so the caller builds the mask.
+ * Reported are all live entries sharing at least one word with the query, *n_sharing of them:
+ *   [0, *n_listed)          the listed ones in the order of lKFsSharingWords (first encounter of a walk over the query's words
+ *                           ascending and each word's list front to back = ordered by smallest common word, then add order), each
+ *                           with common_words (mnRelocWords / mnPlaceRecognitionWords, the size of the word intersection) and
+ *                           score = the DOUBLE ScoringObject.cpp:65 returns, its additions made in ascending word order as the merge
+ *                           walk makes them (the reference narrows it to float si, :663 / :788).  Every listed entry is scored; the
+ *                           reference scores those with common_words > *min_common_words (:660, :785), which the caller applies;
+ *   [*n_listed, *n_sharing) the others in ascending id, with common_words and score 0 (the reference touches their word counters
+ *                           too, :622 / :631 / :759).
+ * *max_common_words: the largest common_words of the listed entries (:639-644, :767-772); *min_common_words: max * 0.8f for
+ * rule 0 (:774), max > 10 ? max * 0.8f : max * 0.6f for rule 1 (:646-650), int * float truncated as there.  Both 0 without a
+ * listed entry.  capacity = length of entry / common_words / score; *n_sharing > capacity: MSORB_E_CAPACITY with *n_sharing
+ * set and nothing else written (id_bound always suffices).  *elapsed_ms (may be NULL) = device time of the kernel. */
+int msorb_kf_database_query(msorb_kf_database* db, const int* word, const double* value, int n, const uint8_t* listed, int rule,
+                            int* entry, int* common_words, double* score, int capacity, int* n_sharing, int* n_listed,
+                            int* max_common_words, int* min_common_words, float* elapsed_ms);
+
 /* Frame::ComputeStereoMatches (Frame.cc:743-913, median rejection :899-912 included) for every stereo pair of the last
  * msorb_extract_batch() call of `h`, all on the device: pair p = images 2p (left) and 2p+1 (right) of that batch.
  * d_keypoints / d_descriptors / capacity are the arrays that call filled, d_counts[2*n_pairs] the keypoint counts as a

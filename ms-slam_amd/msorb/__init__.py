@@ -1696,3 +1696,89 @@ class host_registered:
     def __exit__(self, *exc):
         _check(_hlib().msorb_host_unregister(self.ptr), "msorb_host_unregister")
         return False
+
+
+# ---- KeyFrameDatabase on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_kf_database_create", "msorb_kf_database_destroy", "msorb_kf_database_add", "msorb_kf_database_erase",
+                     "msorb_kf_database_clear", "msorb_kf_database_info", "msorb_kf_database_query")
+
+
+class KeyFrameDatabase:
+    """msorb_kf_database: the BowVectors of the map's KeyFrames resident on the device, and the place-recognition query of
+    KeyFrameDatabase::DetectRelocalizationCandidates / DetectNBestCandidates up to the scores (KeyFrameDatabase.cc:39-98, :612-668,
+    :746-792)."""
+    RELOC, NBEST = 0, 1
+
+    def __init__(self, n_words, device=0):
+        self.L = L = lib()
+        self.h = None
+        vp, ci = C.c_void_p, C.c_int
+        L.msorb_kf_database_create.argtypes = [ci, ci, C.POINTER(vp)]
+        L.msorb_kf_database_destroy.argtypes = [vp]
+        L.msorb_kf_database_destroy.restype = None
+        L.msorb_kf_database_add.argtypes = [vp, vp, vp, ci, vp]
+        L.msorb_kf_database_erase.argtypes = [vp, ci]
+        L.msorb_kf_database_clear.argtypes = [vp]
+        L.msorb_kf_database_info.argtypes = [vp] * 5
+        L.msorb_kf_database_query.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+        h = vp()
+        _check(L.msorb_kf_database_create(device, n_words, C.byref(h)), "msorb_kf_database_create")
+        self.h = h
+        self.n_words = n_words
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.msorb_kf_database_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def add(self, word, value):
+        """BowVector as (ascending word ids, values) -> entry id"""
+        w, v = _c(word, np.int32), _c(value, np.float64)
+        if len(w) != len(v):
+            raise ValueError("word and value differ in length")
+        eid = C.c_int(-1)
+        _check(self.L.msorb_kf_database_add(self.h, _np_ptr(w), _np_ptr(v), len(w), C.addressof(eid)), "msorb_kf_database_add")
+        return eid.value
+
+    def erase(self, entry_id):
+        _check(self.L.msorb_kf_database_erase(self.h, entry_id), "msorb_kf_database_erase")
+
+    def clear(self):
+        _check(self.L.msorb_kf_database_clear(self.h), "msorb_kf_database_clear")
+
+    def info(self):
+        """dict(n_entries, id_bound, rows_in_use, rows_reserved)"""
+        n, b, u, r = C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+        _check(self.L.msorb_kf_database_info(self.h, C.addressof(n), C.addressof(b), C.addressof(u), C.addressof(r)), "msorb_kf_database_info")
+        return dict(n_entries=n.value, id_bound=b.value, rows_in_use=u.value, rows_reserved=r.value)
+
+    def query(self, word, value, listed=None, rule=0, capacity=None):
+        """-> dict(entry, common_words, score (float64) [n_sharing]: the listed entries in the reference's list order, then the
+        unlisted sharing ones in ascending id; n_sharing, n_listed, max_common_words, min_common_words, elapsed_ms).
+        listed: uint8 [id_bound] or None = all.  capacity None = id_bound."""
+        w, v = _c(word, np.int32), _c(value, np.float64)
+        if len(w) != len(v):
+            raise ValueError("word and value differ in length")
+        bound = self.info()["id_bound"]
+        ls = None
+        if listed is not None:
+            ls = _c(listed, np.uint8)
+            if len(ls) < bound:
+                raise ValueError("listed is shorter than id_bound")
+        cap = bound if capacity is None else int(capacity)
+        ent, cw, sc = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float64)
+        ns, nl, mx, mn = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        ms = C.c_float()
+        rc = self.L.msorb_kf_database_query(self.h, _np_ptr(w), _np_ptr(v), len(w), None if ls is None else _np_ptr(ls), rule,
+                                            _np_ptr(ent), _np_ptr(cw), _np_ptr(sc), cap, C.addressof(ns), C.addressof(nl),
+                                            C.addressof(mx), C.addressof(mn), C.addressof(ms))
+        if rc == E_CAPACITY:
+            e = MsorbError(rc, "msorb_kf_database_query")
+            e.n_sharing = ns.value
+            raise e
+        _check(rc, "msorb_kf_database_query")
+        k = ns.value
+        return dict(entry=ent[:k], common_words=cw[:k], score=sc[:k], n_sharing=k, n_listed=nl.value, max_common_words=mx.value,
+                    min_common_words=mn.value, elapsed_ms=ms.value)

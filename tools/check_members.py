@@ -247,6 +247,8 @@ def owner(classes, cls, name):
 # parsed declarations, only what the checks consult: the members the host layer touches, the public interface of the two
 # classes it replaces, EXPECTED_TYPES, and PROBES (members tests/test_check_members.py asks about: access, kind, arity).
 FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_members.json")
+# members a later host header touches go to a second file beside it (`--write-extra`), so that the first one stays as it was pinned
+FIXTURE_EXTRA = os.path.join(ROOT, "tests", "golden", "reference_members_kf_database.json")
 PROBES = [("KeyFrame", "NLeft"), ("KeyFrame", "GetNLeft"), ("Frame", "mvKeysUn"), ("KeyFrame", "mvKeysUn"), ("MapPoint", "mfMaxDistance"),
           ("ORBmatcher", "SearchByProjection"), ("ORBmatcher", "mfNNratio"), ("ORBextractor", "mvImagePyramid")]
 
@@ -266,6 +268,11 @@ def table(classes):
 def load_table(path=FIXTURE):
     """-> the classes of the stored table, in parse_reference()'s form"""
     classes = json.load(open(path))
+    if path == FIXTURE and os.path.exists(FIXTURE_EXTRA):
+        for c, v in json.load(open(FIXTURE_EXTRA)).items():
+            classes.setdefault(c, {"bases": v["bases"], "file": v["file"], "n_members": v["n_members"], "members": {}})
+            for name, e in v["members"].items():
+                classes[c]["members"].setdefault(name, e)
     for v in classes.values():
         for e in v["members"].values():
             for k in ("access", "arity", "types"):
@@ -370,12 +377,25 @@ def type_check(classes, accesses):
 
 def main(argv):
     """no argument: the reference headers if present, else the stored table; --stored: the stored table;
-    --write-table: parse the reference headers and (re)write the stored table"""
+    --write-table: parse the reference headers and (re)write the stored table; --write-extra: write only the members the stored
+    table lacks to a second file, which --stored reads as well"""
     if "--write-table" in argv:
         with open(FIXTURE, "w") as f:
             json.dump(table(parse_reference()), f, indent=1, sort_keys=True)
             f.write("\n")
         print("wrote", os.path.relpath(FIXTURE, ROOT))
+        return 0
+    if "--write-extra" in argv:   # what the host layer touches today and the stored table lacks
+        full, have = table(parse_reference()), json.load(open(FIXTURE))
+        extra = {}
+        for c, v in full.items():
+            new = {n: e for n, e in v["members"].items() if n not in have.get(c, {}).get("members", {})}
+            if new:
+                extra[c] = dict(v, members=new)
+        with open(FIXTURE_EXTRA, "w") as f:
+            json.dump(extra, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print("wrote", os.path.relpath(FIXTURE_EXTRA, ROOT), sum(len(v["members"]) for v in extra.values()), "members")
         return 0
     if "--stored" in argv or not os.path.isdir(os.path.join(REF, "include")):
         classes, source = load_table(), os.path.relpath(FIXTURE, ROOT)
