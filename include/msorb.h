@@ -277,6 +277,16 @@ int msorb_debug_patch_tables(msorb_extractor* h, int8_t* pattern /* 1024 */, int
  * order[i] = input position of the item that ends at position i; sorted_keys and sort_us (the sort alone, timed on the device's
  * constant clock) may be NULL.  Since ABI 6000. */
 int msorb_debug_std_sort(int device, const uint32_t* keys, int n, int frame_form, uint32_t* order, uint32_t* sorted_keys, float* sort_us);
+/* Host-only: the per-thread table of the FAST kernel (one 16-byte record per thread of every class of cells with equal records) as
+ * an extractor of these parameters builds it for a rows x cols image and workgroups of `threads` (128 or 256) threads.  cells receives
+ * MSORB_FAST_CELL_FIELDS int32 per cell, in cell order: level, x0, y0, rw, rh, G, ndw, g_magic, R128, R256, by_wave[0], by_wave[1], spw,
+ * rw128, yw128, rw256, yw256, first record of the cell's class, level width, level height.  records receives 4 uint32 per record:
+ * staging store offset, quick-test window offset, column mask, rows | work-list base << 16.  The counts are written even when a
+ * capacity is too small (MSORB_E_CAPACITY).  Needs no GPU. */
+#define MSORB_FAST_CELL_FIELDS 20
+int msorb_debug_fast_thread_table(int rows, int cols, int nfeatures, float scale_factor, int nlevels, int threads,
+                                  int32_t* cells, int cell_capacity, int* n_cells,
+                                  uint32_t* records, int record_capacity, int* n_records, int* n_classes);
 /* Host-only: DistributeOctTree (ORBextractor.cc:555-779) on explicit candidates; writes the indices of
  * the kept candidates in result order.  Needs no GPU. */
 int msorb_distribute_quadtree(const uint16_t* xs, const uint16_t* ys, const uint16_t* scores, int n, int min_x,

@@ -175,6 +175,7 @@ struct msorb_extractor {
     TowerPlan tower;           // the pyramid of a frame or two as one launch (orb_device.h); ntx == 0: not available for this geometry
     std::vector<size_t> tap_x_off, tap_y_off;
     DevBuf<CellDesc> d_cells;
+    DevBuf<FastThreadRec> d_ttab;   // the FAST kernel's per-thread constants, one run of records per cell class (orb_host.h)
     DevBuf<int> d_level_cell_begin, d_cell_count, d_cell_off, d_level_count, d_img_total, d_img_base, d_sel_count;
     DevBuf<Cand16> d_slots, d_compact;
     DevBuf<SelRec> d_sel;
@@ -344,6 +345,8 @@ int ensure_geometry(msorb_extractor* h, int rows, int cols) {
     h->G = g;
     h->small_cells = true;
     for (const CellDesc& c : g.cells) h->small_cells = h->small_cells && c.rw <= 46 && c.rh <= 57;
+    std::vector<FastThreadRec> ttab;   // for the workgroup shape this geometry runs with; sets the cells' tt_off
+    build_fast_thread_table(h->G.cells, h->small_cells ? kFastSmall.threads : kFastLarge.threads, ttab);
     // resize taps for levels 1..n-1
     std::vector<ResizeTap> all;
     std::vector<std::vector<ResizeTap>> taps_x(g.nlevels), taps_y(g.nlevels);
@@ -370,7 +373,9 @@ int ensure_geometry(msorb_extractor* h, int rows, int cols) {
     if ((rc = h->d_taps.ensure(std::max<size_t>(all.size(), 1)))) return rc;
     if (!all.empty()) HIPCHK(hipMemcpy(h->d_taps.p, all.data(), all.size() * sizeof(ResizeTap), hipMemcpyHostToDevice));
     if ((rc = h->d_cells.ensure(g.cells.size()))) return rc;
-    HIPCHK(hipMemcpy(h->d_cells.p, g.cells.data(), g.cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_cells.p, h->G.cells.data(), h->G.cells.size() * sizeof(CellDesc), hipMemcpyHostToDevice));
+    if ((rc = h->d_ttab.ensure(ttab.size()))) return rc;
+    HIPCHK(hipMemcpy(h->d_ttab.p, ttab.data(), ttab.size() * sizeof(FastThreadRec), hipMemcpyHostToDevice));
     h->level_cell_begin.assign(g.nlevels + 1, 0);
     for (int l = 0; l < g.nlevels; l++) h->level_cell_begin[l] = g.lv[l].cell_begin;
     h->level_cell_begin[g.nlevels] = (int)g.cells.size();
@@ -648,10 +653,10 @@ int run_pipeline_groups(msorb_extractor* h, const LevelView& level0, int n_image
             mark(8, sb);
             if (side_blur) (void)hipEventRecord(G.ev_blur, sb);
         };
-        if (!(fuse_fb && launch_frame_fast_blur(pyr, blur, h->d_cells.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p + cslot,
+        if (!(fuse_fb && launch_frame_fast_blur(pyr, blur, h->d_cells.p, h->d_ttab.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p + cslot,
                                                 h->d_cell_count.p + (size_t)first * ncells, n, h->small_cells, s, h->sem))) {
             if (!h->overlap_blur) blur_now();   // one stream: pyramid, blur, FAST (the stage events expect this order)
-            launch_fast_cells(pyr, h->d_cells.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p + cslot,
+            launch_fast_cells(pyr, h->d_cells.p, h->d_ttab.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p + cslot,
                               h->d_cell_count.p + (size_t)first * ncells, n, h->small_cells, s);
             mark(2, s);
             if (h->overlap_blur && !fuse_qt) blur_now();
@@ -729,7 +734,7 @@ int run_pipeline(msorb_extractor* h, const LevelView& level0, int n_images, int 
         if (prof) (void)hipEventRecord(h->pe[8], h->copy_stream);
         HIPCHK(hipEventRecord(h->ev_blur, h->copy_stream));
     }
-    launch_fast_cells(pyr, h->d_cells.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p,
+    launch_fast_cells(pyr, h->d_cells.p, h->d_ttab.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p,
                       h->d_cell_count.p, n_images, h->small_cells, s);
     mark(2);
     launch_cand_compact(h->d_cells.p, ncells, h->d_level_cell_begin.p, nl, g.slots_per_image, h->d_slots.p,
@@ -1001,7 +1006,7 @@ void msorb_extractor_destroy(msorb_extractor* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->pool.reset();
-    h->d_pyr.release(); h->d_blur.release(); h->d_desc1.release(); h->d_taps.release(); h->d_cells.release();
+    h->d_pyr.release(); h->d_blur.release(); h->d_desc1.release(); h->d_taps.release(); h->d_cells.release(); h->d_ttab.release();
     h->d_level_cell_begin.release(); h->d_cell_count.release(); h->d_cell_off.release(); h->d_level_count.release();
     h->d_img_total.release(); h->d_img_base.release(); h->d_sel_count.release(); h->d_slots.release();
     h->d_compact.release(); h->d_sel.release(); h->d_kps1.release();
@@ -1870,6 +1875,34 @@ int msorb_distribute_quadtree(const uint16_t* xs, const uint16_t* ys, const uint
     *n_kept = (int)kept.size();
     if ((int)kept.size() > capacity) return MSORB_E_CAPACITY;
     for (size_t i = 0; i < kept.size(); i++) kept_idx[i] = kept[i];
+    return MSORB_OK;
+}
+
+int msorb_debug_fast_thread_table(int rows, int cols, int nfeatures, float scale_factor, int nlevels, int threads,
+                                  int32_t* cells, int cell_capacity, int* n_cells,
+                                  uint32_t* records, int record_capacity, int* n_records, int* n_classes) {
+    if (!n_cells || !n_records || !n_classes || rows <= 0 || cols <= 0 || nfeatures <= 0 || nlevels < 1 || nlevels > kMaxLevels ||
+        !(scale_factor > 1.f) || (threads != kFastSmall.threads && threads != kFastLarge.threads))
+        return MSORB_E_INVALID;
+    OrbParams P;
+    P.init(nfeatures, scale_factor, nlevels, 20, 7);   // (the thresholds do not enter the geometry)
+    FrameGeom g;
+    if (!g.build(P, rows, cols)) return MSORB_E_GEOMETRY;
+    std::vector<FastThreadRec> table;
+    *n_classes = build_fast_thread_table(g.cells, threads, table);
+    *n_cells = (int)g.cells.size();
+    *n_records = (int)table.size();
+    if (*n_cells > cell_capacity || *n_records > record_capacity) return MSORB_E_CAPACITY;
+    if (!cells || !records) return MSORB_E_INVALID;
+    for (size_t i = 0; i < g.cells.size(); i++) {
+        const CellDesc& c = g.cells[i];
+        const int32_t f[MSORB_FAST_CELL_FIELDS] = {c.level, c.x0, c.y0, c.rw, c.rh, c.G, c.ndw, (int32_t)c.g_magic, c.R128, c.R256, c.by_wave[0], c.by_wave[1],
+                                                   c.spw, (int32_t)c.rw128, (int32_t)c.yw128, (int32_t)c.rw256, (int32_t)c.yw256, (int32_t)c.tt_off,
+                                                   g.lv[c.level].w, g.lv[c.level].h};
+        memcpy(cells + i * MSORB_FAST_CELL_FIELDS, f, sizeof(f));
+    }
+    static_assert(sizeof(FastThreadRec) == 16, "four dwords per record");
+    memcpy(records, table.data(), table.size() * sizeof(FastThreadRec));
     return MSORB_OK;
 }
 

@@ -114,7 +114,7 @@ void launch_pyramid(const PyramidView& pyr, const ResizeTap* taps, const size_t*
                     hipStream_t s, const Semantics& sem = Semantics());
 void launch_pyr_resize(const LevelView& src, const LevelView& dst, uint8_t* dst_base, const ResizeTap* tx,
                        const ResizeTap* ty, int n_images, hipStream_t s, int single_stage = 0);
-void launch_fast_cells(const PyramidView& pyr, const CellDesc* cells, int n_cells, int ini_th, int min_th,
+void launch_fast_cells(const PyramidView& pyr, const CellDesc* cells, const FastThreadRec* ttab, int n_cells, int ini_th, int min_th,
                        int slots_per_image, Cand16* slots, int* cell_count, int n_images, bool small_cells, hipStream_t s);
 void launch_cand_compact(const CellDesc* cells, int n_cells, const int* level_cell_begin, int nlevels,
                          int slots_per_image, const Cand16* slots, const int* cell_count, int* cell_off,
@@ -122,7 +122,7 @@ void launch_cand_compact(const CellDesc* cells, int n_cells, const int* level_ce
                          hipStream_t s, bool packed = true, bool frame_form = false);   // frame_form: <= 4 images, !packed: scan + gather as one launch
 int launch_gauss7(const PyramidView& src, const PyramidView& dst, int n_images, hipStream_t s, const Semantics& sem = Semantics());
 // FAST + blur of a frame (1-4 images) as one launch; false = not applicable (unaligned rows, non-default taps), nothing launched
-bool launch_frame_fast_blur(const PyramidView& pyr, const PyramidView& blur, const CellDesc* cells, int n_cells, int ini_th, int min_th,
+bool launch_frame_fast_blur(const PyramidView& pyr, const PyramidView& blur, const CellDesc* cells, const FastThreadRec* ttab, int n_cells, int ini_th, int min_th,
                             int slots_per_image, Cand16* slots, int* cell_count, int n_images, bool small_cells, hipStream_t s,
                             const Semantics& sem = Semantics());
 void launch_describe(const PyramidView& pyr, const PyramidView& blur, const SelRec* sel, const int* sel_count,

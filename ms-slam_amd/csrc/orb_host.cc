@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <map>
 
 namespace msorb {
 
@@ -155,6 +156,7 @@ bool FrameGeom::build(const OrbParams& p, int rows_, int cols_) {
                     c.by_wave[0] = split(2, c.R128, 5, c.rw128, c.yw128);   // GeoSmall::kMaxR
                     c.by_wave[1] = split(4, c.R256, 6, c.rw256, c.yw256);   // GeoLarge::kMaxR
                 }
+                c.tt_off = 0;
                 cells.push_back(c);
             }
         }
@@ -164,6 +166,57 @@ bool FrameGeom::build(const OrbParams& p, int rows_, int cols_) {
     blur_bytes = boff;
     slots_per_image = slot;
     return true;
+}
+
+// The FAST kernel's per-thread constants (FastThreadRec), by the formulas the kernel itself used up to round 6 and its
+// byte-granular variant still uses (orb_kernels.hip fast_cells_body); tests/test_fast_thread_table.py restates them independently.
+int build_fast_thread_table(std::vector<CellDesc>& cells, int threads, std::vector<FastThreadRec>& table) {
+    const FastShape shape = threads == kFastSmall.threads ? kFastSmall : kFastLarge;
+    const int T = shape.threads, P = shape.tile_pitch;
+    const bool small = T == kFastSmall.threads;
+    table.clear();
+    std::map<std::vector<uint32_t>, uint32_t> classes;   // records of a class -> its first record
+    std::vector<uint32_t> key((size_t)T * 4);
+    for (CellDesc& cd : cells) {
+        const int ga = cd.x0 & ~3, x_lo = cd.x0 + 3, x_hi = cd.x0 + cd.rw - 3, gx0 = x_lo & ~3;
+        const int G = cd.G, c_lo = gx0 - ga, dh = cd.rh - 6;
+        const uint32_t magic = cd.g_magic;
+        const bool by_wave = (small ? cd.by_wave[0] : cd.by_wave[1]) != 0;
+        for (int tid = 0; tid < T; tid++) {
+            int g_own, R, y_b;
+            if (!by_wave) {
+                const int strip = (int)(((uint32_t)tid * magic) >> 20);
+                g_own = tid - strip * G;
+                R = small ? cd.R128 : cd.R256;
+                y_b = strip * R;
+            } else {
+                const int lane = tid & 63, sw = (tid >> 6) * 8;
+                const int sl = (int)(((uint32_t)lane * magic) >> 20);
+                g_own = lane - sl * G;
+                R = (int)(((small ? cd.rw128 : cd.rw256) >> sw) & 255u);
+                const int y_w = (int)(((small ? cd.yw128 : cd.yw256) >> sw) & 255u);
+                y_b = sl < (int)cd.spw ? y_w + sl * R : dh;
+            }
+            const int nrows = std::min(std::max(dh - y_b, 0), R);
+            const int c_own = c_lo + 4 * g_own, xg = ga + c_own;
+            const int vlo = std::min(std::max(x_lo - xg, 0), 4), vhi = std::min(std::max(x_hi - xg, 0), 4);
+            uint32_t hm = 0;
+            for (int j = vlo; j < vhi; j++) hm |= 0x80u << (8 * j);
+            const int c = tid & (shape.col_lanes - 1), r0 = tid / shape.col_lanes;
+            uint32_t* rec = &key[(size_t)tid * 4];
+            rec[0] = (uint32_t)(r0 * P + 4 * c);
+            rec[1] = (uint32_t)(y_b * P + c_own);
+            rec[2] = hm;
+            rec[3] = (uint32_t)nrows | ((uint32_t)(uint16_t)(((y_b + 3) << 7) | c_own) << 16);
+        }
+        auto it = classes.find(key);
+        if (it == classes.end()) {
+            it = classes.emplace(key, (uint32_t)table.size()).first;
+            for (int tid = 0; tid < T; tid++) table.push_back(FastThreadRec{key[4 * tid], key[4 * tid + 1], key[4 * tid + 2], key[4 * tid + 3]});
+        }
+        cd.tt_off = it->second;
+    }
+    return (int)classes.size();
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -53,7 +53,25 @@ struct CellDesc {  // one FAST cell of ComputeKeyPointsOctTree (ORBextractor.cc:
     // register window; otherwise the kernel keeps the uniform split above.
     uint8_t by_wave[2], spw, pad_;
     uint32_t rw128, yw128, rw256, yw256;
+    uint32_t tt_off;  // first record of the cell's class in the per-thread table (build_fast_thread_table), in records
 };
+
+// What a thread of the FAST kernel needs to know about its place in the cell, tabulated once per geometry so that no wave spends
+// instructions on it: the records of thread 0 .. threads - 1 of a cell start at CellDesc::tt_off.  Every field is a function of
+// (x0 & 3, rw, rh, thread id) and the workgroup shape alone — not of the image, the level's pitch or the cell's position — so cells
+// with equal records share them (a "class"), and one coalesced 16-byte load per thread replaces the arithmetic.
+struct FastThreadRec {
+    uint32_t lds_store;   // staging: byte offset inside the LDS tile of the dword the thread stores per pass (row tid / col_lanes, dword tid % col_lanes)
+    uint32_t colp;        // quick test: byte offset inside the tile of (first detection row - 3, first pixel of the thread's column group)
+    uint32_t hm;          // 0x80 in every byte whose pixel of the group lies in the detection columns [x0 + 3, x0 + rw - 3)
+    uint32_t rows_tbase;  // low half: detection rows the thread owns (0 beyond the last strip); high half: its work-list base
+                          // (tile row of its first detection row) << 7 | tile column of its group, as the kernel's LDS table holds it
+};
+// The two workgroup shapes of the FAST kernel (orb_kernels.hip GeoSmall / GeoLarge hold the same numbers, checked there)
+struct FastShape { int threads, tile_pitch, col_lanes; };
+constexpr FastShape kFastSmall = {128, 52, 16}, kFastLarge = {256, 84, 32};
+// Fills `table` and every cell's tt_off for workgroups of `threads` (128 or 256) threads; returns the number of classes.
+int build_fast_thread_table(std::vector<CellDesc>& cells, int threads, std::vector<FastThreadRec>& table);
 
 struct LevelGeom {
     int w = 0, h = 0;    // level size (ComputePyramid, ORBextractor.cc:1174-1175)

@@ -371,7 +371,7 @@ __device__ __forceinline__ int block_excl_scan(int cnt, int lane, int wave, int*
 // The kernel's body, on a workgroup's LINEAR index among `total` = cells_x * n_images workgroups (so that the frame kernel below can
 // run it on a sub-range of its grid).
 template <bool ALIGNED, class GEO>
-__device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const CellDesc* __restrict__ cells,
+__device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const CellDesc* __restrict__ cells, const FastThreadRec* __restrict__ ttab,
                                                          int ini_th, int min_th, int slots_per_image,
                                                          Cand16* __restrict__ slots, int* __restrict__ cell_count,
                                                          int n_cells, uint32_t gx_magic, const unsigned lin, const unsigned grid_x, const unsigned total) {
@@ -379,6 +379,8 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
     constexpr int kScoreBytes = (GEO::kScoreRows * SP + 15) & ~15;
     constexpr int kBitWords = GEO::kWordsPerRow * GEO::kMaxDet;
     static_assert(kBitWords <= T, "one bitmap word per thread");
+    constexpr FastShape kShape = T == kFastSmall.threads ? kFastSmall : kFastLarge;   // what the host built the per-thread table for
+    static_assert(kShape.threads == T && kShape.tile_pitch == P && kShape.col_lanes == (P <= 64 ? 16 : 32), "orb_host.h FastShape");
     __shared__ __attribute__((aligned(16))) uint8_t tile_mem[kTileFront + GEO::kTileRows * P + 8];
     __shared__ __attribute__((aligned(16))) uint8_t score[kScoreBytes];
     __shared__ uint16_t work[GEO::kWorkCap];
@@ -413,6 +415,11 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
     // back to back (one memory round trip per cell).  Rows past the ROI are clamped to its last row (an unconditional load of
     // a row that exists; what lands in the tile rows below the ROI is never used), so no pass needs a predicate.
     const uint8_t* src = lv.base + (size_t)img * lv.img_stride + (size_t)cd.y0 * lv.pitch;  // wave-uniform: SGPR base
+    // The thread's constants of this cell shape, tabulated by the host (orb_host.h FastThreadRec): one 16-byte load, issued with
+    // the tile loads (both wait for the cell record only), instead of some forty instructions per wave that give the same values
+    // for every image and every cell of the class.  The byte-granular variant keeps the formulas.
+    FastThreadRec tr{};
+    if (ALIGNED) tr = ttab[cd.tt_off + (uint32_t)tid];
     if (ALIGNED) {
         constexpr int kColLanes = P <= 64 ? 16 : 32;  // dwords per tile row: <= 13 (GeoSmall) / <= 21 (GeoLarge)
         constexpr int kRowsPerPass = T / kColLanes;
@@ -420,13 +427,16 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
         const int c = tid & (kColLanes - 1), r0 = tid / kColLanes;
         if (c < cd.ndw) {  // dwords per tile row = (x0 + rw - ga + 3) >> 2
             const uint32_t col = (uint32_t)(ga + 4 * c);
+            // the row clamp on byte offsets: min(r0 + k, rh - 1) * pitch + col = min((r0 + k) * pitch + col, (rh - 1) * pitch + col),
+            // and the pass strides k * pitch are scalars: an add and a min per pass.  (Needs (r0 + k) * pitch + col < 2^32, as the
+            // 32-bit offset of the row clamp did: fewer than 80 rows of a pitch the 24-bit multiply already bounds by 2^24.)
+            const uint32_t pitch = (uint32_t)lv.pitch;
+            const uint32_t off0 = __umul24((uint32_t)r0, pitch) + col, off_last = (uint32_t)(rh - 1) * pitch + col;
             uint32_t v[kPasses];
 #pragma unroll
-            for (int p = 0; p < kPasses; p++) {
-                const uint32_t row = (uint32_t)min(r0 + p * kRowsPerPass, rh - 1);
-                v[p] = *reinterpret_cast<const uint32_t*>(src + (__umul24(row, (uint32_t)lv.pitch) + col));
-            }
-            uint8_t* l0 = &tile[r0 * P + 4 * c];
+            for (int p = 0; p < kPasses; p++)
+                v[p] = *reinterpret_cast<const uint32_t*>(src + min(off0 + (uint32_t)(p * kRowsPerPass) * pitch, off_last));
+            uint8_t* l0 = &tile[tr.lds_store];
 #pragma unroll
             for (int p = 0; p < kPasses; p++)
                 if ((p + 1) * kRowsPerPass <= GEO::kTileRows || r0 + p * kRowsPerPass < GEO::kTileRows)
@@ -456,30 +466,44 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
     // Two ways to deal the detection rows: uniformly (strip = tid / G over the whole workgroup, R rows each), or per wave
     // (64 / G strips inside every wave; wave w takes rw[w] rows per thread from row yw[w] on) when that needs fewer iterations
     // of the row loop — 39 rows over 2 x 6 strips are 4 + 3 instead of 4 + 4 (host-decided per cell, block-uniform).
-    int g_own, R, y_b;
-    if ((T == 128 ? cd.by_wave[0] : cd.by_wave[1]) == 0) {
-        const int strip = (int)(__umul24((uint32_t)tid, magic) >> 20);
-        g_own = tid - strip * G;
-        R = T == 128 ? cd.R128 : cd.R256;               // wave-uniform
-        y_b = strip * R;                                // first detection row of the thread
+    // R, the iterations of the row loop, is wave-uniform and stays on the scalar unit; what differs from thread to thread — rows
+    // owned, column mask, window offset, work-list base — comes from the table (ALIGNED) or from the formulas the host tabulates.
+    const bool by_wave = (T == 128 ? cd.by_wave[0] : cd.by_wave[1]) != 0;
+    const int sw = __builtin_amdgcn_readfirstlane(wave) * 8;
+    const int R = !by_wave ? (T == 128 ? cd.R128 : cd.R256) : (int)(((T == 128 ? cd.rw128 : cd.rw256) >> sw) & 255u);   // wave-uniform (scalar)
+    int nrows;          // detection rows of the thread: 0 for the threads beyond the last strip
+    uint32_t Hm;        // 0x80 in every byte whose pixel lies inside [x_lo, x_hi)
+    uint32_t colp_off;  // tile offset of (first detection row - 3, pixel 0 of the group)
+    uint32_t baseA;     // (tile row of the first detection row) << 7 | tile column of the group
+    if (ALIGNED) {
+        nrows = (int)(tr.rows_tbase & 0xffffu);
+        Hm = tr.hm;
+        colp_off = tr.colp;
+        // (16 bits of it, as the LDS table holds it: the full value differs only where y_b reaches 509, in threads past the last
+        // strip of a cell — they own no rows, raise no flag and never use baseA)
+        baseA = tr.rows_tbase >> 16;
     } else {
-        const int sw = __builtin_amdgcn_readfirstlane(wave) * 8;
-        const int sl = (int)(__umul24((uint32_t)lane, magic) >> 20);
-        g_own = lane - sl * G;
-        R = (int)(((T == 128 ? cd.rw128 : cd.rw256) >> sw) & 255u);    // wave-uniform (scalar)
-        const int y_w = (int)(((T == 128 ? cd.yw128 : cd.yw256) >> sw) & 255u);
-        y_b = sl < (int)cd.spw ? y_w + sl * R : dh;     // lanes past the wave's last strip: no rows
-    }
-    const int nrows = min(max(dh - y_b, 0), R);         // 0 for the threads beyond the last strip
-    const int c_own = c_lo + 4 * g_own;                 // tile column of pixel 0 of the group
-    uint32_t Hm;                                        // 0x80 in every byte whose pixel lies inside [x_lo, x_hi)
-    {
+        int g_own, y_b;
+        if (!by_wave) {
+            const int strip = (int)(__umul24((uint32_t)tid, magic) >> 20);
+            g_own = tid - strip * G;
+            y_b = strip * R;                                // first detection row of the thread
+        } else {
+            const int sl = (int)(__umul24((uint32_t)lane, magic) >> 20);
+            g_own = lane - sl * G;
+            const int y_w = (int)(((T == 128 ? cd.yw128 : cd.yw256) >> sw) & 255u);
+            y_b = sl < (int)cd.spw ? y_w + sl * R : dh;     // lanes past the wave's last strip: no rows
+        }
+        nrows = min(max(dh - y_b, 0), R);
+        const int c_own = c_lo + 4 * g_own;                 // tile column of pixel 0 of the group
         const int xg = ga + c_own;
         const int vlo = min(max(x_lo - xg, 0), 4), vhi = min(max(x_hi - xg, 0), 4);
         Hm = (0x80808080u << (8 * vlo)) & (uint32_t)(0x0080808080ull >> (8 * (4 - vhi)));  // shifts by 32 must give 0
         if (vlo >= 4) Hm = 0;
+        colp_off = __umul24((uint32_t)y_b, P) + (uint32_t)c_own;
+        baseA = (uint32_t)(((y_b + 3) << 7) | c_own);
     }
-    tbase[tid] = (uint16_t)(((y_b + 3) << 7) | c_own);
+    tbase[tid] = (uint16_t)baseA;
     // Quick test at threshold th for the thread's rows: wA / wB receive 2 flags (dark, bright) per pixel, bit 8 j + 2 k (+ 1)
     // for pixel j of row k (rows 0..3 in wA, 4.. in wB).  All four pixels of a group are tested at once on raw bytes:
     //   A = sat0(v - t), B = sat255(v + t) per byte (v_pk_sub_u16 clamp on the even / odd bytes),
@@ -489,7 +513,7 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
     // pair: a corner needs the predicate for (up OR down) AND (left OR right).
     auto quick_test = [&](int th, uint32_t& wA, uint32_t& wB) {
         wA = 0; wB = 0;
-        const uint8_t* colp = &tile[(int)__umul24((uint32_t)y_b, P) + c_own];
+        const uint8_t* colp = &tile[colp_off];
         uint32_t cw[GEO::kMaxR + 6], lw[GEO::kMaxR], rw_[GEO::kMaxR];
 #pragma unroll
         for (int r = 0; r < GEO::kMaxR + 6; r++)
@@ -548,7 +572,7 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
         // (S = A' - 1 with A' = max over the 16 arcs of the min over 9 contiguous signed contrasts of the entry's polarity)
         // (the append loop runs as long as the busiest lane of the wave has flags left, so it only packs thread id and flag
         // bit; the list's consumers — all lanes busy — turn that into tile coordinates through two small tables)
-        const uint32_t baseA = (uint32_t)(((y_b + 3) << 7) | c_own), baseB = baseA + (4u << 7);
+        const uint32_t baseB = baseA + (4u << 7);
         int w_begin = 0, n_corner = 0;   // this wave's stretch of the list, its corners (wave-uniform)
         if (n_work <= GEO::kWorkCap) {
             uint16_t* wp = &work[my_base];
@@ -649,8 +673,14 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
             // saturated cell: strict 3x3 NMS by scanning the score plane; one task = one group of one detection row in scan
             // order, balanced consecutive task ranges per thread (thread t owns tasks [t*n/T, (t+1)*n/T)), 4 flag bits per task
             const int n_task = dh * G;
-            const int t_begin = (int)(__umul24((uint32_t)tid, (uint32_t)n_task) / T),
-                      t_end = (int)(__umul24((uint32_t)tid + 1u, (uint32_t)n_task) / T);
+            // (the empty statement ties the task range to this branch: derived from tid alone it is loop-invariant, and the compiler
+            // moves its dozen instructions in front of the pass loop, where every cell pays for what a saturated one uses.  It leans
+            // on what this compiler does; the check is the static VALU count in front of the kernel's first s_barrier in
+            // `hipcc -S`: 100 for fast_cells_kernel<true, GeoSmall> with it, 114 without)
+            uint32_t tid_here = (uint32_t)tid;
+            asm volatile("" : "+v"(tid_here));
+            const int t_begin = (int)(__umul24(tid_here, (uint32_t)n_task) / T),
+                      t_end = (int)(__umul24(tid_here + 1u, (uint32_t)n_task) / T);
             uint64_t keep = 0;
             {
                 int y = (int)(__umul24((uint32_t)t_begin, magic) >> 20);
@@ -709,10 +739,11 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
 
 template <bool ALIGNED, class GEO>
 __global__ __launch_bounds__(GEO::kThreads, GEO::kMinWaves) void fast_cells_kernel(PyramidView pyr, const CellDesc* __restrict__ cells,
+                                                         const FastThreadRec* __restrict__ ttab,
                                                          int ini_th, int min_th, int slots_per_image,
                                                          Cand16* __restrict__ slots, int* __restrict__ cell_count,
                                                          int n_cells, uint32_t gx_magic) {
-    fast_cells_body<ALIGNED, GEO>(pyr, cells, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic,
+    fast_cells_body<ALIGNED, GEO>(pyr, cells, ttab, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic,
                                   blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, gridDim.x * gridDim.y);
 }
 
@@ -1001,12 +1032,12 @@ __global__ __launch_bounds__(256) void gauss7_stream_kernel(PyramidView src, Pyr
 // fast_cells_body on their cell, the rest gauss7_stream_body: GEO::kThreads / 64 waves of a blur block each (the blur's waves are
 // independent).  The blur's registers (88) set the allocation: no minimum-waves bound here — a frame does not fill the chip.
 template <bool ALIGNED, class GEO>
-__global__ __launch_bounds__(GEO::kThreads) void frame_fast_blur_kernel(PyramidView pyr, const CellDesc* __restrict__ cells, int ini_th, int min_th,
+__global__ __launch_bounds__(GEO::kThreads) void frame_fast_blur_kernel(PyramidView pyr, const CellDesc* __restrict__ cells, const FastThreadRec* __restrict__ ttab, int ini_th, int min_th,
                                                                         int slots_per_image, Cand16* __restrict__ slots, int* __restrict__ cell_count,
                                                                         int n_cells, uint32_t gx_magic, unsigned n_fast, PyramidView blur, BlurPlan plan,
                                                                         int blur_blocks) {
     if (blockIdx.x < n_fast) {
-        fast_cells_body<ALIGNED, GEO>(pyr, cells, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic, blockIdx.x, (unsigned)n_cells, n_fast);
+        fast_cells_body<ALIGNED, GEO>(pyr, cells, ttab, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic, blockIdx.x, (unsigned)n_cells, n_fast);
         return;
     }
     constexpr int kWavesPerWg = GEO::kThreads / 64, kWgPerTile = 4 / kWavesPerWg;   // 128 threads: two workgroups per blur block
@@ -1124,6 +1155,34 @@ __device__ __forceinline__ int wave_sum_dpp(int v) {
     return __builtin_amdgcn_readlane(v, 63);
 }
 
+// Eight wave sums in one folded butterfly: every exchange halves the number of live values instead of carrying all eight through
+// all six steps.  v_permlane32_swap trades the upper half of one value for the lower half of another, so one add leaves each half
+// of the wave with the partial sums of ONE of the two (4 swaps + 4 adds: eight values to four); inside a row of 16 lanes the same
+// fold is select, select, DPP add: over row_mirror (lanes 0-7 keep the first of a pair, lanes 8-15 the second: four to two), over
+// row_half_mirror (bit 2 of the lane: two to one); two quad_perm adds finish.  Returned: in all four lanes of quad q = lane >> 2 the
+// sum over the lane's row AND the row 32 lanes away of v[4 (q >> 3) + (q >> 1 & 1) + 2 (q & 1)]; the rows of a half (q >> 2 & 1) are
+// left for the reader to add.  19 instructions (4 swaps, 4 adds, 6 selects, 3 + 2 DPP adds) and 4 for the two lane-bit masks, for
+// 8 x 6 DPP adds + 8 v_readlane.
+__device__ __forceinline__ int wave_sum8_fold(const int (&v)[8], int lane) {
+    int w[4], x[2];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {   // lanes 0-31: v[j], lanes 32-63: v[j + 4]
+        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v[j], (unsigned)v[j + 4], false, false);
+        w[j] = (int)(r[0] + r[1]);
+    }
+    const bool b3 = (lane & 8) != 0, b2 = (lane & 4) != 0;
+#pragma unroll
+    for (int j = 0; j < 2; j++) {   // lane l receives from lane 15 - l of its row: the other half of the row
+        const int keep = b3 ? w[2 * j + 1] : w[2 * j], send = b3 ? w[2 * j] : w[2 * j + 1];
+        x[j] = keep + __builtin_amdgcn_update_dpp(0, send, 0x140 /* row_mirror */, 0xf, 0xf, false);
+    }
+    const int keep = b2 ? x[1] : x[0], send = b2 ? x[0] : x[1];   // lane l receives from lane l ^ 7: same bit 3, other bit 2
+    int s = keep + __builtin_amdgcn_update_dpp(0, send, 0x141 /* row_half_mirror */, 0xf, 0xf, false);
+    s += __builtin_amdgcn_update_dpp(0, s, 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, false);
+    s += __builtin_amdgcn_update_dpp(0, s, 0x4E /* quad_perm [2,3,0,1] */, 0xf, 0xf, false);
+    return s;
+}
+
 // cvRound for |x| < 2^22 as one fp32 add and one integer subtract (both fast-class VALU ops; v_rndne_f32 + v_cvt_i32_f32
 // are two slow-class ones): adding 1.5 * 2^23 leaves round-to-nearest-even of x in the low mantissa bits.
 __device__ __forceinline__ int rint_small(float x) { return __float_as_int(__fadd_rn(x, 12582912.0f)) - 0x4B400000; }
@@ -1169,6 +1228,11 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
                                                        LevelScale scales, msorb_keypoint* __restrict__ kps,
                                                        uint8_t* __restrict__ desc, int out_stride, int atan2_fma, uint32_t gx_magic) {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kDescWaves * kKpPerWave][kBlkSlot];  // one slot per (wave, keypoint)
+    // phase V's mailbox: the moments of every wave's keypoints in, (angle, cos, sin) of the workgroup's keypoints out.  512 bytes:
+    // six workgroups of 25,600 + 512 bytes still share a CU's 160 KB (at most 1 KB may be added here, static_assert below)
+    __shared__ int mom[kDescWaves][16];   // per wave: wave_sum8_fold's result of quad q at [q]
+    __shared__ __attribute__((aligned(16))) float tri[kDescWaves * kKpPerWave][4];
+    static_assert(sizeof(mom) + sizeof(tri) <= 1024, "six descriptor workgroups per CU");
     // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs; give every image to ONE XCD so that the
     // overlapping keypoint patches of an image are served by a single L2 instead of being fetched by all eight.
     int img = blockIdx.y, bx = blockIdx.x;
@@ -1183,7 +1247,9 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int k_first = (bx * kDescWaves + wave) * kKpPerWave;  // wave-uniform -> SALU
     const int n_sel = sel_count[img];
-    if (k_first >= n_sel) return;
+    // A workgroup past the image's last keypoint leaves as a whole.  A WAVE past it stays for the two barriers of phase V: it runs
+    // on the image's last keypoint, like the unused places of a partial wave, and stores nothing.
+    if (bx * (kDescWaves * kKpPerWave) >= n_sel) return;
     // IC-angle patch (raw level, registers): 16-byte loads, three lanes per patch row (lane = 3 row' + seg, 21 rows per load
     // instruction, lane 63 idles): 2 load instructions per keypoint.  The texture addresser spends its cycles per lane address,
     // not per byte (PMC, round 4), so the same bytes in a quarter of the addresses is what shortened this kernel in round 4.
@@ -1247,16 +1313,17 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
     // The last wave of an image repeats the image's last keypoint in its unused places (no exit inside the sequence: the four
     // keypoints are one straight line of code; only the stores are conditional).
     const SelRec* recs = sel + (size_t)img * sel_stride;
+    // Lane l fetches the record of keypoint l & 3 (one load instruction) and keeps it: lanes 0-3 write the keypoint records at the end.
     SelRec R[kKpPerWave];
+    uint32_t rl[3];
+    static_assert(sizeof(SelRec) == sizeof(rl), "a selection record is three dwords");
     {
-        SelRec rv[kKpPerWave];
-#pragma unroll
-        for (int kk = 0; kk < kKpPerWave; kk++) rv[kk] = recs[min(k_first + kk, n_sel - 1)];
+        const uint32_t* mine = reinterpret_cast<const uint32_t*>(recs + min(k_first + (lane & (kKpPerWave - 1)), n_sel - 1));
+        for (int i = 0; i < 3; i++) rl[i] = mine[i];
 #pragma unroll
         for (int kk = 0; kk < kKpPerWave; kk++) {
             uint32_t w[3];
-            memcpy(w, &rv[kk], sizeof(w));
-            for (int i = 0; i < 3; i++) w[i] = __builtin_amdgcn_readfirstlane(w[i]);
+            for (int i = 0; i < 3; i++) w[i] = __builtin_amdgcn_readlane(rl[i], kk);
             memcpy(&R[kk], w, sizeof(w));
         }
     }
@@ -1297,10 +1364,11 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
     Raw Lq[kKpPerWave];
 #pragma unroll
     for (int kk = 0; kk < MSORB_DESC_RAW_DEPTH && kk < kKpPerWave; kk++) issue_raw(R[kk], Lq[kk]);
-    // Phase A, per keypoint: moments of the IC-angle patch (wave-uniform totals).  Phase V, once per wave: angle, cos, sin of all
-    // four keypoints at once — lane kk computes keypoint kk, so the atan2 polynomial and the double-precision sincos run once
-    // per wave instead of once per keypoint.  Phase B, per keypoint: steered BRIEF from its LDS slot.
-    int M10[kKpPerWave], M01[kKpPerWave];
+    // Phase A, per keypoint: moments of the IC-angle patch, per lane; the eight wave sums are taken together afterwards.  Phase V,
+    // once per workgroup: angle, cos, sin of all sixteen keypoints at once — lane k of wave 0 computes keypoint k, so the two
+    // divisions, the atan2 polynomial and the double-precision sincos run once per workgroup instead of once per keypoint (rounds
+    // 1-4) or per wave (rounds 5-6).  Phase B, per keypoint: steered BRIEF from its LDS slot.
+    int mv[2 * kKpPerWave];   // m10 of the four keypoints, then m01
 #pragma unroll
     for (int kk = 0; kk < kKpPerWave; kk++) {
         if (kk + MSORB_DESC_RAW_DEPTH < kKpPerWave) issue_raw(R[kk + MSORB_DESC_RAW_DEPTH], Lq[kk + MSORB_DESC_RAW_DEPTH]);
@@ -1327,27 +1395,34 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
             m10 += (int)su - 16 * (int)sI;
             m01 += vrow[t] * (int)sI;
         }
-        M10[kk] = wave_sum_dpp(m10);  // wave-uniform (SGPR) totals
-        M01[kk] = wave_sum_dpp(m01);
+        mv[kk] = m10;
+        mv[kKpPerWave + kk] = m01;
     }
+    static_assert(kKpPerWave == 4, "wave_sum8_fold sums eight values");
+    mom[wave][lane >> 2] = wave_sum8_fold(mv, lane);   // (the four lanes of a quad store the same word)
+    __syncthreads();
     // Phase V
-    int m10v = M10[0], m01v = M01[0];
-#pragma unroll
-    for (int kk = 1; kk < kKpPerWave; kk++)
-        if (lane == kk) { m10v = M10[kk]; m01v = M01[kk]; }
-    const float angle_v = fast_atan2_deg((float)m01v, (float)m10v, atan2_fma);
-    float a_v, b_v;
-    glibc_sincosf<true>(__fmul_rn(angle_v, factor_pi), &b_v, &a_v);  // a = cos, b = sin (ORBextractor.cc:112)
+    if (wave == 0) {   // wave-uniform
+        const int kp = lane & (kDescWaves * kKpPerWave - 1), wv = kp / kKpPerWave, kk = kp % kKpPerWave;
+        const int q = 2 * (kk & 1) + (kk >> 1);   // quad of mv[kk] in the wave's first row; + 4: its second row; + 8: mv[4 + kk]
+        const int m10v = mom[wv][q] + mom[wv][q + 4], m01v = mom[wv][q + 8] + mom[wv][q + 12];
+        const float angle_v = fast_atan2_deg((float)m01v, (float)m10v, atan2_fma);
+        float a_v, b_v;
+        glibc_sincosf<true>(__fmul_rn(angle_v, factor_pi), &b_v, &a_v);  // a = cos, b = sin (ORBextractor.cc:112)
+        if (lane < kDescWaves * kKpPerWave) *reinterpret_cast<float4*>(tri[lane]) = float4{angle_v, a_v, b_v, 0.f};
+    }
+    __syncthreads();
     glds_wait_all();   // the four slots have landed (the wave reads only what its own lanes' DMA wrote: no barrier needed)
+    if (k_first >= n_sel) return;   // (wave-uniform; no barrier follows, and nothing is on its way into the wave's LDS slots any more)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     // Phase B
 #pragma unroll
     for (int kk = 0; kk < kKpPerWave; kk++) {
         const SelRec r = R[kk];
-        const float angle = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(angle_v), kk));
-        const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(a_v), kk));
-        const float b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(b_v), kk));
+        const float4 t4 = *reinterpret_cast<const float4*>(tri[wave * kKpPerWave + kk]);   // one address for the wave
+        const float a = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t4.y)));
+        const float b = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t4.z)));
         // rr = cvRound(x*b + y*a) + 18 + oy, qq = cvRound(x*a - y*b) + 18 + poff (contraction order of oracle/orb_extractor_oracle.cc:
         // fma(x, b, y*a) and fma(x, a, -(y*b)); y * (-b) is -(y*b) bit for bit), both taps of a test at once as packed fp32.
         // cvRound + offset in one subtract: the magic-number rounding leaves the integer in the low mantissa bits.  Then the
@@ -1389,18 +1464,21 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
             unsigned long long* d = reinterpret_cast<unsigned long long*>(desc + ((size_t)img * out_stride + r.dst) * 32);
             d[lane] = lane == 0 ? word[0] : lane == 1 ? word[1] : lane == 2 ? word[2] : word[3];
         }
-        if (lane == 0) {
-            msorb_keypoint kp;
-            const float sc = scales.scale[r.level];
-            kp.x = r.level ? __fmul_rn((float)r.x, sc) : (float)r.x;   // keypoint->pt *= scale (ORBextractor.cc:1149-1151)
-            kp.y = r.level ? __fmul_rn((float)r.y, sc) : (float)r.y;
-            kp.size = scales.patch[r.level];
-            kp.angle = angle;
-            kp.response = (float)r.score;
-            kp.octave = r.level;
-            kp.class_id = -1;
-            kps[(size_t)img * out_stride + r.dst] = kp;
-        }
+    }
+    // the wave's keypoint records, all at once: lane kk writes keypoint kk from the selection record it fetched itself
+    if (lane < kKpPerWave && k_first + lane < n_sel) {
+        SelRec r;
+        memcpy(&r, rl, sizeof(r));
+        msorb_keypoint kp;
+        const float sc = scales.scale[r.level];
+        kp.x = r.level ? __fmul_rn((float)r.x, sc) : (float)r.x;   // keypoint->pt *= scale (ORBextractor.cc:1149-1151)
+        kp.y = r.level ? __fmul_rn((float)r.y, sc) : (float)r.y;
+        kp.size = scales.patch[r.level];
+        kp.angle = tri[wave * kKpPerWave + lane][0];
+        kp.response = (float)r.score;
+        kp.octave = r.level;
+        kp.class_id = -1;
+        kps[(size_t)img * out_stride + r.dst] = kp;
     }
 }
 
@@ -1746,7 +1824,7 @@ void launch_pyramid(const PyramidView& pyr, const ResizeTap* taps, const size_t*
         launch_pyr_resize(pyr.lv[l - 1], pyr.lv[l], const_cast<uint8_t*>(pyr.lv[l].base), taps + tap_x_off[l], taps + tap_y_off[l], n_images, s,
                           sem.resize_single_stage);
 }
-void launch_fast_cells(const PyramidView& pyr, const CellDesc* cells, int n_cells, int ini_th, int min_th,
+void launch_fast_cells(const PyramidView& pyr, const CellDesc* cells, const FastThreadRec* ttab, int n_cells, int ini_th, int min_th,
                        int slots_per_image, Cand16* slots, int* cell_count, int n_images, bool small_cells, hipStream_t s) {
     bool aligned = true;
     for (int l = 0; l < pyr.nlevels; l++) {
@@ -1756,7 +1834,7 @@ void launch_fast_cells(const PyramidView& pyr, const CellDesc* cells, int n_cell
     const dim3 grid(n_cells, n_images);
     const uint32_t gx_magic = exact_div_magic((unsigned)n_cells, (unsigned long long)n_cells * (unsigned)n_images);
 #define MSORB_FAST_LAUNCH(AL, GEO)                                                                                        \
-    hipLaunchKernelGGL((fast_cells_kernel<AL, GEO>), grid, dim3(GEO::kThreads), 0, s, pyr, cells, ini_th, min_th, slots_per_image, slots, \
+    hipLaunchKernelGGL((fast_cells_kernel<AL, GEO>), grid, dim3(GEO::kThreads), 0, s, pyr, cells, ttab, ini_th, min_th, slots_per_image, slots, \
                        cell_count, n_cells, gx_magic)
     if (small_cells) { if (aligned) MSORB_FAST_LAUNCH(true, GeoSmall); else MSORB_FAST_LAUNCH(false, GeoSmall); }
     else { if (aligned) MSORB_FAST_LAUNCH(true, GeoLarge); else MSORB_FAST_LAUNCH(false, GeoLarge); }
@@ -1843,7 +1921,7 @@ bool make_frame_blur_job(const PyramidView& src, const PyramidView& dst, int n_i
 }
 // FAST + blur of a frame as one launch (frame_fast_blur_kernel); false: the conditions of the one-launch form do not hold (rows
 // not 4-byte aligned, non-default Gaussian taps) and nothing was launched — the caller issues the two launches.
-bool launch_frame_fast_blur(const PyramidView& pyr, const PyramidView& blur, const CellDesc* cells, int n_cells, int ini_th, int min_th,
+bool launch_frame_fast_blur(const PyramidView& pyr, const PyramidView& blur, const CellDesc* cells, const FastThreadRec* ttab, int n_cells, int ini_th, int min_th,
                             int slots_per_image, Cand16* slots, int* cell_count, int n_images, bool small_cells, hipStream_t s,
                             const Semantics& sem) {
     if (!levels_aligned(pyr) || !sem.default_taps()) return false;
@@ -1854,10 +1932,10 @@ bool launch_frame_fast_blur(const PyramidView& pyr, const PyramidView& blur, con
     const uint32_t gx_magic = exact_div_magic((unsigned)n_cells, (unsigned long long)n_cells * (unsigned)n_images);
     if (small_cells)
         hipLaunchKernelGGL((frame_fast_blur_kernel<true, GeoSmall>), dim3(n_fast + (unsigned)blur_blocks * (256 / GeoSmall::kThreads)), dim3(GeoSmall::kThreads), 0, s,
-                           pyr, cells, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic, n_fast, blur, plan, blur_blocks);
+                           pyr, cells, ttab, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic, n_fast, blur, plan, blur_blocks);
     else
         hipLaunchKernelGGL((frame_fast_blur_kernel<true, GeoLarge>), dim3(n_fast + (unsigned)blur_blocks * (256 / GeoLarge::kThreads)), dim3(GeoLarge::kThreads), 0, s,
-                           pyr, cells, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic, n_fast, blur, plan, blur_blocks);
+                           pyr, cells, ttab, ini_th, min_th, slots_per_image, slots, cell_count, n_cells, gx_magic, n_fast, blur, plan, blur_blocks);
     return true;
 }
 void launch_describe(const PyramidView& pyr, const PyramidView& blur, const SelRec* sel, const int* sel_count,

@@ -394,6 +394,28 @@ def distribute_quadtree(xs, ys, scores, min_x, max_x, min_y, max_y, n_features):
     return kept[:nk.value].copy()
 
 
+EXPORTS = EXPORTS + ("msorb_debug_fast_thread_table",)
+FAST_CELL_FIELDS = ("level", "x0", "y0", "rw", "rh", "G", "ndw", "g_magic", "R128", "R256", "by_wave128", "by_wave256", "spw",
+                    "rw128", "yw128", "rw256", "yw256", "tt_off", "level_w", "level_h")
+
+
+def fast_thread_table(rows, cols, nfeatures, scale_factor, nlevels, threads):
+    """Host-only: the FAST kernel's per-thread table for this geometry and workgroup size (include/msorb.h
+    msorb_debug_fast_thread_table) -> (cells int32 [n_cells, len(FAST_CELL_FIELDS)], records uint32 [n_records, 4], n_classes)."""
+    L = lib()
+    ci, vp = C.c_int, C.c_void_p
+    L.msorb_debug_fast_thread_table.argtypes = [ci, ci, ci, C.c_float, ci, ci, vp, ci, C.POINTER(ci), vp, ci, C.POINTER(ci), C.POINTER(ci)]
+    nc, nr, ncl = ci(), ci(), ci()
+    rc = L.msorb_debug_fast_thread_table(rows, cols, nfeatures, scale_factor, nlevels, threads, None, 0, C.byref(nc), None, 0, C.byref(nr), C.byref(ncl))
+    if rc != -4 or nc.value <= 0:   # -4 = MSORB_E_CAPACITY: the counts are known now
+        _check(rc, "fast_thread_table")
+    cells = np.zeros((nc.value, len(FAST_CELL_FIELDS)), np.int32)
+    recs = np.zeros((nr.value, 4), np.uint32)
+    _check(L.msorb_debug_fast_thread_table(rows, cols, nfeatures, scale_factor, nlevels, threads, _np_ptr(cells), len(cells), C.byref(nc),
+                                           _np_ptr(recs), len(recs), C.byref(nr), C.byref(ncl)), "fast_thread_table")
+    return cells, recs, ncl.value
+
+
 # ------------------------------------------------------------------------------------------------
 # Matcher (include/msorb.h "Matcher" section)
 # ------------------------------------------------------------------------------------------------
