@@ -715,6 +715,43 @@ int msorb_kf_database_query(msorb_kf_database* db, const int* word, const double
                             int* entry, int* common_words, double* score, int capacity, int* n_sharing, int* n_listed,
                             int* max_common_words, int* min_common_words, float* elapsed_ms);
 
+/* Optimizer::PoseOptimization (src/Optimizer.cc:759-1037) for pinhole mono / stereo frames on the device: the four rounds, every
+ * Levenberg step and trial of g2o (core/optimization_algorithm_levenberg.cpp:61-170) and the classification after each round in
+ * ONE launch, in double.  Appended to ABI 6002 as the KeyFrame database was: MSORB_ABI_VERSION stays 6002, so a caller that
+ * needs these entries asks the loader for them.  The two-camera arm (:870-931) and the inertial variants are not covered.
+ * An observation is a stereo edge when its u_right >= 0 (:808) and a mono edge otherwise.  Two calls on the same input return
+ * the same bits.  Re-entrant: every calling thread has its own stream and staging. */
+typedef struct msorb_pose_problem {      /* one Optimizer::PoseOptimization call */
+    float q[4], t[3];                    /* pFrame->GetPose(): unit quaternion x,y,z,w + translation */
+    float fx, fy, cx, cy, mbf;
+    int n;                               /* observations */
+} msorb_pose_problem;
+typedef struct msorb_pose_result {
+    float q[4], t[3];                    /* what SetPose receives (:1033-1035) */
+    double qd[4], td[3];                 /* the double estimate before the narrowing */
+    int n_initial, n_bad;                /* return value = n_initial - n_bad */
+    int iterations[4], rejected_trials[4];   /* per round: solve() calls made, trials popped; -1 = round not run */
+} msorb_pose_result;
+/* Observations up to which a problem is held in registers; a larger one walks global memory (same additions, same result). */
+int msorb_pose_optimization_capacity(void);
+/* n_problems independent calls (the relocalisation candidates, :3746-3777 of Tracking.cc) as flat host arrays: one upload, one
+ * launch, one read-back.  Problem i owns the observations [obs_offset[i], obs_offset[i+1]) (obs_offset[0] = 0, the difference =
+ * problems[i].n) of xy [2 per observation: kpUn.pt], u_right, inv_sigma2 (already mvInvLevelSigma2[octave]) and pos_w [3 per
+ * observation: pMP->GetWorldPos()].  Entries the reference skips (no map point, isBad()) are simply not passed.
+ * outlier_out [per observation] = mvbOutlier after the last round.  With n < 3 the reference returns 0 before it touches the
+ * pose (:936-937): q / t repeat the input, the flags are cleared, n_bad = n_initial and every round reads -1.
+ * *elapsed_ms (may be NULL) = device time of the kernel. */
+int msorb_pose_optimization_batch(int device, int n_problems, const msorb_pose_problem* problems, const int* obs_offset,
+                                  const float* xy, const float* u_right, const float* inv_sigma2, const float* pos_w,
+                                  uint8_t* outlier_out, msorb_pose_result* results, float* elapsed_ms);
+/* The frame form: x, y, u_right and the octave are read from the keypoint table resident on the handle, which holds mvKeysUn
+ * only when mvKeysUn == mvKeys, i.e. for rectified input.  has_point [N] marks the keypoints with a usable map point, pos_w
+ * [3 N] their world positions (read where has_point is set), inv_level_sigma2 [nlevels] = mvInvLevelSigma2; p->n is ignored.
+ * Only the indices of the marked keypoints and their positions go up.  outlier [N] is written where has_point is set and left
+ * alone elsewhere.  The result equals msorb_pose_optimization_batch on the same data bit for bit. */
+int msorb_frame_pose_optimization(msorb_frame* f, const msorb_pose_problem* p, const uint8_t* has_point, const float* pos_w,
+                                  const float* inv_level_sigma2, int nlevels, uint8_t* outlier, msorb_pose_result* r);
+
 /* Frame::ComputeStereoMatches (Frame.cc:743-913, median rejection :899-912 included) for every stereo pair of the last
  * msorb_extract_batch() call of `h`, all on the device: pair p = images 2p (left) and 2p+1 (right) of that batch.
  * d_keypoints / d_descriptors / capacity are the arrays that call filled, d_counts[2*n_pairs] the keypoint counts as a

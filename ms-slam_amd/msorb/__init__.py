@@ -571,6 +571,10 @@ class Frame:
                                               len(inv), n, *[_np_ptr(a) for a in arrs], _np_ptr(bi), _np_ptr(bd)), "fuse_search_gated")
         return bi[:n], bd[:n]
 
+    def pose_optimization(self, q, t, cam, has_point, pos_w, inv_level_sigma2, outlier=None):
+        """msorb_frame_pose_optimization (Optimizer::PoseOptimization of this frame): see _frame_pose_optimization"""
+        return _frame_pose_optimization(self, q, t, cam, has_point, pos_w, inv_level_sigma2, outlier)
+
 
 def _sim3_side(p):
     return [_c(p["valid"], np.uint8), _c(p["u"], np.float32), _c(p["v"], np.float32), _c(p["level"], np.int32),
@@ -1804,3 +1808,75 @@ class KeyFrameDatabase:
         k = ns.value
         return dict(entry=ent[:k], common_words=cw[:k], score=sc[:k], n_sharing=k, n_listed=nl.value, max_common_words=mx.value,
                     min_common_words=mn.value, elapsed_ms=ms.value)
+
+
+# ---- Optimizer::PoseOptimization on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_pose_optimization_capacity", "msorb_pose_optimization_batch", "msorb_frame_pose_optimization")
+
+POSE_PROBLEM_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                               ("mbf", "<f4"), ("n", "<i4")])                                    # msorb_pose_problem
+POSE_RESULT_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("_pad", "<i4"), ("qd", "<f8", 4), ("td", "<f8", 3),
+                              ("n_initial", "<i4"), ("n_bad", "<i4"), ("iterations", "<i4", 4),
+                              ("rejected_trials", "<i4", 4)])                                    # msorb_pose_result
+assert POSE_PROBLEM_DTYPE.itemsize == 52 and POSE_RESULT_DTYPE.itemsize == 128
+
+
+def _pose_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_pose_optimization_capacity.argtypes = []
+    L.msorb_pose_optimization_batch.argtypes = [ci, ci] + [vp] * 9
+    L.msorb_frame_pose_optimization.argtypes = [vp, vp, vp, vp, vp, ci, vp, vp]
+    return L
+
+
+def pose_optimization_capacity():
+    """observations up to which the kernel keeps a problem in registers"""
+    return _pose_lib().msorb_pose_optimization_capacity()
+
+
+def pose_problem(q, t, cam, n=0):
+    """one msorb_pose_problem record; cam: dict(fx, fy, cx, cy, mbf)"""
+    p = np.zeros(1, POSE_PROBLEM_DTYPE)
+    p["q"], p["t"], p["n"] = np.asarray(q, np.float32), np.asarray(t, np.float32), n
+    for k in ("fx", "fy", "cx", "cy", "mbf"):
+        p[k] = cam[k]
+    return p
+
+
+def pose_optimization_batch(problems, xy, u_right, inv_sigma2, pos_w, device=0, timing=False):
+    """msorb_pose_optimization_batch: Optimizer::PoseOptimization of every problem in one launch.  problems: POSE_PROBLEM_DTYPE
+    records whose n partition the flat arrays xy [M, 2], u_right [M], inv_sigma2 [M], pos_w [M, 3] in order.
+    -> (results: POSE_RESULT_DTYPE [n_problems], outlier: bool [M]) and, with timing, the kernel's device time in ms."""
+    L = _pose_lib()
+    pr = _c(problems, POSE_PROBLEM_DTYPE).reshape(-1)
+    off = np.zeros(len(pr) + 1, np.int32)
+    off[1:] = np.cumsum(pr["n"])
+    m = int(off[-1])
+    arrs = [_c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1),
+            _c(pos_w, np.float32).reshape(-1)]
+    if [len(a) for a in arrs] != [2 * m, m, m, 3 * m]:
+        raise ValueError("the flat arrays do not hold sum(problems.n) observations")
+    res = np.zeros(len(pr), POSE_RESULT_DTYPE)
+    out = np.zeros(max(m, 1), np.uint8)
+    ms = C.c_float()
+    _check(L.msorb_pose_optimization_batch(device, len(pr), _np_ptr(pr), _np_ptr(off), *[_np_ptr(a) for a in arrs], _np_ptr(out),
+                                           _np_ptr(res), C.addressof(ms)), "msorb_pose_optimization_batch")
+    return (res, out[:m].astype(bool), ms.value) if timing else (res, out[:m].astype(bool))
+
+
+def _frame_pose_optimization(self, q, t, cam, has_point, pos_w, inv_level_sigma2, outlier=None):
+    """msorb_frame_pose_optimization: Optimizer::PoseOptimization of this frame (keypoints, mvuRight and octaves are the handle's;
+    rectified input).  has_point [N] marks the keypoints with a usable map point, pos_w [N, 3] their world positions.
+    -> (POSE_RESULT_DTYPE record, outlier uint8 [N]: written where has_point is set, the rest as passed in / zero)"""
+    L = _pose_lib()
+    hp, pw, inv = _c(has_point, np.uint8), _c(pos_w, np.float32).reshape(-1), _c(inv_level_sigma2, np.float32)
+    if len(hp) != self.n or len(pw) != 3 * self.n:
+        raise ValueError("has_point / pos_w do not match the frame's keypoints")
+    out = np.zeros(max(self.n, 1), np.uint8) if outlier is None else outlier
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and len(out) >= self.n
+    p = pose_problem(q, t, cam)
+    res = np.zeros(1, POSE_RESULT_DTYPE)
+    _check(L.msorb_frame_pose_optimization(self.h, _np_ptr(p), _np_ptr(hp), _np_ptr(pw), _np_ptr(inv), len(inv), _np_ptr(out),
+                                           _np_ptr(res)), "msorb_frame_pose_optimization")
+    return res[0], out[:self.n]
