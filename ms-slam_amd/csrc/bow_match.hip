@@ -28,6 +28,7 @@
 #include "../../include/msorb.h"
 #include "hip_host.h"
 #include "matcher_device.h"
+#include "matcher_rules.h"
 #include "store_arena.h"
 
 namespace msorb {
@@ -37,6 +38,7 @@ hipError_t small_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind ki
 }
 using msorb::set_last_error;
 using msorb::kHistoLength;
+using msorb::rotation_bin;
 using msorb::ThreadScratch;
 using msorb::up16;
 
@@ -398,7 +400,6 @@ int replay_histogram(const FeatVec& a, const std::vector<Common>& common, const 
     // vectors it cost 23 us per pair, seven times the whole device part of a 32-pair batch
     static thread_local std::vector<int8_t> bin_of;
     int sizes[kHistoLength] = {0};
-    const float factor = 1.0f / kHistoLength;
     int nm = 0, n_feat = 0;
     for (const Common& c : common) n_feat = std::max(n_feat, a.begin[c.r1 + 1]);
     if (check_orientation && (int)bin_of.size() < n_feat) bin_of.resize(n_feat);
@@ -411,11 +412,8 @@ int replay_histogram(const FeatVec& a, const std::vector<Common>& common, const 
             if (check_orientation) {
                 float a1, a2;
                 angle(idx1, idx2, a1, a2);
-                float rot = a1 - a2;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int)std::round(rot * factor);
-                if (bin == kHistoLength) bin = 0;
-                if (bin >= 0 && bin < kHistoLength) { bin_of[k] = (int8_t)bin; sizes[bin]++; }
+                const int bin = rotation_bin(a1, a2);
+                if (bin >= 0) { bin_of[k] = (int8_t)bin; sizes[bin]++; }
                 else { match12[idx1] = -1; nm--; }  // NaN / out-of-range angle: the reference asserts
             }
         }
@@ -605,7 +603,6 @@ extern "C" int msorb_search_by_bow_rig(int device, msorb_bow_pair* pair, int n_l
     // order, the left match of a feature before its right match (:338-353, :361-378); then ComputeThreeMaxima (:396-418)
     for (int j = 0; j < P.n2; j++) P.match21[j] = -1;
     std::vector<std::pair<int, int>> hist[kHistoLength];   // (frame feature, KeyFrame feature)
-    const float factor = 1.0f / kHistoLength;
     int nm = 0;
     int i = 0, j = 0;
     while (i < fa.nodes && j < fb.nodes) {
@@ -618,11 +615,8 @@ extern "C" int msorb_search_by_bow_rig(int device, msorb_bow_pair* pair, int n_l
                     P.match21[i2] = i1;
                     nm++;
                     if (check_orientation) {
-                        float rot = P.angle1[i1] - P.angle2[i2];
-                        if (rot < 0.0) rot += 360.0f;
-                        int bin = (int)std::round(rot * factor);
-                        if (bin == kHistoLength) bin = 0;
-                        if (bin >= 0 && bin < kHistoLength) hist[bin].push_back({i2, i1});
+                        const int bin = rotation_bin(P.angle1[i1], P.angle2[i2]);
+                        if (bin >= 0) hist[bin].push_back({i2, i1});
                         else { P.match21[i2] = -1; nm--; }
                     }
                 }

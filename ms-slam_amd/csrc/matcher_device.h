@@ -4,12 +4,9 @@
 #include <stdint.h>
 
 #include "../../include/msorb.h"
+#include "window_query.h"   // the grid / threshold constants, kTopK, the kQ* flags, WinQuery, TopK
 
 namespace msorb {
-
-constexpr int kGridCols = 64, kGridRows = 48;  // FRAME_GRID_COLS / FRAME_GRID_ROWS, Frame.h:44-45
-constexpr int kThHigh = 100, kThLow = 50, kHistoLength = 30;  // ORBmatcher.cc:35-37
-constexpr int kTopK = 8;  // candidates kept per query: with 4 a busy frame needed 4-5 device rounds (exhausted lists), with 8 fewer
 
 struct KpLite {  // what the window search needs of one train keypoint (16 B, one load)
     float x, y, u_right;
@@ -27,16 +24,6 @@ struct FrameView {
     const KpLite* gate_kp;  // nullptr, or n keypoints the level band and the kQFuseGate error test read INSTEAD of kp (the window test
                             // stays on kp): ORBmatcher::Fuse(..., bRight = true) walks the right camera's grid but reads
                             // pKF->GetKeyPoint(idx) / GetuRight(idx) with that right-camera index (ORBmatcher.cc:1502, 1509-1545)
-};
-constexpr uint8_t kQValid = 1, kQSkipOccupied = 2, kQFuseGate = 4, kQNoUr = 8;
-struct WinQuery {
-    float x, y, r, ur;
-    int16_t min_level, max_level;
-    uint8_t flags, pad[3];
-};
-struct TopK {
-    int idx[kTopK];
-    int dist[kTopK];
 };
 struct StereoArgs {
     const msorb_keypoint *kpL, *kpR;

@@ -1,5 +1,5 @@
 // Internals shared by the host-side matcher sources (matcher_host.hip, track.hip): the frame handle (features + 64x48
-// grid on the device) and the claiming window search.  Not part of the C ABI.
+// grid on the device) and the device rounds of the claiming window search (its replay rule: claim_replay.h).  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,8 +12,10 @@
 #include <string>
 #include <vector>
 
+#include "claim_replay.h"
 #include "hip_host.h"
 #include "matcher_device.h"
+#include "matcher_rules.h"
 #include "orb_device.h"
 
 namespace msorb {
@@ -76,134 +78,111 @@ struct msorb_frame {
 
 namespace msorb {
 
-// Shared replay driver of the claiming window searches (SearchByProjection forms, ORBmatcher.cc:88-90,129).
-// The device computes, for every query at once, the kTopK best candidates against an occupancy SNAPSHOT; the host replays
-// the accept rules in query order, dropping candidates claimed since the snapshot.  If a query's list is exhausted or a
-// keypoint was freed (mbSparsified bypass), the snapshot is refreshed and the kernel re-run from that query on.
+inline HostGrid host_grid(const msorb_frame* f) {   // valid after frame_host_grid(f)
+    return HostGrid{f->kps.data(), f->cell_begin.data(), f->cell_idx.data(), f->minX, f->minY, f->gridWInv, f->gridHInv};
+}
+
+// Device side of one frame's claiming window search: what a round of the replay (claim_replay.h) runs.
 //   q / qdesc   host queries + descriptors to upload; nullptr: f->d_q / f->d_qdesc already hold them (built on the device)
+//   d_qdesc     device query descriptors when they do not live in f->d_qdesc
+//   lanes       lanes per query of the window kernel (0: chosen from the mean radius of the host queries)
+// A frame without keypoints has no device side: prepare and round do nothing.
+struct WindowRounds {
+    msorb_frame* f = nullptr;
+    int M = 0, lanes = 0;
+    const WinQuery* q_dev = nullptr;
+    const uint8_t* d_qdesc = nullptr;
+    uint8_t *occ_dev = nullptr, *h_occ = nullptr;
+    size_t block_bytes = 0;   // host queries + host descriptors: queries | descriptors staged ahead of the occupancy, pending as ONE upload
+                              // that the first round() issues (and zeroes this): such a search has no round 0 run by the caller
+
+    int prepare(msorb_frame* frame, int n_queries, const WinQuery* q, const uint8_t* qdesc, const uint8_t* qdesc_dev, int n_lanes) {
+        f = frame; M = n_queries; lanes = n_lanes; d_qdesc = qdesc_dev;
+        if (f->N <= 0) return MSORB_OK;
+        int rc;
+        if ((rc = f->d_q.ensure(M)) || (!d_qdesc && (rc = f->d_qdesc.ensure((size_t)M * 32))) || (rc = f->d_topk.ensure(M)) ||
+            (rc = f->d_occ.ensure(f->N)))
+            return rc;
+        // host queries + host descriptors (the class paths: ORBmatcher::SearchByProjection with unchanged callers): queries, descriptors
+        // and the occupancy snapshot are staged side by side and go up as ONE copy into one device block (three copy launches before:
+        // each costs the host ~6 us to issue and the chain ~3 us)
+        const bool one_block = q && qdesc && !d_qdesc;
+        if (!d_qdesc) d_qdesc = f->d_qdesc.p;
+        hipStream_t s = f->stream;
+        const size_t qb = q ? (size_t)M * sizeof(WinQuery) : 0, db = qdesc ? (size_t)M * 32 : 0;
+        const size_t qb16 = (qb + 15) & ~(size_t)15;
+        if ((rc = f->h_in.ensure(qb16 + db + (size_t)f->N + 64)) || (rc = f->h_topk.ensure(M))) return rc;
+        if (one_block && (rc = f->d_win.ensure(qb16 + db + (size_t)f->N + 64))) return rc;
+        q_dev = one_block ? reinterpret_cast<const WinQuery*>(f->d_win.p) : f->d_q.p;
+        if (one_block) d_qdesc = f->d_win.p + qb16;
+        occ_dev = one_block ? f->d_win.p + qb16 + db : f->d_occ.p;
+        h_occ = f->h_in.p + qb16 + db;
+        if (lanes == 0) {   // lanes per query from the mean window radius of the valid queries
+            lanes = 16;
+            if (q) {
+                double sum = 0;
+                int nv = 0;
+                for (int i = 0; i < M; i++)
+                    if (q[i].flags & kQValid) { sum += q[i].r; nv++; }
+                if (nv) lanes = window_lanes_for((float)(sum / nv), f->gridWInv, f->gridHInv);
+            }
+        }
+        if (q) std::memcpy(f->h_in.p, q, qb);
+        if (qdesc) std::memcpy(f->h_in.p + qb16, qdesc, db);
+        if (one_block) block_bytes = qb16 + db;
+        else {
+            if (q) HIPCHK(small_copy(f->d_q.p, f->h_in.p, qb, hipMemcpyHostToDevice, s));
+            if (qdesc) HIPCHK(small_copy(f->d_qdesc.p, f->h_in.p + qb16, db, hipMemcpyHostToDevice, s));
+        }
+        return MSORB_OK;
+    }
+    // the lists of queries [from, M) against the occupancy occ, into f->h_topk (stream synchronised)
+    int round(const uint8_t* occ, int from) {
+        if (f->N <= 0) return MSORB_OK;
+        hipStream_t s = f->stream;
+        std::memcpy(h_occ, occ, f->N);  // the previous round's copy has completed (stream synchronised below)
+        if (block_bytes) {
+            HIPCHK(small_copy(f->d_win.p, f->h_in.p, block_bytes + (size_t)f->N, hipMemcpyHostToDevice, s));   // queries | descriptors | occupancy
+            block_bytes = 0;
+        } else
+            HIPCHK(small_copy(occ_dev, h_occ, f->N, hipMemcpyHostToDevice, s));
+        FrameView view = f->view();
+        view.occupied = occ_dev;
+        launch_window_topk(view, q_dev, d_qdesc, from, M, f->d_topk.p, s, 1, 0, 0, nullptr, lanes);
+        HIPCHK(small_copy(f->h_topk.p + from, f->d_topk.p + from, (size_t)(M - from) * sizeof(TopK), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        return MSORB_OK;
+    }
+    ClaimSide side(const WinQuery* q, const uint8_t* flags, uint8_t* occ) const {
+        ClaimSide S;
+        S.kps = f->kps.data(); S.N = f->N; S.q = q; S.flags = flags; S.topk = f->h_topk.p; S.occ = occ;
+        return S;
+    }
+    void account(int rounds) const { f->last_rounds = rounds; f->total_rounds += rounds; f->total_searches++; }   // msorb_frame_search_rounds
+};
+
+// One-camera claiming window search: replay_claims (claim_replay.h) over the device rounds of frame f.
 //   flags       kQValid / kQSkipOccupied per query; nullptr: taken from q
 //   ready       round 0 has been run by the caller: f->d_occ holds `occ`, f->h_topk[0, M) the lists (stream synchronised)
-//   d_qdesc     device query descriptors when they do not live in f->d_qdesc (read by the re-runs)
-//   lanes       lanes per query of the window kernel (0: chosen from the mean radius of the host queries)
-// accept(q, idx, dist, n, &new_occ) is called in query order with the query's exact candidate prefix (>= need entries unless
-// the true candidate set is smaller); it returns the keypoint index it assigned (or -1) and that keypoint's new occupancy.
+// q / qdesc / d_qdesc / lanes as WindowRounds takes them, accept as replay_claims takes it.
 template <typename Accept>
 int run_window_search(msorb_frame* f, int M, const WinQuery* q, const uint8_t* flags, const uint8_t* qdesc,
                       std::vector<uint8_t>& occ, int need, Accept accept, bool ready = false, int* rounds_out = nullptr,
                       const uint8_t* d_qdesc = nullptr, int lanes = 0) {
     if (rounds_out) *rounds_out = 0;
     if (M <= 0 || f->N <= 0) return MSORB_OK;   // no queries / no train keypoints (also a handle whose set failed): no match
-    int rc;
-    if ((rc = f->d_q.ensure(M)) || (!d_qdesc && (rc = f->d_qdesc.ensure((size_t)M * 32))) || (rc = f->d_topk.ensure(M)) ||
-        (rc = f->d_occ.ensure(f->N)))
-        return rc;
-    // host queries + host descriptors (the class paths: ORBmatcher::SearchByProjection with unchanged callers): queries, descriptors
-    // and the occupancy snapshot are staged side by side and go up as ONE copy into one device block (three copy launches before:
-    // each costs the host ~6 us to issue and the chain ~3 us)
-    const bool one_block = q && qdesc && !d_qdesc;
-    if (!d_qdesc) d_qdesc = f->d_qdesc.p;
-    hipStream_t s = f->stream;
-    const size_t qb = q ? (size_t)M * sizeof(WinQuery) : 0, db = qdesc ? (size_t)M * 32 : 0;
-    const size_t qb16 = (qb + 15) & ~(size_t)15;
-    if ((rc = f->h_in.ensure(qb16 + db + (size_t)f->N + 64)) || (rc = f->h_topk.ensure(M))) return rc;
-    if (one_block && (rc = f->d_win.ensure(qb16 + db + (size_t)f->N + 64))) return rc;
-    const WinQuery* const q_dev = one_block ? reinterpret_cast<const WinQuery*>(f->d_win.p) : f->d_q.p;
-    if (one_block) d_qdesc = f->d_win.p + qb16;
-    uint8_t* const occ_dev = one_block ? f->d_win.p + qb16 + db : f->d_occ.p;
-    std::vector<uint8_t> flags_own;
-    if (!flags) {
-        if (!q) return MSORB_E_INVALID;
-        flags_own.resize(M);
-        for (int i = 0; i < M; i++) flags_own[i] = q[i].flags;
-        flags = flags_own.data();
+    if (!flags && !q) return MSORB_E_INVALID;
+    if (ready && q && qdesc && !d_qdesc) {   // a round 0 of the caller's cannot have read queries that are still to go up
+        set_last_error("run_window_search: ready with host queries and host descriptors");
+        return MSORB_E_INVALID;
     }
-    if (lanes == 0) {   // lanes per query from the mean window radius of the valid queries
-        lanes = 16;
-        if (q) {
-            double sum = 0;
-            int nv = 0;
-            for (int i = 0; i < M; i++)
-                if (q[i].flags & kQValid) { sum += q[i].r; nv++; }
-            if (nv) lanes = window_lanes_for((float)(sum / nv), f->gridWInv, f->gridHInv);
-        }
-    }
-    if (one_block) {
-        std::memcpy(f->h_in.p, q, qb);
-        std::memcpy(f->h_in.p + qb16, qdesc, db);
-    } else {
-        if (q) {
-            std::memcpy(f->h_in.p, q, qb);
-            HIPCHK(small_copy(f->d_q.p, f->h_in.p, qb, hipMemcpyHostToDevice, s));
-        }
-        if (qdesc) {
-            std::memcpy(f->h_in.p + qb16, qdesc, db);
-            HIPCHK(small_copy(f->d_qdesc.p, f->h_in.p + qb16, db, hipMemcpyHostToDevice, s));
-        }
-    }
-    uint8_t* const h_occ = f->h_in.p + qb16 + db;
-    TopK* const topk = f->h_topk.p;
-    std::vector<int8_t> diff(f->N, 0);  // occupancy now vs snapshot: +1 claimed since, -1 freed since
-    // a keypoint that was occupied at the snapshot and is free now is missing from the lists of exactly those queries whose window
-    // (box and level band as window_topk_kernel tests them; its mvuRight test can only drop more) holds it: only they need a new round
-    std::vector<int> freed;
-    auto holds_freed = [&](const WinQuery& w) {
-        for (int idx : freed) {
-            if (diff[idx] >= 0) continue;
-            const msorb_keypoint& kp = f->kps[idx];
-            if (kp.octave < w.min_level || (w.max_level >= 0 && kp.octave > w.max_level)) continue;
-            if (fabsf(kp.x - w.x) < w.r && fabsf(kp.y - w.y) < w.r) return true;
-        }
-        return false;
-    };
-    int q0 = 0, n_rounds = 0;
-    while (q0 < M) {
-        if (!(ready && n_rounds == 0)) {
-            if (f->N) std::memcpy(h_occ, occ.data(), f->N);  // the previous round's copy has completed (stream synchronised below)
-            if (one_block && n_rounds == 0)
-                HIPCHK(small_copy(f->d_win.p, f->h_in.p, qb16 + db + (size_t)f->N, hipMemcpyHostToDevice, s));   // queries | descriptors | occupancy
-            else if (f->N)
-                HIPCHK(small_copy(occ_dev, h_occ, f->N, hipMemcpyHostToDevice, s));
-            FrameView view = f->view();
-            view.occupied = occ_dev;
-            launch_window_topk(view, q_dev, d_qdesc, q0, M, f->d_topk.p, s, 1, 0, 0, nullptr, lanes);
-            HIPCHK(small_copy(topk + q0, f->d_topk.p + q0, (size_t)(M - q0) * sizeof(TopK), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-        }
-        std::vector<uint8_t> snap = occ;
-        std::fill(diff.begin(), diff.end(), 0);
-        int n_freed = 0;
-        freed.clear();
-        int qi = q0;
-        bool resync = false;
-        for (; qi < M; qi++) {
-            if (!(flags[qi] & kQValid)) continue;
-            const bool skip = flags[qi] & kQSkipOccupied;
-            if (skip && n_freed > 0 && qi > q0 && (!q || holds_freed(q[qi]))) { resync = true; break; }   // (queries built on the device: windows unknown here)
-            const TopK& t = topk[qi];
-            int idx[kTopK], dist[kTopK], n = 0, n_dev = 0;
-            for (int k = 0; k < kTopK; k++) {
-                if (t.idx[k] < 0) break;
-                n_dev++;
-                if (skip && diff[t.idx[k]] > 0) continue;
-                idx[n] = t.idx[k]; dist[n] = t.dist[k]; n++;
-            }
-            if (n < need && n < n_dev && n_dev == kTopK && qi > q0) { resync = true; break; }
-            int new_occ = 0;
-            const int assigned = accept(qi, idx, dist, n, &new_occ);
-            if (assigned >= 0) {
-                occ[assigned] = (uint8_t)new_occ;
-                const int8_t d = (int8_t)((int)occ[assigned] - (int)snap[assigned]);
-                if (diff[assigned] < 0) n_freed--;
-                diff[assigned] = d;
-                if (d < 0) { n_freed++; freed.push_back(assigned); }
-            }
-        }
-        n_rounds++;
-        if (!resync) break;
-        q0 = qi;
-    }
-    if (rounds_out) *rounds_out = n_rounds;
-    f->last_rounds = n_rounds; f->total_rounds += n_rounds; f->total_searches++;
+    WindowRounds dev;
+    if (const int rc = dev.prepare(f, M, q, qdesc, d_qdesc, lanes)) return rc;
+    ClaimSide S = dev.side(q, flags, occ.data());
+    const int rounds = replay_claims(S, M, need, ready, [&](int from) { return dev.round(occ.data(), from); }, accept);
+    if (rounds < 0) return rounds;
+    if (rounds_out) *rounds_out = rounds;
+    dev.account(rounds);
     return MSORB_OK;
 }
 

@@ -1,13 +1,6 @@
-// Matcher side of the C ABI: frame handle (features + 64x48 grid on the device), the sequential replay
-// that reproduces the reference's in-loop side effects, stereo matching orchestration.
-//
-// Sequential side effects.  SearchByProjection assigns F.mvpMapPoints[bestIdx] inside
-// its loop and later map points skip keypoints that hold a map point with Observations() > 0
-// (ORBmatcher.cc:88-90,129).  The device computes, for every query at once, the kTopK best candidates
-// against an occupancy SNAPSHOT; the host then replays the accept rules in query order, dropping
-// candidates claimed since the snapshot.  If a query's list is exhausted (all but <2 of a full list were
-// claimed) or a keypoint was freed (only possible through the mbSparsified bypass), the snapshot is
-// refreshed and the kernel re-run from that query on — the result is always the reference's.
+// Matcher side of the C ABI: frame handle (features + 64x48 grid on the device), the searches whose sequential
+// side effects are replayed on the host (the rule: claim_replay.h, its device rounds: matcher_host.h),
+// stereo matching orchestration.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -115,30 +108,11 @@ int msorb_frame_features_in_area(const msorb_frame* f, float x, float y, float r
         const int rc = frame_host_grid(const_cast<msorb_frame*>(f));
         if (rc) return rc;
     }
-    const int minCX = std::max(0, (int)std::floor((x - f->minX - r) * f->gridWInv));
-    if (minCX >= kGridCols) return MSORB_OK;
-    const int maxCX = std::min(kGridCols - 1, (int)std::ceil((x - f->minX + r) * f->gridWInv));
-    if (maxCX < 0) return MSORB_OK;
-    const int minCY = std::max(0, (int)std::floor((y - f->minY - r) * f->gridHInv));
-    if (minCY >= kGridRows) return MSORB_OK;
-    const int maxCY = std::min(kGridRows - 1, (int)std::ceil((y - f->minY + r) * f->gridHInv));
-    if (maxCY < 0) return MSORB_OK;
-    const bool check = (min_level > 0) || (max_level >= 0);
-    for (int ix = minCX; ix <= maxCX; ix++)
-        for (int iy = minCY; iy <= maxCY; iy++) {
-            const int c = ix * kGridRows + iy;
-            for (int j = f->cell_begin[c]; j < f->cell_begin[c + 1]; j++) {
-                const msorb_keypoint& kp = f->kps[f->cell_idx[j]];
-                if (check) {
-                    if (kp.octave < min_level) continue;
-                    if (max_level >= 0 && kp.octave > max_level) continue;
-                }
-                if (std::fabs(kp.x - x) < r && std::fabs(kp.y - y) < r) {
-                    if (n < capacity) out[n] = f->cell_idx[j];
-                    n++;
-                }
-            }
-        }
+    walk_features_in_area(host_grid(f), x, y, r, min_level, max_level, [&](int idx) {
+        if (n < capacity) out[n] = idx;
+        n++;
+        return true;
+    });
     *n_out = n;
     return n > capacity ? MSORB_E_CAPACITY : MSORB_OK;
 }
@@ -154,23 +128,12 @@ int msorb_search_by_projection_mps(msorb_frame* f, int M, const uint8_t* track_i
         return MSORB_E_INVALID;
     HIPCHK(hipSetDevice(f->device));
     *nmatches = 0;
-    const bool bFactor = th != 1.0;
     std::vector<WinQuery> q(M);
     for (int i = 0; i < M; i++) {
-        WinQuery w{};
-        bool valid = track_in_view[i] && !(far_points && track_depth[i] > th_far) && !bad[i];
-        if (valid && (level[i] < 0 || level[i] >= f->nlevels)) { set_last_error("predicted level out of range"); return MSORB_E_INVALID; }
-        if (valid) {
-            float r = (view_cos[i] > 0.998) ? 2.5 : 4.0;  // RadiusByViewingCos, ORBmatcher.cc:215-221
-            if (bFactor) r *= th;
-            w.x = proj_x[i]; w.y = proj_y[i];
-            w.r = r * f->scale[level[i]];
-            w.ur = proj_xr[i];
-            w.min_level = (int16_t)(level[i] - 1);
-            w.max_level = (int16_t)level[i];
-            w.flags = kQValid | (sparsified[i] ? 0 : kQSkipOccupied);
-        }
-        q[i] = w;
+        const bool valid = track_in_view[i] && !(far_points && track_depth[i] > th_far) && !bad[i];
+        if (!valid) { q[i] = WinQuery{}; continue; }
+        if (level[i] < 0 || level[i] >= f->nlevels) { set_last_error("predicted level out of range"); return MSORB_E_INVALID; }
+        q[i] = map_point_left_query(proj_x[i], proj_y[i], proj_xr[i], level[i], view_cos[i], th, f->scale.data(), sparsified[i]);
     }
     std::vector<uint8_t> occ(f->N);
     for (int i = 0; i < f->N; i++) {
@@ -179,21 +142,12 @@ int msorb_search_by_projection_mps(msorb_frame* f, int M, const uint8_t* track_i
     }
     int nm = 0;
     auto accept = [&](int qi, const int* idx, const int* dist, int n, int* new_occ) -> int {
-        if (n == 0) return -1;
-        const int bestDist = dist[0], bestIdx = idx[0];
-        const int bestLevel = f->kps[bestIdx].octave;
-        const int bestDist2 = n > 1 ? dist[1] : 256;
-        const int bestLevel2 = n > 1 ? f->kps[idx[1]].octave : -1;
-        if (bestDist <= kThHigh) {  // ORBmatcher.cc:122-141
-            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) return -1;
-            if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                frame_mp[bestIdx] = qi;
-                nm++;
-                *new_occ = obs[qi] > 0;
-                return bestIdx;
-            }
-        }
-        return -1;
+        const int bestIdx = accept_best_of_two(f->kps.data(), idx, dist, n, nnratio);
+        if (bestIdx < 0) return -1;
+        frame_mp[bestIdx] = qi;
+        nm++;
+        *new_occ = obs[qi] > 0;
+        return bestIdx;
     };
     const int rc = run_window_search(f, M, q.data(), nullptr, mp_desc, occ, 2, accept);
     *nmatches = nm;
@@ -204,103 +158,10 @@ int msorb_search_by_projection_mps(msorb_frame* f, int M, const uint8_t* track_i
 // the KannalaBrandt8 stereo rig), ORBmatcher.cc:43-213 with both arms: per map point a LEFT pass (mbTrackInView: window in the left
 // camera's grid, best / second over the left keypoints, :61-142) and a RIGHT pass (mbTrackInViewR: window in the right camera's grid,
 // :144-210).  The two cameras are two device frames (left: F.mvKeys[0, Nleft), right: F.mvKeysRight — what Frame::GetFeaturesInArea
-// walks for such a frame, Frame.cc:589-655 with bRight); F.mvpMapPoints is one array of n_left + n_right entries.  What couples
-// the passes, all replayed here in map-point order:
-//   * a left match also claims the right keypoint it is stereo-matched with (mvLeftToRightMatch, :130-134), a right match the left
-//     one (mvRightToLeftMatch, :196-200): the occupancy each LATER map point sees on either side;
-//   * a left pass that fails its ratio test `continue`s the map-point loop (:125-126): the right pass of that point is skipped;
-//   * the right pass does not scale its radius by th (:148) and has no mbSparsified bypass (:169-171).
-// Both device searches run against occupancy snapshots; the replay drops candidates claimed since and re-runs a side from the first
-// query whose list is exhausted (run_window_search's rule, per side).
-namespace {
-struct RigSide {
-    msorb_frame* f = nullptr;
-    std::vector<WinQuery> q;
-    std::vector<uint8_t> occ, snap;
-    std::vector<int8_t> diff;   // occupancy now vs the snapshot the side's lists were computed against
-    int n_freed = 0, next = 0, fresh_from = 0, lanes = 16, rounds = 0;
-    bool pristine = true;   // no occupancy change since the last round: only then is the list of query `fresh_from` exact as it stands.  (The
-                            // OTHER camera's pass of the same map point can change this side between its round and its first query: a left
-                            // match of a point without observations frees the right partner it overwrites, ORBmatcher.cc:130-134.)
-    uint8_t* h_occ = nullptr;
-    int prepare(int M, const uint8_t* mp_desc) {   // queries + query descriptors to the device, once
-        int rc;
-        if ((rc = f->d_q.ensure(M)) || (rc = f->d_qdesc.ensure((size_t)M * 32)) || (rc = f->d_topk.ensure(M)) || (rc = f->d_occ.ensure(std::max(f->N, 1))))
-            return rc;
-        const size_t qb = (size_t)M * sizeof(WinQuery), db = (size_t)M * 32;
-        if ((rc = f->h_in.ensure(qb + db + (size_t)f->N + 64)) || (rc = f->h_topk.ensure(M))) return rc;
-        double sum = 0;
-        int nv = 0;
-        for (int i = 0; i < M; i++)
-            if (q[i].flags & kQValid) { sum += q[i].r; nv++; }
-        if (nv) lanes = window_lanes_for((float)(sum / nv), f->gridWInv, f->gridHInv);
-        std::memcpy(f->h_in.p, q.data(), qb);
-        std::memcpy(f->h_in.p + qb, mp_desc, db);
-        HIPCHK(small_copy(f->d_q.p, f->h_in.p, qb, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(small_copy(f->d_qdesc.p, f->h_in.p + qb, db, hipMemcpyHostToDevice, f->stream));
-        h_occ = f->h_in.p + qb + db;
-        diff.assign(f->N, 0);
-        return MSORB_OK;
-    }
-    int round(int M) {   // the side's lists for queries [next, M) against its occupancy as it is now
-        if (f->N > 0 && next < M) {
-            std::memcpy(h_occ, occ.data(), f->N);
-            HIPCHK(small_copy(f->d_occ.p, h_occ, f->N, hipMemcpyHostToDevice, f->stream));
-            launch_window_topk(f->view(), f->d_q.p, f->d_qdesc.p, next, M, f->d_topk.p, f->stream, 1, 0, 0, nullptr, lanes);
-            HIPCHK(small_copy(f->h_topk.p + next, f->d_topk.p + next, (size_t)(M - next) * sizeof(TopK), hipMemcpyDeviceToHost, f->stream));
-            HIPCHK(hipStreamSynchronize(f->stream));
-        }
-        snap = occ;
-        std::fill(diff.begin(), diff.end(), 0);
-        n_freed = 0;
-        fresh_from = next;
-        pristine = true;
-        freed.clear();
-        rounds++;
-        return MSORB_OK;
-    }
-    std::vector<int> freed;   // keypoints freed since the round (entries whose diff is no longer negative were claimed again)
-    void set_occ(int idx, int v) {
-        pristine = false;
-        occ[idx] = (uint8_t)v;
-        const int8_t d = (int8_t)((int)occ[idx] - (int)snap[idx]);
-        if (diff[idx] < 0) n_freed--;
-        diff[idx] = d;
-        if (d < 0) { n_freed++; freed.push_back(idx); }
-    }
-    // a keypoint that was occupied at the round and is free now is missing from the lists of exactly those queries whose window
-    // (box and level band, as window_topk_kernel tests them) holds it: only such a query needs a new round
-    bool window_holds_a_freed_keypoint(const WinQuery& w) const {
-        for (int idx : freed) {
-            if (diff[idx] >= 0) continue;
-            const msorb_keypoint& kp = f->kps[idx];
-            if (kp.octave < w.min_level || (w.max_level >= 0 && kp.octave > w.max_level)) continue;
-            if (fabsf(kp.x - w.x) < w.r && fabsf(kp.y - w.y) < w.r) return true;
-        }
-        return false;
-    }
-    // the exact candidate prefix of query qi (>= need entries unless the true candidate set is smaller); false: the list cannot be
-    // trusted any more (exhausted by claims, or a keypoint was freed): the side needs a new round from qi
-    bool prefix(int qi, int need, int* idx, int* dist, int* n_out) const {
-        const bool skip = q[qi].flags & kQSkipOccupied;
-        if (f->N <= 0) { *n_out = 0; return true; }
-        const bool stale = qi > fresh_from || !pristine;   // claims may lie between the round and this query
-        if (skip && n_freed > 0 && stale && window_holds_a_freed_keypoint(q[qi])) return false;
-        const TopK& t = f->h_topk.p[qi];
-        int n = 0, n_dev = 0;
-        for (int k = 0; k < kTopK; k++) {
-            if (t.idx[k] < 0) break;
-            n_dev++;
-            if (skip && diff[t.idx[k]] > 0) continue;
-            idx[n] = t.idx[k]; dist[n] = t.dist[k]; n++;
-        }
-        if (n < need && n < n_dev && n_dev == kTopK && stale) return false;
-        *n_out = n;
-        return true;
-    }
-};
-}  // namespace
-
+// walks for such a frame, Frame.cc:589-655 with bRight); F.mvpMapPoints is one array of n_left + n_right entries.  The right pass
+// does not scale its radius by th (:148) and has no mbSparsified bypass (:169-171).  What couples the passes (partner claims, the
+// left ratio failure that skips the right pass) is replayed in map-point order by replay_claims_two_cameras (claim_replay.h) over
+// the two frames' device rounds.
 int msorb_search_by_projection_mps_rig(msorb_frame* left, msorb_frame* right, int M, const uint8_t* track_in_view, const uint8_t* track_in_view_r,
                                        const uint8_t* bad, const uint8_t* sparsified, const float* proj_x, const float* proj_y,
                                        const float* proj_xr, const float* proj_yr, const float* track_depth, const int* level, const int* level_r,
@@ -315,102 +176,41 @@ int msorb_search_by_projection_mps_rig(msorb_frame* left, msorb_frame* right, in
     HIPCHK(hipSetDevice(left->device));
     *nmatches = 0;
     const int NL = left->N, NR = right->N;
-    const bool bFactor = th != 1.0;
-    RigSide L, R;
-    L.f = left; R.f = right;
-    L.q.assign(M, WinQuery{}); R.q.assign(M, WinQuery{});
-    std::vector<uint8_t> live(M, 0);
+    std::vector<WinQuery> ql(M, WinQuery{}), qr(M, WinQuery{});
     for (int i = 0; i < M; i++) {
         if (!track_in_view[i] && !track_in_view_r[i]) continue;          // :50-51
         if (far_points && track_depth[i] > th_far) continue;             // :53-54
         if (bad[i]) continue;                                            // :56-57
-        live[i] = 1;
         if (track_in_view[i]) {
             if (level[i] < 0 || level[i] >= left->nlevels) { set_last_error("predicted level out of range"); return MSORB_E_INVALID; }
-            float r = (view_cos[i] > 0.998) ? 2.5 : 4.0;                 // RadiusByViewingCos, :215-221
-            if (bFactor) r *= th;
-            WinQuery& w = L.q[i];
-            w.x = proj_x[i]; w.y = proj_y[i]; w.r = r * left->scale[level[i]]; w.ur = 0.0f;
-            w.min_level = (int16_t)(level[i] - 1); w.max_level = (int16_t)level[i];
-            w.flags = kQValid | (sparsified[i] ? 0 : kQSkipOccupied);
+            ql[i] = map_point_left_query(proj_x[i], proj_y[i], 0.0f, level[i], view_cos[i], th, left->scale.data(), sparsified[i]);
         }
         if (track_in_view_r[i] && level_r[i] != -1) {                    // :144-146
             if (level_r[i] < 0 || level_r[i] >= right->nlevels) { set_last_error("predicted level (right camera) out of range"); return MSORB_E_INVALID; }
-            const float r = (view_cos_r[i] > 0.998) ? 2.5 : 4.0;         // (:147: not scaled by th)
-            WinQuery& w = R.q[i];
+            const float r = (view_cos_r[i] > 0.998) ? 2.5 : 4.0;         // RadiusByViewingCos, :215-221 (:147: not scaled by th)
+            WinQuery& w = qr[i];
             w.x = proj_xr[i]; w.y = proj_yr[i]; w.r = r * right->scale[level_r[i]]; w.ur = 0.0f;
             w.min_level = (int16_t)(level_r[i] - 1); w.max_level = (int16_t)level_r[i];
             w.flags = kQValid | kQSkipOccupied;
         }
     }
-    L.occ.assign(NL, 0); R.occ.assign(NR, 0);
+    std::vector<uint8_t> occ(NL + NR, 0);
     for (int i = 0; i < NL + NR; i++) {
         if (frame_mp[i] >= M) { set_last_error("frame_mp holds an id outside the map-point table"); return MSORB_E_INVALID; }
-        const uint8_t o = frame_mp[i] >= 0 && obs[frame_mp[i]] > 0;
-        if (i < NL) L.occ[i] = o; else R.occ[i - NL] = o;
+        occ[i] = frame_mp[i] >= 0 && obs[frame_mp[i]] > 0;
     }
     for (int i = 0; i < NL; i++) if (left_to_right[i] < -1 || left_to_right[i] >= NR) { set_last_error("left_to_right out of range"); return MSORB_E_INVALID; }
     for (int i = 0; i < NR; i++) if (right_to_left[i] < -1 || right_to_left[i] >= NL) { set_last_error("right_to_left out of range"); return MSORB_E_INVALID; }
     if (M == 0) return MSORB_OK;
     int rc;
-    if ((rc = L.prepare(M, mp_desc)) || (rc = R.prepare(M, mp_desc))) return rc;
-    int nm = 0;
-    // one side's accept rule on a candidate prefix: -1 no match, -2 the ratio test failed (:125-126 / :191-192), else the keypoint
-    auto pick = [&](const msorb_frame* f, const int* idx, const int* dist, int n) -> int {
-        if (n == 0) return -1;
-        const int bestDist = dist[0], bestIdx = idx[0];
-        const int bestLevel = f->kps[bestIdx].octave;
-        const int bestDist2 = n > 1 ? dist[1] : 256;
-        const int bestLevel2 = n > 1 ? f->kps[idx[1]].octave : -1;
-        if (bestDist > kThHigh) return -1;
-        if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) return -2;
-        return bestIdx;   // (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2 holds here)
-    };
-    bool needL = true, needR = true;
-    std::vector<uint8_t> skip_right(M, 0);   // the left pass of the point `continue`d the loop
-    for (;;) {
-        if (needL && (rc = L.round(M))) return rc;
-        if (needR && (rc = R.round(M))) return rc;
-        needL = needR = false;
-        for (int i = std::min(L.next, R.next); i < M; i++) {
-            int idx[kTopK], dist[kTopK], n = 0;
-            if (i >= L.next) {
-                if (live[i] && (L.q[i].flags & kQValid)) {
-                    if (!L.prefix(i, 2, idx, dist, &n)) { needL = true; break; }
-                    const int b = pick(left, idx, dist, n);
-                    if (b == -2) skip_right[i] = 1;
-                    if (b >= 0) {
-                        frame_mp[b] = i; nm++;
-                        L.set_occ(b, obs[i] > 0);
-                        if (left_to_right[b] != -1) {                    // :130-134
-                            frame_mp[NL + left_to_right[b]] = i; nm++;
-                            R.set_occ(left_to_right[b], obs[i] > 0);
-                        }
-                    }
-                }
-                L.next = i + 1;
-            }
-            if (i >= R.next) {
-                if (live[i] && !skip_right[i] && (R.q[i].flags & kQValid)) {
-                    if (!R.prefix(i, 2, idx, dist, &n)) { needR = true; break; }
-                    const int b = pick(right, idx, dist, n);
-                    if (b >= 0) {
-                        if (right_to_left[b] != -1) {                    // :196-200
-                            frame_mp[right_to_left[b]] = i; nm++;
-                            L.set_occ(right_to_left[b], obs[i] > 0);
-                        }
-                        frame_mp[NL + b] = i; nm++;
-                        R.set_occ(b, obs[i] > 0);
-                    }
-                }
-                R.next = i + 1;
-            }
-        }
-        if (!needL && !needR) break;
-    }
-    left->last_rounds = L.rounds; left->total_rounds += L.rounds; left->total_searches++;
-    right->last_rounds = R.rounds; right->total_rounds += R.rounds; right->total_searches++;
-    *nmatches = nm;
+    WindowRounds dl, dr;
+    if ((rc = dl.prepare(left, M, ql.data(), mp_desc, nullptr, 0)) || (rc = dr.prepare(right, M, qr.data(), mp_desc, nullptr, 0))) return rc;
+    ClaimSide L = dl.side(ql.data(), nullptr, occ.data()), R = dr.side(qr.data(), nullptr, occ.data() + NL);
+    if ((rc = replay_claims_two_cameras(L, R, M, obs, left_to_right, right_to_left, frame_mp, nnratio,
+                                        [&](int from) { return dl.round(L.occ, from); }, [&](int from) { return dr.round(R.occ, from); }, nmatches)))
+        return rc;
+    dl.account(L.rounds);
+    dr.account(R.rounds);
     return MSORB_OK;
 }
 
@@ -452,8 +252,7 @@ int search_projected(msorb_frame* f, int NL, const uint8_t* valid, const float* 
     }
     for (int i = 0; i < f->N; i++) occ[i] = cur_mp[i] >= 0 && (!obs || obs[cur_mp[i]] > 0);
     int nm = 0;
-    std::vector<int> rotHist[kHistoLength];
-    const float factor = 1.0f / kHistoLength;
+    RotationHistogram rotHist;
     auto accept = [&](int qi, const int* idx, const int* dist, int n, int* new_occ) -> int {
         if (n == 0) return -1;
         if ((float)dist[0] <= accept_dist) {  // ORBmatcher.cc:2035-2057 / :2229-2247 / :521
@@ -461,13 +260,7 @@ int search_projected(msorb_frame* f, int NL, const uint8_t* valid, const float* 
             cur_mp[bestIdx2] = ids[qi];
             nm++;
             if (push_log) push_log->push_back({qi, bestIdx2});
-            else if (check_orientation && angle) {
-                float rot = angle[qi] - f->kps[bestIdx2].angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int)std::round(rot * factor);
-                if (bin == kHistoLength) bin = 0;
-                if (bin >= 0 && bin < kHistoLength) rotHist[bin].push_back(bestIdx2);
-            }
+            else if (check_orientation && angle) rotHist.push(rotation_bin(angle[qi], f->kps[bestIdx2].angle), bestIdx2);
             *new_occ = !obs || obs[ids[qi]] > 0;
             return bestIdx2;
         }
@@ -475,14 +268,8 @@ int search_projected(msorb_frame* f, int NL, const uint8_t* valid, const float* 
     };
     const int rc = run_window_search(f, NL, q.data(), nullptr, mp_desc, occ, 1, accept);
     if (rc) return rc;
-    if (check_orientation && !push_log) {  // ORBmatcher.cc:2129-2149 / :2253-2272
-        int sizes[kHistoLength], ind[3];
-        for (int i = 0; i < kHistoLength; i++) sizes[i] = (int)rotHist[i].size();
-        msorb_three_maxima(sizes, kHistoLength, ind);
-        for (int i = 0; i < kHistoLength; i++)
-            if (i != ind[0] && i != ind[1] && i != ind[2])
-                for (int k : rotHist[i]) { cur_mp[k] = -1; nm--; }
-    }
+    if (check_orientation && !push_log)  // ORBmatcher.cc:2129-2149 / :2253-2272
+        rotHist.for_each_outside_three_maxima([&](int k) { cur_mp[k] = -1; nm--; });
     *nmatches = nm;
     return MSORB_OK;
 }
@@ -524,29 +311,9 @@ int msorb_search_by_projection_frames_rig(msorb_frame* left, msorb_frame* right,
     // `vIndices2.empty()` of the left window (:2001-2004), whatever its keypoints hold: GetFeaturesInArea's walk (Frame.cc:589-655) cut
     // short at the first keypoint found
     auto left_window_has_a_keypoint = [&](float x, float y, float r, int min_level, int max_level) {
-        const msorb_frame* f = left;
-        const int minCX = std::max(0, (int)std::floor((x - f->minX - r) * f->gridWInv));
-        if (minCX >= kGridCols) return false;
-        const int maxCX = std::min(kGridCols - 1, (int)std::ceil((x - f->minX + r) * f->gridWInv));
-        if (maxCX < 0) return false;
-        const int minCY = std::max(0, (int)std::floor((y - f->minY - r) * f->gridHInv));
-        if (minCY >= kGridRows) return false;
-        const int maxCY = std::min(kGridRows - 1, (int)std::ceil((y - f->minY + r) * f->gridHInv));
-        if (maxCY < 0) return false;
-        const bool check = (min_level > 0) || (max_level >= 0);
-        for (int ix = minCX; ix <= maxCX; ix++)
-            for (int iy = minCY; iy <= maxCY; iy++) {
-                const int c = ix * kGridRows + iy;
-                for (int j = f->cell_begin[c]; j < f->cell_begin[c + 1]; j++) {
-                    const msorb_keypoint& kp = f->kps[f->cell_idx[j]];
-                    if (check) {
-                        if (kp.octave < min_level) continue;
-                        if (max_level >= 0 && kp.octave > max_level) continue;
-                    }
-                    if (std::fabs(kp.x - x) < r && std::fabs(kp.y - y) < r) return true;
-                }
-            }
-        return false;
+        bool found = false;
+        walk_features_in_area(host_grid(left), x, y, r, min_level, max_level, [&](int) { found = true; return false; });
+        return found;
     };
     for (int i = 0; i < NLast; i++) {
         if (!valid[i]) continue;
@@ -566,26 +333,14 @@ int msorb_search_by_projection_frames_rig(msorb_frame* left, msorb_frame* right,
         return rc;
     int nm = nl + nr;
     if (check_orientation) {
-        std::vector<int> rotHist[kHistoLength];
-        const float factor = 1.0f / kHistoLength;
-        auto push = [&](int qi, float kp_angle, int entry) {
-            float rot = last_angle[qi] - kp_angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)std::round(rot * factor);
-            if (bin == kHistoLength) bin = 0;
-            if (bin >= 0 && bin < kHistoLength) rotHist[bin].push_back(entry);
-        };
+        RotationHistogram rotHist;
+        auto push = [&](int qi, float kp_angle, int entry) { rotHist.push(rotation_bin(last_angle[qi], kp_angle), entry); };
         size_t a = 0, b = 0;   // both logs are in query order: merge, the left entry of a query first
         while (a < pl.size() || b < pr.size()) {
             if (b >= pr.size() || (a < pl.size() && pl[a].first <= pr[b].first)) { push(pl[a].first, left->kps[pl[a].second].angle, pl[a].second); a++; }
             else { push(pr[b].first, right->kps[pr[b].second].angle, NL + pr[b].second); b++; }
         }
-        int sizes[kHistoLength], ind[3];
-        for (int i = 0; i < kHistoLength; i++) sizes[i] = (int)rotHist[i].size();
-        msorb_three_maxima(sizes, kHistoLength, ind);
-        for (int i = 0; i < kHistoLength; i++)
-            if (i != ind[0] && i != ind[1] && i != ind[2])
-                for (int k : rotHist[i]) { cur_mp[k] = -1; nm--; }
+        rotHist.for_each_outside_three_maxima([&](int k) { cur_mp[k] = -1; nm--; });
     }
     *nmatches = nm;
     return MSORB_OK;
@@ -893,8 +648,7 @@ int msorb_search_for_initialization(msorb_frame* f1, msorb_frame* f2, float* pre
     const TopK* const topk = f2->h_topk.p;
     // the reference's loop (:767-835): every distance that can matter is known, the sequential part is compare / select
     int nm = 0;
-    std::vector<int> rotHist[kHistoLength];
-    const float factor = 1.0f / kHistoLength;
+    RotationHistogram rotHist;
     std::vector<int> vMatchedDistance(N2, INT_MAX), vnMatches21(N2, -1);
     for (int i1 = 0; i1 < N1; i1++) {
         if (!(q[i1].flags & kQValid)) continue;
@@ -937,26 +691,14 @@ int msorb_search_for_initialization(msorb_frame* f1, msorb_frame* f2, float* pre
                 vnMatches21[bestIdx2] = i1;
                 vMatchedDistance[bestIdx2] = bestDist;
                 nm++;
-                if (check_orientation) {
-                    float rot = f1->kps[i1].angle - f2->kps[bestIdx2].angle;
-                    if (rot < 0.0) rot += 360.0f;
-                    int bin = (int)std::round(rot * factor);
-                    if (bin == kHistoLength) bin = 0;
-                    if (bin >= 0 && bin < kHistoLength) rotHist[bin].push_back(i1);
-                }
+                if (check_orientation) rotHist.push(rotation_bin(f1->kps[i1].angle, f2->kps[bestIdx2].angle), i1);
             }
         }
     }
-    if (check_orientation) {  // :837-861
-        int sizes[kHistoLength], ind[3];
-        for (int i = 0; i < kHistoLength; i++) sizes[i] = (int)rotHist[i].size();
-        msorb_three_maxima(sizes, kHistoLength, ind);
-        for (int i = 0; i < kHistoLength; i++) {
-            if (i == ind[0] || i == ind[1] || i == ind[2]) continue;
-            for (int idx1 : rotHist[i])
-                if (matches12[idx1] >= 0) { matches12[idx1] = -1; nm--; }
-        }
-    }
+    if (check_orientation)  // :837-861
+        rotHist.for_each_outside_three_maxima([&](int idx1) {
+            if (matches12[idx1] >= 0) { matches12[idx1] = -1; nm--; }
+        });
     for (int i1 = 0; i1 < N1; i1++)  // :864-867
         if (matches12[i1] >= 0) { prev_xy[2 * i1] = f2->kps[matches12[i1]].x; prev_xy[2 * i1 + 1] = f2->kps[matches12[i1]].y; }
     *nmatches = nm;

@@ -571,21 +571,12 @@ int replay_local_points(msorb_frame* f, const LocalPointsCall& c, std::vector<ui
     int nm = 0;
     const float nnratio = c.nnratio;
     auto accept = [&](int qi, const int* idx, const int* dist, int n, int* new_occ) -> int {
-        if (n == 0) return -1;
-        const int bestDist = dist[0], bestIdx = idx[0];
-        const int bestLevel = f->kps[bestIdx].octave;
-        const int bestDist2 = n > 1 ? dist[1] : 256;
-        const int bestLevel2 = n > 1 ? f->kps[idx[1]].octave : -1;
-        if (bestDist <= kThHigh) {  // ORBmatcher.cc:122-141
-            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) return -1;
-            if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                frame_mp[bestIdx] = qi;
-                nm++;
-                *new_occ = c.obs[qi] > 0;
-                return bestIdx;
-            }
-        }
-        return -1;
+        const int bestIdx = accept_best_of_two(f->kps.data(), idx, dist, n, nnratio);
+        if (bestIdx < 0) return -1;
+        frame_mp[bestIdx] = qi;
+        nm++;
+        *new_occ = c.obs[qi] > 0;
+        return bestIdx;
     };
     // resync rounds (rare) read the query descriptors from f->d_qdesc: alias the uploaded block
     const int rc = run_window_search(f, c.m, nullptr, flags.data(), nullptr, occ, 2, accept, true, rounds, T.d_in.p + L.o_desc,
@@ -687,21 +678,14 @@ int replay_last_frame(msorb_frame* f, const LastFrameCall& c, std::vector<uint8_
     std::vector<uint8_t> flags(n);
     for (size_t i = 0; i < n; i++) flags[i] = valid[i] ? (uint8_t)(kQValid | kQSkipOccupied) : 0;
     int nm = 0;
-    std::vector<int> rotHist[kHistoLength];
-    const float factor = 1.0f / kHistoLength;
+    RotationHistogram rotHist;
     const int* obs = c.obs;
     auto accept = [&](int qi, const int* idx, const int* dist, int nc, int* new_occ) -> int {
         if (nc == 0 || dist[0] > kThHigh) return -1;   // :2035
         const int bestIdx2 = idx[0];
         cur_mp[bestIdx2] = qi;
         nm++;
-        if (c.check_orientation) {
-            float rot = T.last_angle[qi] - f->kps[bestIdx2].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)std::round(rot * factor);
-            if (bin == kHistoLength) bin = 0;
-            if (bin >= 0 && bin < kHistoLength) rotHist[bin].push_back(bestIdx2);
-        }
+        if (c.check_orientation) rotHist.push(rotation_bin(T.last_angle[qi], f->kps[bestIdx2].angle), bestIdx2);
         *new_occ = obs[qi] > 0;
         return bestIdx2;
     };
@@ -709,14 +693,7 @@ int replay_last_frame(msorb_frame* f, const LastFrameCall& c, std::vector<uint8_
     const int rc = run_window_search(f, T.last_n, nullptr, flags.data(), nullptr, occ, 1, accept, true, nullptr, T.d_last.p + L.o_desc,
                                      window_lanes_for(c.th * mid, f->gridWInv, f->gridHInv));
     if (rc) return rc;
-    if (c.check_orientation) {
-        int sizes[kHistoLength], ind[3];
-        for (int i = 0; i < kHistoLength; i++) sizes[i] = (int)rotHist[i].size();
-        msorb_three_maxima(sizes, kHistoLength, ind);
-        for (int i = 0; i < kHistoLength; i++)
-            if (i != ind[0] && i != ind[1] && i != ind[2])
-                for (int k : rotHist[i]) { cur_mp[k] = -1; nm--; }
-    }
+    if (c.check_orientation) rotHist.for_each_outside_three_maxima([&](int k) { cur_mp[k] = -1; nm--; });
     *nmatches = nm;
     return MSORB_OK;
 }
