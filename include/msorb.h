@@ -287,6 +287,11 @@ int msorb_debug_std_sort(int device, const uint32_t* keys, int n, int frame_form
 int msorb_debug_fast_thread_table(int rows, int cols, int nfeatures, float scale_factor, int nlevels, int threads,
                                   int32_t* cells, int cell_capacity, int* n_cells,
                                   uint32_t* records, int record_capacity, int* n_records, int* n_classes);
+/* The cosine and sine describe_kernel steers the rBRIEF pattern with (ORBextractor.cc:112: a = cos(angle * factorPI), b = sin(..)),
+ * ALONE, on n <= 2^26 explicit angles in degrees: the same device function the kernel calls, so every bit of the device build of the
+ * glibc sinf / cosf restatement can be held to the installed libm (inside the extractor a and b are seen only through the rounded
+ * tap positions).  Appended to ABI 6002: MSORB_ABI_VERSION is unchanged, a caller that needs the entry asks the loader for it. */
+int msorb_debug_cos_sin(int device, const float* angles_deg, int n, float* cos_out, float* sin_out);
 /* Host-only: DistributeOctTree (ORBextractor.cc:555-779) on explicit candidates; writes the indices of
  * the kept candidates in result order.  Needs no GPU. */
 int msorb_distribute_quadtree(const uint16_t* xs, const uint16_t* ys, const uint16_t* scores, int n, int min_x,

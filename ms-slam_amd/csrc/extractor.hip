@@ -1812,6 +1812,14 @@ int msorb_debug_std_sort(int device, const uint32_t* keys, int n, int frame_form
     return rc;
 }
 
+int msorb_debug_cos_sin(int device, const float* angles_deg, int n, float* cos_out, float* sin_out) {
+    if (n < 0 || (n > 0 && (!angles_deg || !cos_out || !sin_out))) return MSORB_E_INVALID;
+    HIPCHK(hipSetDevice(device));
+    const int rc = launch_debug_cos_sin(angles_deg, n, cos_out, sin_out);
+    if (rc == MSORB_E_HIP) set_last_error(std::string("msorb_debug_cos_sin: ") + hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
 int msorb_debug_patch_tables(msorb_extractor* h, int8_t* pattern, int8_t* umax) {
     if (!h || !pattern || !umax) return MSORB_E_INVALID;
     HIPCHK(hipSetDevice(h->device));

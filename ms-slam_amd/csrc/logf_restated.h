@@ -3,6 +3,8 @@
 // to on the reference's platform.  Restated in double exactly as published (16-entry table, degree-3 polynomial),
 // fp contraction off.  Checked against the installed glibc over EVERY positive finite float (2 139 095 039 values,
 // 0 mismatches; tests/logf_check.cc, strided in CI, exhaustive with MSORB_EXHAUSTIVE=1).
+// The DEVICE build of this header is held to the installed glibc by tests/test_device_logf_gpu.py, which reads every bit of the
+// result out through the predicted level of msorb_is_in_frustum.
 #pragma once
 #include <stdint.h>
 #include <string.h>

@@ -1143,6 +1143,41 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x, int fma) {
     return a;
 }
 
+// a = cos, b = sin of a keypoint's angle (ORBextractor.cc:112: angle * factorPI in float, then cos / sin of the float): glibc's
+// cosf / sinf restated (sincosf_restated.h).  The one place the expression is written: describe_kernel's phase V and the test hook
+// below call it, so the hook observes what the kernel computes.
+__device__ __forceinline__ void angle_cos_sin(float angle_deg, float* a, float* b) {
+    const float factor_pi = (float)(3.1415926535897932384626433832795 / 180.0);
+    glibc_sincosf<true>(__fmul_rn(angle_deg, factor_pi), b, a);
+}
+// Test hook (msorb_debug_cos_sin): angle_cos_sin ALONE on explicit angles; every bit of the result must be libm's (tests/test_device_sincosf_gpu.py).
+__global__ __launch_bounds__(256) void debug_cos_sin_kernel(const float* __restrict__ angles_deg, int n, float* __restrict__ cos_out,
+                                                            float* __restrict__ sin_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float a, b;
+    angle_cos_sin(angles_deg[i], &a, &b);
+    cos_out[i] = a;
+    sin_out[i] = b;
+}
+int launch_debug_cos_sin(const float* h_angles_deg, int n, float* h_cos, float* h_sin) {
+    if (n < 0 || n > (1 << 26)) return MSORB_E_INVALID;
+    if (n == 0) return MSORB_OK;
+    float* d = nullptr;
+    const size_t bytes = (size_t)n * sizeof(float);
+    hipError_t e = hipMalloc((void**)&d, 3 * bytes);
+    if (e != hipSuccess) return MSORB_E_HIP;
+    e = hipMemcpy(d, h_angles_deg, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(debug_cos_sin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d, n, d + n, d + 2 * (size_t)n);
+        e = hipDeviceSynchronize();
+    }
+    if (e == hipSuccess) e = hipMemcpy(h_cos, d + n, bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_sin, d + 2 * (size_t)n, bytes, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return e == hipSuccess ? MSORB_OK : MSORB_E_HIP;
+}
+
 // Sum over the 64 lanes with DPP adds only (no LDS crossbar): xor-butterfly inside each row of 16 lanes, then the row
 // totals are chained through lanes 15 / 31 into row 3; lane 63 holds the total, returned as a scalar.
 __device__ __forceinline__ int wave_sum_dpp(int v) {
@@ -1306,7 +1341,6 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
         patx[w] = f32x2{(float)(int8_t)(pw & 255u), (float)(int8_t)((pw >> 16) & 255u)};
         paty[w] = f32x2{(float)(int8_t)((pw >> 8) & 255u), (float)(int8_t)(pw >> 24)};
     }
-    const float factor_pi = (float)(3.1415926535897932384626433832795 / 180.0);
 
     // The wave's four selection records, fetched together and moved to scalar registers: everything derived from them (level
     // view, row pointers, strides, the LDS-DMA bases) is SALU work, and no keypoint's addresses wait for an earlier keypoint.
@@ -1408,7 +1442,7 @@ __global__ __launch_bounds__(64 * kDescWaves) __attribute__((amdgpu_waves_per_eu
         const int m10v = mom[wv][q] + mom[wv][q + 4], m01v = mom[wv][q + 8] + mom[wv][q + 12];
         const float angle_v = fast_atan2_deg((float)m01v, (float)m10v, atan2_fma);
         float a_v, b_v;
-        glibc_sincosf<true>(__fmul_rn(angle_v, factor_pi), &b_v, &a_v);  // a = cos, b = sin (ORBextractor.cc:112)
+        angle_cos_sin(angle_v, &a_v, &b_v);  // a = cos, b = sin (ORBextractor.cc:112)
         if (lane < kDescWaves * kKpPerWave) *reinterpret_cast<float4*>(tri[lane]) = float4{angle_v, a_v, b_v, 0.f};
     }
     __syncthreads();

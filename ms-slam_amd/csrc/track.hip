@@ -75,11 +75,12 @@ __device__ __forceinline__ void last_frame_point(const LastFrameArgs& A, const i
         // :1973 `const float invzc = 1.0/x3Dc(2)`: the double quotient rounded to float IS the float quotient (53 >= 2*24 + 2)
         const float invzc = __fdiv_rn(1.0f, zc);
         if (!(invzc < 0.0f)) {
-            u = __fadd_rn(__fdiv_rn(__fmul_rn(A.fx, xc), zc), A.cx);   // Pinhole::project, Pinhole.cpp:43-49
-            v = __fadd_rn(__fdiv_rn(__fmul_rn(A.fy, yc), zc), A.cy);
-            if (!(u < A.min_x || u > A.max_x) && !(v < A.min_y || v > A.max_y)) {   // :1980-1983
+            const float pu = __fadd_rn(__fdiv_rn(__fmul_rn(A.fx, xc), zc), A.cx);   // Pinhole::project, Pinhole.cpp:43-49
+            const float pv = __fadd_rn(__fdiv_rn(__fmul_rn(A.fy, yc), zc), A.cy);
+            if (!(pu < A.min_x || pu > A.max_x) && !(pv < A.min_y || pv > A.max_y)) {   // :1980-1983
                 const int oct = A.octave[i];
                 ok = 1;
+                u = pu; v = pv;   // (a point outside the image reports zeros, like every other rejected point)
                 ur = __fmaf_rn(-A.mbf, invzc, u);                                  // :2019
                 w.x = u; w.y = v; w.ur = ur;
                 w.r = __fmul_rn(A.th, A.scale[oct]);                               // :1989

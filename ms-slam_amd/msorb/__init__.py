@@ -377,6 +377,19 @@ def debug_std_sort(keys, frame_form=True, device=0, lane_sort=True, timing=False
     return (order, out, us.value) if timing else (order, out)
 
 
+EXPORTS = EXPORTS + ("msorb_debug_cos_sin",)
+
+
+def debug_cos_sin(angles_deg, device=0):
+    """msorb_debug_cos_sin: (a = cos, b = sin) of float32 angles in degrees as describe_kernel computes them (float32 each)."""
+    ang = np.ascontiguousarray(angles_deg, np.float32).ravel()
+    a, b = np.zeros(len(ang), np.float32), np.zeros(len(ang), np.float32)
+    L = lib()
+    L.msorb_debug_cos_sin.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    _check(L.msorb_debug_cos_sin(device, _np_ptr(ang), len(ang), _np_ptr(a), _np_ptr(b)), "msorb_debug_cos_sin")
+    return a, b
+
+
 def keypoints_from_device(d_kps, counts):
     """torch uint8 [n, cap, 28] -> list of numpy KP_DTYPE arrays."""
     host = d_kps.cpu().numpy()

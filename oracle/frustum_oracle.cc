@@ -75,6 +75,12 @@ extern "C" void orc_is_in_frustum(const orc_frustum* F, float viewingCosLimit, i
     }
 }
 
+// the platform's logf over an array: what std::log(ratio) above resolves to (tests/boundary_cases.py builds the cases that read the
+// device's logf out through the predicted level from it)
+extern "C" void orc_logf_n(const float* x, long long n, float* out) {
+    for (long long i = 0; i < n; i++) out[i] = std::log(x[i]);
+}
+
 // The per-keypoint projection of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono)
 // (/root/reference/src/ORBmatcher.cc:1951-1990, rectified / Nleft == -1): x3Dc = Tcw * x3Dw, invzc, Pinhole::project, the
 // image-bounds rejections, ur = uv(0) - mbf*invzc (:2019).  Tcw * x3Dw is Sophus' SE3 action,

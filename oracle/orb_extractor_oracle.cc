@@ -552,6 +552,13 @@ void orc_cos_sin(float angle_deg, float* a, float* b) {
     const float r = angle_deg * orc::kFactorPI;
     *a = cosf(r); *b = sinf(r);
 }
+// the same over an array (tests/test_device_sincosf_gpu.py: millions of angles, one call)
+void orc_cos_sin_n(const float* angles_deg, long long n, float* a, float* b) {
+    for (long long i = 0; i < n; i++) {
+        const float r = angles_deg[i] * orc::kFactorPI;
+        a[i] = cosf(r); b[i] = sinf(r);
+    }
+}
 // libstdc++'s std::sort itself on (key, input position) items compared by key alone — the shape of ORBextractor.cc:700's
 // std::sort(vPrevSizeAndPointerToNode, compareNodes): unstable, the order of equal keys is the algorithm's.  order[i] = input
 // position of the item that ends at position i.  (tests/test_quadtree_sort_gpu.py: the device's restatement against this.)

@@ -219,6 +219,17 @@ def cos_sin(angle_deg):
     return a.value, b.value
 
 
+def cos_sin_n(angles_deg):
+    """cos_sin over an array of float32 degrees -> (a = cosf, b = sinf) of float(angle * factorPI), float32 each."""
+    ang = np.ascontiguousarray(angles_deg, np.float32).ravel()
+    a, b = np.empty(len(ang), np.float32), np.empty(len(ang), np.float32)
+    L = lib()
+    L.orc_cos_sin_n.restype = None
+    L.orc_cos_sin_n.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.orc_cos_sin_n(_ptr(ang), len(ang), _ptr(a), _ptr(b))
+    return a, b
+
+
 _RIG_FIELDS = (("track_in_view", np.uint8), ("track_in_view_r", np.uint8), ("bad", np.uint8), ("sparsified", np.uint8), ("proj_x", np.float32),
                ("proj_y", np.float32), ("proj_xr", np.float32), ("proj_yr", np.float32), ("track_depth", np.float32), ("level", np.int32),
                ("level_r", np.int32), ("view_cos", np.float32), ("view_cos_r", np.float32), ("desc", np.uint8), ("obs", np.int32))
@@ -561,6 +572,17 @@ def is_in_frustum(frustum, pos_w, normal, max_distance, min_distance, viewing_co
                          _ptr(px), _ptr(py), _ptr(pxr), _ptr(dep), _ptr(lvl), _ptr(vc))
     return dict(track_in_view=inv[:n], proj_x=px[:n], proj_y=py[:n], proj_xr=pxr[:n], track_depth=dep[:n], level=lvl[:n],
                 view_cos=vc[:n])
+
+
+def logf_n(x):
+    """the installed libm's logf over a float32 array (oracle/frustum_oracle.cc orc_logf_n)"""
+    Lb = lib()
+    Lb.orc_logf_n.argtypes = [C.c_void_p, C.c_longlong, C.c_void_p]
+    Lb.orc_logf_n.restype = None
+    xx = _c(x, np.float32).ravel()
+    out = np.empty(len(xx), np.float32)
+    Lb.orc_logf_n(_ptr(xx), len(xx), _ptr(out))
+    return out
 
 
 class MotionModel(C.Structure):
