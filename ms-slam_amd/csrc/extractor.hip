@@ -1,11 +1,7 @@
 // libmsorb.so — extractor handle, host orchestration and the C ABI of include/msorb.h.
 //
-// Per call (one stream, n_images same-sized frames):
-//   pyramid (nlevels-1 launches) -> FAST cells -> candidate compaction -> [copy stream: D2H candidates]
-//   -> Gaussian blur (overlaps the host stage) -> host quadtree selection (thread pool, one task per image)
-//   -> H2D selection -> IC-angle + rBRIEF -> keypoints/descriptors in device memory.
-// The quadtree (DistributeOctTree, ORBextractor.cc:555-779) is serial and order-defining; it stays on the
-// host (orb_host.cc) in this version.
+// Per call (n_images same-sized frames): run_pipeline() issues pyramid -> (blur) -> FAST cells -> candidate compaction -> selection
+// -> (blur) -> IC-angle + rBRIEF -> counts, once per sub-batch; the entry points below build a PipelineCall around it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "frame_io.h"
 #include "hip_host.h"
 #include "host_admission.h"
 #include "orb_device.h"
@@ -117,7 +114,7 @@ constexpr int kMaxGroups = 4;
 struct StreamGroup {  // one sub-batch pipeline: main stream (group 0 uses the handle's own), sync + timing events
     hipStream_t s = nullptr;
     bool own_stream = false;
-    hipEvent_t ev_pyr = nullptr, ev_blur = nullptr, ev_fast = nullptr;
+    hipEvent_t ev_pyr = nullptr, ev_blur = nullptr;
     hipEvent_t pe[10] = {};
     bool ready = false;
 };
@@ -130,21 +127,17 @@ struct msorb_extractor {
     OrbParams P;
     Semantics sem;   // msorb_extractor_set_semantics: variants of the [OpenCV-recall] primitives (defaults = SURVEY.md Appendix A)
     hipStream_t stream = nullptr, copy_stream = nullptr;
-    // Environment switches, read ONCE when the handle is created (README.md lists them): MSORB_SERIAL_PIPELINE (one stream,
-    // host-synchronised stages: debugging), MSORB_QUADTREE=host (DistributeOctTree on the host twin), MSORB_HOST_THREADS (its
+    // Environment switches, read ONCE when the handle is created (README.md lists them): MSORB_SERIAL_PIPELINE (one sub-batch,
+    // every stage on the main stream, no fused launches: debugging), MSORB_QUADTREE=host (DistributeOctTree on the host twin), MSORB_HOST_THREADS (its
     // worker threads), MSORB_SPLIT_NO_PEER (test hook: the two-device gather staged through the host), MSORB_FORCE_PEER_PYRAMID
     // (test hook: msorb_stereo_matches pulls the right pyramid over the peer path even on one device)
-    const StereoRowJob* row_job = nullptr;   // set by the stereo-frame calls around run_pipeline: the right eye's band records leave the layout launch
     struct Knobs { bool serial_pipeline = false, quadtree_host = false, quadtree_global = false, split_no_peer = false, force_peer_pyramid = false, frame_compact = true; int host_threads = 0, frame_fuse = 2; } knobs;
     int lds_per_block = 64 * 1024;   // hipDeviceAttributeMaxSharedMemoryPerBlock of the handle's device
-    static constexpr bool capturing = false;   // (no graph capture: plain launches; see tools/experiments/README.md)
-    bool defer_sync = false;     // enqueue only, the caller appends more work and synchronises (msorb_extract[_stereo])
-    bool last_prof = false;      // the stage events of the last run_pipeline_groups() call were recorded
+    bool last_prof = false;      // the stage events of the last run_pipeline() call were recorded
     int pending_batch = 0;       // images of a batch enqueued by msorb_extract_batch_submit and not yet waited for
-    bool skip_count_copies = false;  // with defer_sync: the caller fetches the counts from the device itself
     DevBuf<int> d_st_sad, d_st_rows, d_st_list;  // stereo association scratch of msorb_extract_stereo
     DevBuf<uint8_t> d_st_block, d_st_img;        // its output block and its two level-0 planes
-    DevBuf<uint8_t> d_out1;                      // msorb_extract: keypoints + descriptors of one frame as one block
+    DevBuf<uint8_t> d_out1;                      // msorb_extract (and the right eye of the split call): keypoints + descriptors of one frame as one block
     DevBuf<uint8_t> d_gather_pyr;                // msorb_extract_stereo_split: the right eye's pyramid, gathered onto this (left) device
     DevBuf<int> d_gather_cnt;                    // ... and its keypoint count
     hipEvent_t ev_split = nullptr;               // ... recorded on the right handle's stream after the gather copies
@@ -153,14 +146,11 @@ struct msorb_extractor {
     // for KITTI) rides PCIe while FAST / quadtree / describe run; level 0 is the staged input image itself
     bool host_pyramid = false;
     hipStream_t pyr_stream = nullptr;
-    hipEvent_t ev_pyr_done = nullptr;
     bool h_pyr_async = false;  // h_pyr holds levels 1.. of the last msorb_extract call, level 0 = h_img_pin
     const uint8_t* pair_l0[2] = {nullptr, nullptr};   // host level 0 of the two images of the last msorb_extract_pair call
-    int pair_request = 0;      // one-shot: set by msorb_extract_pair around its run_pipeline call
     int pair_pyramids = 0;     // msorb_extract_pair: host pyramids of this many images are wanted / were copied (image i at h_pyr + i * pyramid_bytes)
     unsigned long long buffers_epoch = 0;  // bumped whenever a device / pinned buffer may have moved
-    hipEvent_t ev_compact = nullptr, ev_pyramid = nullptr, ev_blur = nullptr;
-    hipEvent_t pe[10] = {};
+    hipEvent_t ev_compact = nullptr;   // behind the compaction fetch_candidates() waits for (host selection)
     bool profiling = false;
     float stage_ms[MSORB_N_STAGES] = {};
 
@@ -170,7 +160,7 @@ struct msorb_extractor {
     LevelScale scales;
 
     // device state
-    DevBuf<uint8_t> d_pyr, d_blur, d_desc1;
+    DevBuf<uint8_t> d_pyr, d_blur;
     DevBuf<ResizeTap> d_taps;
     TowerPlan tower;           // the pyramid of a frame or two as one launch (orb_device.h); ntx == 0: not available for this geometry
     std::vector<size_t> tap_x_off, tap_y_off;
@@ -179,7 +169,6 @@ struct msorb_extractor {
     DevBuf<int> d_level_cell_begin, d_cell_count, d_cell_off, d_level_count, d_img_total, d_img_base, d_sel_count;
     DevBuf<Cand16> d_slots, d_compact;
     DevBuf<SelRec> d_sel;
-    DevBuf<msorb_keypoint> d_kps1;
     DevBuf<uint16_t> d_label;
     DevBuf<int> d_sel_pt, d_sel_n, d_mono;
     QtLevels qt{};
@@ -207,20 +196,19 @@ struct msorb_extractor {
     int sel_stride = 0;
 
     std::unique_ptr<Pool> pool;
-    std::vector<std::vector<int>> kept_scratch;  // per worker-task scratch is allocated inside tasks
 };
 
 namespace {
 
+// per-frame transfer between a pinned block and device memory on stream s (orb_kernels.hip small_copy)
+int frame_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    HIPCHK(small_copy(dst, src, bytes, kind, s));
+    return MSORB_OK;
+}
 // Upper bound of the keypoints one image returns.  DistributeOctTree overshoots a level's quota by at most 3 (the split that
 // reaches it), but its FIRST pass divides every initial column unconditionally (ORBextractor.cc:610-681 runs before any quota
 // check): a level returns up to max(quota + 3, 4 * nIni) keypoints, nIni = round(width / height) <= 4 for every camera the
 // reference is configured for.  16 more rows per level cover that whatever the quota (tiny nfeatures on wide images).
-// per-frame transfer between a pinned block and device memory on stream s (orb_kernels.hip small_copy)
-int frame_copy(msorb_extractor*, void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    HIPCHK(small_copy(dst, src, bytes, kind, s));
-    return MSORB_OK;
-}
 int capacity_of(const msorb_extractor* h) { return h->P.nfeatures + (3 + 16) * h->P.nlevels; }
 
 // ---- the process's host-memory admission table (host_admission.h) on the HIP runtime
@@ -285,6 +273,10 @@ HostAdmission& admission() {
     return *t;
 }
 
+void copy_rows(uint8_t* dst, size_t dst_pitch, const uint8_t* src, size_t stride, int rows, int cols) {
+    for (int y = 0; y < rows; y++) memcpy(dst + (size_t)y * dst_pitch, src + (size_t)y * stride, cols);
+}
+
 // The level-0 sources of one per-frame call.  admit() looks an image's byte range up in the admission table and, when it lies
 // wholly inside one entry, holds that entry and records the device-visible address of the image (hipHostGetDevicePointer of the
 // entry's base on the current device, asked once per entry and device and kept IN the entry, plus the image's offset).  The holds
@@ -295,6 +287,7 @@ struct DirectInputs {
     HostAdmission::Entry* held[2] = {nullptr, nullptr};
     hipStream_t launched[2] = {nullptr, nullptr};
     int n_launched = 0;
+    struct { uint8_t* dst = nullptr; const uint8_t* image = nullptr; size_t stride = 0; } late[2];   // host level 0 still to be made (late_level0)
     bool admit(const msorb_extractor* h, int i, const uint8_t* image, int rows, int cols, size_t stride) {
         if (!h->input_direct) return false;
         HostAdmission::Entry* e = admission().hold(image, (size_t)(rows - 1) * stride + (size_t)cols);
@@ -319,6 +312,54 @@ struct DirectInputs {
         launch_upload_level0(src, n_images, dst, dst_image_stride, dst_pitch, rows, cols, s);
         if (n_launched < 2) launched[n_launched++] = s;
     }
+    // Level 0 of the call's n (1 or 2) images, from the caller's memory to dst (+ i * dst_image_stride) on stream s.  An image in admitted
+    // host memory (msorb_host_alloc / msorb_host_register) is read where it lies by the upload kernel; one whose `staged` bit is set lies in
+    // pinned memory at the library's pitch already (msorb_stage_image); everything else is copied into plane dst_plane[i] of h_img_pin first
+    // (a plain hipMemcpy from pageable memory makes the driver pin / unpin per call, which costs more than the whole kernel chain).
+    // With at least one image read in place ONE launch uploads them all, the others from wherever they lie in pinned memory; otherwise
+    // each image goes up by its own copy, issued before the next image is staged (it rides PCIe meanwhile): the copy kernel, or
+    // hipMemcpyAsync where the caller says so.  host_l0[i]: the image's host level 0, nullptr while it has none (read in place:
+    // late_level0() makes it).
+    int level0(msorb_extractor* h, int n, const uint8_t* const* image, const size_t* stride, int staged, const int* dst_plane, int rows, int cols,
+               uint8_t* dst, size_t dst_image_stride, bool by_memcpy, hipStream_t s, const uint8_t** host_l0) {
+        const int pitch = h->G.lv[0].pitch;
+        const size_t plane = (size_t)pitch * rows;
+        bool any_direct = false;
+        for (int i = 0; i < n; i++) any_direct = (!(staged & (1 << i)) && admit(h, i, image[i], rows, cols, stride[i])) || any_direct;
+        for (int i = 0; i < n; i++) {
+            uint8_t* const d = h->h_img_pin.p + (size_t)dst_plane[i] * plane;
+            if (staged & (1 << i)) {
+                host_l0[i] = image[i];
+            } else if (direct(i)) {
+                host_l0[i] = nullptr;
+                late[i] = {d, image[i], stride[i]};
+                h->in_stats.images_direct++;
+            } else {
+                copy_rows(d, pitch, image[i], stride[i], rows, cols);
+                h->in_stats.images_staged++;
+                h->in_stats.bytes_staged += (uint64_t)rows * cols;
+                host_l0[i] = d;
+            }
+            if (any_direct) {
+                if (!direct(i)) src[i] = Level0Src{host_l0[i], (size_t)pitch};
+                continue;
+            }
+            h->in_stats.upload_launches++;
+            if (by_memcpy) HIPCHK(hipMemcpyAsync(dst + i * dst_image_stride, host_l0[i], plane, hipMemcpyHostToDevice, s));
+            else HIPCHK(small_copy(dst + i * dst_image_stride, host_l0[i], plane, hipMemcpyHostToDevice, s));
+        }
+        if (any_direct) {
+            h->in_stats.upload_launches++;
+            upload(n, dst, dst_image_stride, pitch, rows, cols, s);
+        }
+        return MSORB_OK;
+    }
+    // Host level 0 of the images read in place (msorb_pyramid_level hands out the handle's plane, never the caller's pointer): the copy
+    // the staged path makes in front of the upload, made while the host would wait for the device anyway.
+    void late_level0(const msorb_extractor* h, int rows, int cols, const uint8_t** host_l0) {
+        for (int i = 0; i < 2; i++)
+            if (late[i].dst) { copy_rows(late[i].dst, h->G.lv[0].pitch, late[i].image, late[i].stride, rows, cols); host_l0[i] = late[i].dst; }
+    }
     void done() {   // the streams have been synchronised
         n_launched = 0;
         for (auto& e : held) { HostAdmission::release(e); e = nullptr; }
@@ -328,9 +369,6 @@ struct DirectInputs {
         done();
     }
 };
-void copy_rows(uint8_t* dst, size_t dst_pitch, const uint8_t* src, size_t stride, int rows, int cols) {
-    for (int y = 0; y < rows; y++) memcpy(dst + (size_t)y * dst_pitch, src + (size_t)y * stride, cols);
-}
 
 int ensure_geometry(msorb_extractor* h, int rows, int cols) {
     if (h->geom_valid && h->G.rows == rows && h->G.cols == cols) return MSORB_OK;
@@ -526,14 +564,49 @@ int ensure_group(msorb_extractor* h, int gi) {
     else { HIPCHK(hipStreamCreateWithFlags(&G.s, hipStreamNonBlocking)); G.own_stream = true; }
     HIPCHK(hipEventCreateWithFlags(&G.ev_pyr, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&G.ev_blur, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&G.ev_fast, hipEventDisableTiming));
     for (auto& e : G.pe) HIPCHK(hipEventCreate(&e));
     G.ready = true;
     return MSORB_OK;
 }
 
-// End of a run_pipeline_groups() call: waits for the sub-batch streams, hands the counts out, folds the stage events.
-int finish_groups(msorb_extractor* h, int n_images, int* h_counts, int* h_mono) {
+// What the entries that enqueue behind the pipeline need: the selection on the device and sub-batches free to run side by side.
+bool device_pipeline(const msorb_extractor* h) { return h->device_quadtree && !h->knobs.serial_pipeline; }
+// the blur has a stream (or a fused launch) of its own; otherwise it sits on the main stream between the pyramid and FAST
+bool blur_off_main(const msorb_extractor* h) { return h->overlap_blur && !h->knobs.serial_pipeline; }
+
+// What one call asks of run_pipeline(); built by the entry point, read-only for the pipeline.
+struct PipelineCall {
+    int lap0 = 0, lap1 = 0;
+    int capacity = 0;                     // rows per image of d_kps / d_desc
+    msorb_keypoint* d_kps = nullptr;
+    uint8_t* d_desc = nullptr;
+    int* h_counts = nullptr;              // handed out by the call unless defer_sync
+    int* h_mono = nullptr;
+    const StereoRowJob* row_job = nullptr;   // stereo frame: the right eye's band records leave the layout launch
+    bool defer_sync = false;              // enqueue only: the caller appends more work and synchronises
+    bool skip_count_copies = false;       // with defer_sync: the caller fetches the counts from the device itself
+    int pair_pyramids = 0;                // msorb_extract_pair: host pyramids of this many images are wanted
+};
+
+// Levels 1.. of images [0, n) of the handle's pyramid leave for pinned memory (h_pyr, image i at i * pyramid_bytes) on a stream of
+// their own, behind the event `after` (nullptr: behind nothing, the pyramid is complete).
+int host_pyramid_copies(msorb_extractor* h, int n, hipEvent_t after) {
+    const FrameGeom& g = h->G;
+    int rc;
+    if ((rc = h->h_pyr.ensure((size_t)n * g.pyramid_bytes))) return rc;
+    if (!h->pyr_stream) HIPCHK(hipStreamCreateWithFlags(&h->pyr_stream, hipStreamNonBlocking));
+    if (after) HIPCHK(hipStreamWaitEvent(h->pyr_stream, after, 0));
+    if (g.nlevels > 1)
+        for (int i = 0; i < n; i++)
+            HIPCHK(hipMemcpyAsync(h->h_pyr.p + (size_t)i * g.pyramid_bytes + g.lv[1].plane_off, h->d_pyr.p + (size_t)i * g.pyramid_bytes + g.lv[1].plane_off,
+                                  g.pyramid_bytes - g.lv[1].plane_off, hipMemcpyDeviceToHost, h->pyr_stream));
+    h->h_pyr_async = true;
+    return MSORB_OK;
+}
+
+// End of a run_pipeline() call: waits for the sub-batch streams, hands the counts out, folds the stage events.
+// host_select_ms >= 0: the selection ran on the host, its stage time is this wall-clock interval.
+int finish_groups(msorb_extractor* h, int n_images, int* h_counts, int* h_mono, float host_select_ms = -1.f) {
     const int ng = h->last_groups;
     for (int gi = 0; gi < ng; gi++) HIPCHK(hipStreamSynchronize(h->grp[gi].s));
     HIPCHK(hipGetLastError());
@@ -544,7 +617,7 @@ int finish_groups(msorb_extractor* h, int n_images, int* h_counts, int* h_mono) 
     }
     if (h->last_prof) {  // stage time = sum over the sub-batches of the stage's HIP-event interval on its own stream
         // (with the blur on the main stream its interval sits between pyramid and FAST: FAST = 8 -> 2)
-        const int fast_from = h->overlap_blur ? 1 : 8;
+        const int fast_from = blur_off_main(h) ? 1 : 8;
         const int map[6][3] = {{MSORB_STAGE_PYRAMID, 0, 1}, {MSORB_STAGE_FAST, fast_from, 2}, {MSORB_STAGE_COMPACT, 2, 3},
                                {MSORB_STAGE_BLUR, 7, 8}, {MSORB_STAGE_SELECT, 3, 5}, {MSORB_STAGE_DESCRIBE, 5, 6}};
         for (auto& m : map) h->stage_ms[m[0]] = 0;
@@ -554,34 +627,96 @@ int finish_groups(msorb_extractor* h, int n_images, int* h_counts, int* h_mono) 
                 HIPCHK(hipEventElapsedTime(&ms, h->grp[gi].pe[m[1]], h->grp[gi].pe[m[2]]));
                 h->stage_ms[m[0]] += ms;
             }
+        if (host_select_ms >= 0) h->stage_ms[MSORB_STAGE_SELECT] = host_select_ms;
     }
     return MSORB_OK;
 }
 
-// Device-only pipeline (device quadtree) over several sub-batches, each on its own pair of streams, so that the
-// latency-bound quadtree of one sub-batch overlaps the FAST / pyramid kernels of the next; inside a sub-batch
-// the blur runs on the second stream.  No host work between the stages; one read-back of the counts at the end.
-int run_pipeline_groups(msorb_extractor* h, const LevelView& level0, int n_images, int lap0, int lap1,
-                        msorb_keypoint* d_kps, uint8_t* d_desc, int capacity, int* h_counts, int* h_mono) {
+// MSORB_QUADTREE=host: the selection of n_images images on the host twin (orb_host.cc), one task per image, between the compaction
+// (ev_compact is recorded behind it on s) and describe.  Fetches the candidates, leaves the records in d_sel / d_sel_count on s and
+// the counts in h_sel_count / h_mono, where finish_groups() looks for them.  *max_sel: the largest count of an image.
+int select_on_host(msorb_extractor* h, int n_images, const PipelineCall& c, hipStream_t s, int* max_sel) {
+    const FrameGeom& g = h->G;
+    const int nl = g.nlevels, sel_stride = h->sel_stride;
+    int rc;
+    if ((rc = fetch_candidates(h, n_images))) return rc;
+    std::atomic<int> overflow{0};
+    std::function<void(int)> task = [&](int img) {
+        const Cand16* cand = h->h_compact.p + h->h_img_base.p[img];
+        const int* lc = h->h_level_count.p + (size_t)img * nl;
+        SelRec* out = h->h_sel.p + (size_t)img * sel_stride;
+        std::vector<int> kept;
+        int n = 0;
+        // pass 1: quadtree per level, records in level-major / quadtree order
+        for (int l = 0; l < nl; l++) {
+            const LevelGeom& lg = g.lv[l];
+            distribute_quadtree(cand, lc[l], lg.min_x, lg.max_x, lg.min_y, lg.max_y, lg.quota, kept);
+            for (int k : kept) {
+                if (n >= sel_stride || n >= c.capacity) { overflow.store(1); break; }
+                SelRec r;
+                r.x = (uint16_t)(cand[k].x + kMinBorder);
+                r.y = (uint16_t)(cand[k].y + kMinBorder);
+                r.score = cand[k].score;
+                r.level = (uint8_t)l;
+                r.pad = 0;
+                r.dst = 0;
+                out[n++] = r;
+            }
+            cand += lc[l];
+        }
+        // pass 2: output rows (ORBextractor.cc:1122-1163): inside [lap0,lap1] from the back, else from the front
+        int mono = 0, stereo = n - 1;
+        for (int i = 0; i < n; i++) {
+            SelRec& r = out[i];
+            const float fx = r.level ? (float)r.x * h->P.scale[r.level] : (float)r.x;
+            if (fx >= (float)c.lap0 && fx <= (float)c.lap1) r.dst = stereo--;
+            else r.dst = mono++;
+        }
+        h->h_sel_count.p[img] = n;
+        h->h_mono.p[img] = mono;
+    };
+    if (!h->pool) {   // the worker threads exist only once this path has run
+        int nthreads = h->knobs.host_threads > 0 ? h->knobs.host_threads : (int)std::thread::hardware_concurrency();
+        h->pool.reset(new Pool(std::max(1, std::min(nthreads, 64))));
+    }
+    h->pool->parallel_for(n_images, task);
+    if (overflow.load()) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
+    *max_sel = 0;
+    for (int i = 0; i < n_images; i++) *max_sel = std::max(*max_sel, h->h_sel_count.p[i]);
+    HIPCHK(hipMemcpyAsync(h->d_sel.p, h->h_sel.p, (size_t)n_images * sel_stride * sizeof(SelRec), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(h->d_sel_count.p, h->h_sel_count.p, (size_t)n_images * sizeof(int), hipMemcpyHostToDevice, s));
+    return MSORB_OK;
+}
+
+// The pipeline proper.  level0: where level 0 of every image lives (device memory).  The images run as sub-batches, each on its
+// own stream, so that the latency-bound quadtree of one sub-batch overlaps the FAST / pyramid kernels of the next; inside a
+// sub-batch the blur runs on the second stream or inside another stage's launch.  No host work between the stages (unless the
+// selection is the host twin's: then one sub-batch, and the host waits for the compaction); one read-back of the counts at the end.
+// MSORB_SERIAL_PIPELINE: one sub-batch, every stage a launch of its own on the main stream.
+int run_pipeline(msorb_extractor* h, const LevelView& level0, int n_images, const PipelineCall& c) {
     const FrameGeom& g = h->G;
     const int nl = g.nlevels;
     const int ncells = (int)g.cells.size();
     const bool prof = h->profiling;
+    const bool host_select = !h->device_quadtree;
+    const bool overlap_blur = blur_off_main(h);
     const int sel_stride = h->sel_stride;
-    int ng = n_images >= 16 ? std::min(h->n_groups, kMaxGroups) : 1;
+    int ng = n_images >= 16 && device_pipeline(h) ? std::min(h->n_groups, kMaxGroups) : 1;
     ng = std::max(1, std::min(ng, n_images));
-    const PyramidView pyr_all = make_view(h, h->d_pyr.p, &level0);
-    const PyramidView blur_all = make_blur_view(h, h->d_blur.p);
-    h->last_pyr = pyr_all; h->last_blur = blur_all; h->last_n_images = n_images;
+    h->last_pyr = make_view(h, h->d_pyr.p, &level0);
+    h->last_blur = make_blur_view(h, h->d_blur.p);
+    h->last_n_images = n_images;
+    h->pair_pyramids = c.pair_pyramids;   // (any other call forgets the pair state of an earlier msorb_extract_pair)
     h->h_pyr_valid = false;
     h->h_pyr_async = false;
     h->compact_on_host = false;
     h->last_groups = ng;
     h->last_prof = prof;
+    float host_select_ms = -1.f;
     // sub-batches on streams of their own must not start before the handle's stream has drained (H2D of level 0 in
     // msorb_extract); a single group runs on that very stream, where the order is implicit — and the launches below are
     // then issued while the copy is still in flight instead of after it
-    if (!h->capturing && ng > 1) HIPCHK(hipStreamSynchronize(h->stream));
+    if (ng > 1) HIPCHK(hipStreamSynchronize(h->stream));
     int first = 0;
     for (int gi = 0; gi < ng; gi++) {
         int rc;
@@ -606,44 +741,19 @@ int run_pipeline_groups(msorb_extractor* h, const LevelView& level0, int n_image
         // table the streaming blur does not serve (launch_frame_fast_blur then returns false before launching anything).
         // frame_fuse (MSORB_FRAME_FUSE, read once per handle): 2 (default) the blur rides the SELECTION launch (quadtree_select_blur_kernel:
         // off the critical path — the selection leaves 240 CUs idle), 1 it rides FAST's launch (frame_fast_blur_kernel), 0 side stream.
-        const bool fuse_ok = ng == 1 && n <= 4 && !prof && h->overlap_blur && h->sem.default_taps();
+        const bool fuse_ok = ng == 1 && n <= 4 && !prof && overlap_blur && h->sem.default_taps();
         FrameBlurJob blur_job;
-        const bool fuse_qt = fuse_ok && h->knobs.frame_fuse == 2 && n_images <= 4 && make_frame_blur_job(pyr, blur, n, h->sem, &blur_job);
+        const bool fuse_qt = fuse_ok && !host_select && h->knobs.frame_fuse == 2 && n_images <= 4 && make_frame_blur_job(pyr, blur, n, h->sem, &blur_job);
         const bool fuse_fb = fuse_ok && !fuse_qt && h->knobs.frame_fuse >= 1;
-        hipStream_t sb = h->overlap_blur && !fuse_fb && !fuse_qt ? h->copy_stream : s;
-        const bool side_blur = h->overlap_blur && !fuse_fb && !fuse_qt;
+        const bool side_blur = overlap_blur && !fuse_fb && !fuse_qt;
+        hipStream_t sb = side_blur ? h->copy_stream : s;
+        // the host-pyramid copies of a per-frame call (its level 0 is the handle's own plane) or of both images of msorb_extract_pair
+        int host_pyramids = 0;
+        if (h->host_pyramid && n_images == 1 && level0.base == h->d_pyr.p + g.lv[0].plane_off) host_pyramids = 1;
+        if (h->host_pyramid && n_images == 2 && c.pair_pyramids == 2) host_pyramids = 2;
         if (side_blur || h->host_pyramid) HIPCHK(hipEventRecord(G.ev_pyr, s));   // the pyramid is complete: the side stream's blur and the host-pyramid copies wait for this
         if (side_blur) HIPCHK(hipStreamWaitEvent(sb, G.ev_pyr, 0));
-        if (h->host_pyramid && h->pair_pyramids == 2 && n_images == 2 && ng == 1 && !h->capturing) {
-            // msorb_extract_pair with the host pyramids requested: levels 1.. of both images leave on the pyramid stream
-            int prc;
-            if ((prc = h->h_pyr.ensure(2 * g.pyramid_bytes))) return prc;
-            if (!h->pyr_stream) {
-                HIPCHK(hipStreamCreateWithFlags(&h->pyr_stream, hipStreamNonBlocking));
-                HIPCHK(hipEventCreateWithFlags(&h->ev_pyr_done, hipEventDisableTiming));
-            }
-            HIPCHK(hipStreamWaitEvent(h->pyr_stream, G.ev_pyr, 0));
-            if (nl > 1)
-                for (int i = 0; i < 2; i++)
-                    HIPCHK(hipMemcpyAsync(h->h_pyr.p + (size_t)i * g.pyramid_bytes + g.lv[1].plane_off,
-                                          h->d_pyr.p + (size_t)i * g.pyramid_bytes + g.lv[1].plane_off, g.pyramid_bytes - g.lv[1].plane_off,
-                                          hipMemcpyDeviceToHost, h->pyr_stream));
-            h->h_pyr_async = true;
-        }
-        if (h->host_pyramid && n_images == 1 && !h->capturing && level0.base == h->d_pyr.p + g.lv[0].plane_off) {
-            // per-frame call with the host pyramid requested: levels 1.. leave for pinned memory now, on their own stream
-            int prc;
-            if ((prc = h->h_pyr.ensure(g.pyramid_bytes))) return prc;
-            if (!h->pyr_stream) {
-                HIPCHK(hipStreamCreateWithFlags(&h->pyr_stream, hipStreamNonBlocking));
-                HIPCHK(hipEventCreateWithFlags(&h->ev_pyr_done, hipEventDisableTiming));
-            }
-            HIPCHK(hipStreamWaitEvent(h->pyr_stream, G.ev_pyr, 0));
-            if (nl > 1)
-                HIPCHK(hipMemcpyAsync(h->h_pyr.p + g.lv[1].plane_off, h->d_pyr.p + g.lv[1].plane_off,
-                                      g.pyramid_bytes - g.lv[1].plane_off, hipMemcpyDeviceToHost, h->pyr_stream));
-            h->h_pyr_async = true;
-        }
+        if (host_pyramids && (rc = host_pyramid_copies(h, host_pyramids, G.ev_pyr))) return rc;
         // with the blur on its own stream the critical chain goes first: FAST -> compaction -> quadtree is what describe waits
         // for; the blur (needed by describe only) fills in beside it
         bool blur_carried = false;
@@ -655,11 +765,11 @@ int run_pipeline_groups(msorb_extractor* h, const LevelView& level0, int n_image
         };
         if (!(fuse_fb && launch_frame_fast_blur(pyr, blur, h->d_cells.p, h->d_ttab.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p + cslot,
                                                 h->d_cell_count.p + (size_t)first * ncells, n, h->small_cells, s, h->sem))) {
-            if (!h->overlap_blur) blur_now();   // one stream: pyramid, blur, FAST (the stage events expect this order)
+            if (!overlap_blur) blur_now();   // one stream: pyramid, blur, FAST (the stage events expect this order)
             launch_fast_cells(pyr, h->d_cells.p, h->d_ttab.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p + cslot,
                               h->d_cell_count.p + (size_t)first * ncells, n, h->small_cells, s);
             mark(2, s);
-            if (h->overlap_blur && !fuse_qt) blur_now();
+            if (overlap_blur && !fuse_qt) blur_now();
         }
         launch_cand_compact(h->d_cells.p, ncells, h->d_level_cell_begin.p, nl, g.slots_per_image, h->d_slots.p + cslot,
                             h->d_cell_count.p + (size_t)first * ncells, h->d_cell_off.p + (size_t)first * ncells,
@@ -667,26 +777,33 @@ int run_pipeline_groups(msorb_extractor* h, const LevelView& level0, int n_image
                             h->d_compact.p + cslot, n, s, /*packed=*/false, /*frame_form=*/h->knobs.frame_compact && ng == 1);
         h->compact_fixed_stride = true;
         mark(3, s);
-        if ((rc = launch_quadtree(h->qt, h->d_compact.p + cslot, img_base, h->d_level_count.p + (size_t)first * nl,
-                                  h->d_label.p + cslot, h->d_sel_pt.p + (size_t)first * sel_stride, h->d_sel_n.p + (size_t)first * nl,
-                                  sel_stride, h->scales, lap0, lap1, capacity, h->d_sel.p + (size_t)first * sel_stride,
-                                  h->d_sel_count.p + first, h->d_mono.p + first, n, s, ng == 1 ? h->row_job : nullptr,
-                                  fuse_qt ? &blur_job : nullptr, &blur_carried,
-                                  h->qt_global ? h->d_qt_ws.p + (size_t)first * nl * quadtree_global_workspace_stride(h->qt) : nullptr,   // (groups run side by side: a slice each)
-                                  h->qt_global ? h->d_label_wide.p + cslot : nullptr)))
-            return rc;
-        if (fuse_qt && !blur_carried) blur_now();   // (the selection ran a form that does not carry the blur: on this stream, before describe)
+        int max_sel = std::min(c.capacity, sel_stride);
+        if (host_select) {
+            HIPCHK(hipEventRecord(h->ev_compact, s));
+            const auto t0 = std::chrono::steady_clock::now();
+            if ((rc = select_on_host(h, n, c, s, &max_sel))) return rc;
+            host_select_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        } else {
+            if ((rc = launch_quadtree(h->qt, h->d_compact.p + cslot, img_base, h->d_level_count.p + (size_t)first * nl,
+                                      h->d_label.p + cslot, h->d_sel_pt.p + (size_t)first * sel_stride, h->d_sel_n.p + (size_t)first * nl,
+                                      sel_stride, h->scales, c.lap0, c.lap1, c.capacity, h->d_sel.p + (size_t)first * sel_stride,
+                                      h->d_sel_count.p + first, h->d_mono.p + first, n, s, ng == 1 ? c.row_job : nullptr,
+                                      fuse_qt ? &blur_job : nullptr, &blur_carried,
+                                      h->qt_global ? h->d_qt_ws.p + (size_t)first * nl * quadtree_global_workspace_stride(h->qt) : nullptr,   // (groups run side by side: a slice each)
+                                      h->qt_global ? h->d_label_wide.p + cslot : nullptr)))
+                return rc;
+            if (fuse_qt && !blur_carried) blur_now();   // (the selection ran a form that does not carry the blur: on this stream, before describe)
+        }
         mark(5, s);
         if (side_blur) HIPCHK(hipStreamWaitEvent(s, G.ev_blur, 0));
         launch_describe(pyr, blur, h->d_sel.p + (size_t)first * sel_stride, h->d_sel_count.p + first, sel_stride, h->scales,
-                        d_kps + (size_t)first * capacity, d_desc + (size_t)first * capacity * 32, capacity,
-                        std::min(capacity, sel_stride), n, s, h->sem);
+                        c.d_kps + (size_t)first * c.capacity, c.d_desc + (size_t)first * c.capacity * 32, c.capacity, max_sel, n, s, h->sem);
         mark(6, s);
-        if (!h->skip_count_copies) {  // a fused caller takes the counts from the device itself
+        if (!c.skip_count_copies && !host_select) {  // (a fused caller takes the counts from the device itself; the host twin left them in pinned memory)
             if (n_images <= 4 && first == 0) {   // per-frame call: by copy kernel (the buffers hold >= 4 ints)
                 int crc;
-                if ((crc = frame_copy(h, h->h_sel_count.p, h->d_sel_count.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s)) ||
-                    (crc = frame_copy(h, h->h_mono.p, h->d_mono.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s)))
+                if ((crc = frame_copy(h->h_sel_count.p, h->d_sel_count.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s)) ||
+                    (crc = frame_copy(h->h_mono.p, h->d_mono.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s)))
                     return crc;
             } else {
                 HIPCHK(hipMemcpyAsync(h->h_sel_count.p + first, h->d_sel_count.p + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -695,156 +812,34 @@ int run_pipeline_groups(msorb_extractor* h, const LevelView& level0, int n_image
         }
         first += n;
     }
-    if (h->capturing || h->defer_sync) return MSORB_OK;  // graph capture / fused / submitted call: the caller synchronises and reads back
-    return finish_groups(h, n_images, h_counts, h_mono);
+    if (c.defer_sync) return MSORB_OK;  // fused / submitted call: the caller synchronises and reads back
+    return finish_groups(h, n_images, c.h_counts, c.h_mono, host_select_ms);
 }
 
-// The pipeline proper.  level0: where level 0 of every image lives (device memory).
-int run_pipeline(msorb_extractor* h, const LevelView& level0, int n_images, int lap0, int lap1,
-                 msorb_keypoint* d_kps, uint8_t* d_desc, int capacity, int* h_counts, int* h_mono) {
-    h->pair_pyramids = h->pair_request;   // (any other call forgets the pair state of an earlier msorb_extract_pair)
-    h->pair_request = 0;
-    if (h->device_quadtree && !h->knobs.serial_pipeline)
-        return run_pipeline_groups(h, level0, n_images, lap0, lap1, d_kps, d_desc, capacity, h_counts, h_mono);
-    h->last_groups = 1;
-    const FrameGeom& g = h->G;
-    const int nl = g.nlevels;
-    const int ncells = (int)g.cells.size();
-    hipStream_t s = h->stream;
-    const bool prof = h->profiling;
-    auto mark = [&](int i) { if (prof) (void)hipEventRecord(h->pe[i], s); };
-
-    const PyramidView pyr = make_view(h, h->d_pyr.p, &level0);
-    const PyramidView blur = make_blur_view(h, h->d_blur.p);
-    h->last_pyr = pyr; h->last_blur = blur; h->last_n_images = n_images;
-    h->h_pyr_valid = false;
-
-    mark(0);
-    if (!(n_images <= 4 && !h->sem.resize_single_stage && launch_pyramid_tower(pyr, h->tower, h->d_taps.p, h->tap_x_off.data(), h->tap_y_off.data(), n_images, s)))
-        launch_pyramid(pyr, h->d_taps.p, h->tap_x_off.data(), h->tap_y_off.data(), n_images, s, h->sem);
-    mark(1);
-    // the blur only feeds the descriptor stage: unless stage timing is on, it runs on the second stream, overlapping
-    // the (VALU-bound) FAST kernel and the (latency-bound) quadtree with a bandwidth-bound kernel
-    const bool overlap_blur = h->overlap_blur;
-    if (overlap_blur) {
-        HIPCHK(hipEventRecord(h->ev_pyramid, s));
-        HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_pyramid, 0));
-        if (prof) (void)hipEventRecord(h->pe[7], h->copy_stream);
-        (void)launch_gauss7(pyr, blur, n_images, h->copy_stream, h->sem);
-        if (prof) (void)hipEventRecord(h->pe[8], h->copy_stream);
-        HIPCHK(hipEventRecord(h->ev_blur, h->copy_stream));
+// Frame::ComputeStereoMatches on the outputs of a stereo frame in the device block blk (layout fb): the left eye is image 0 of the
+// handle's last call, the right eye's levels are those of `right` (image 1 of the same pyramid, or a pyramid gathered from another
+// device) and its count is at counts_right.  The caller adds the row records (bands or row table) and the pair step.
+StereoBatchArgs stereo_frame_args(const msorb_extractor* h, const FrameBlock& fb, uint8_t* blk, const PyramidView& right, const int* counts_right,
+                                  int rows, float mb, float mbf) {
+    StereoBatchArgs b{};
+    b.A.kpL = reinterpret_cast<msorb_keypoint*>(blk + fb.o_kps(0)); b.A.kpR = reinterpret_cast<msorb_keypoint*>(blk + fb.o_kps(1));
+    b.A.descL = blk + fb.o_descs(0); b.A.descR = blk + fb.o_descs(1);
+    b.countsL = h->d_sel_count.p; b.countsR = counts_right;
+    b.A.rows0 = rows;
+    for (int l = 0; l < h->G.nlevels; l++) {
+        const LevelView &vl = h->last_pyr.lv[l], &vr = right.lv[l];
+        b.A.pyrL[l] = vl.base; b.A.pyrR[l] = vr.base;
+        b.A.pitchL[l] = vl.pitch; b.A.pitchR[l] = vr.pitch;
+        b.A.rows[l] = vl.h; b.A.cols[l] = vl.w;
+        b.A.scale[l] = h->scales.scale[l]; b.A.inv_scale[l] = h->P.inv_scale[l];
+        b.img_strideL[l] = vl.img_stride; b.img_strideR[l] = vr.img_stride;
     }
-    launch_fast_cells(pyr, h->d_cells.p, h->d_ttab.p, ncells, h->P.ini_th, h->P.min_th, g.slots_per_image, h->d_slots.p,
-                      h->d_cell_count.p, n_images, h->small_cells, s);
-    mark(2);
-    launch_cand_compact(h->d_cells.p, ncells, h->d_level_cell_begin.p, nl, g.slots_per_image, h->d_slots.p,
-                        h->d_cell_count.p, h->d_cell_off.p, h->d_level_count.p, h->d_img_total.p, h->d_img_base.p,
-                        h->d_compact.p, n_images, s, /*packed=*/true);
-    h->compact_fixed_stride = false;
-    mark(3);
-    HIPCHK(hipEventRecord(h->ev_compact, s));
-    if (!overlap_blur) (void)launch_gauss7(pyr, blur, n_images, s, h->sem);
-    mark(4);
-    h->compact_on_host = false;
-    const int sel_stride = h->sel_stride;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), t1 = t0;
-
-    if (h->device_quadtree) {
-        // selection stays on the device: quadtree per (level, image), output layout per image
-        const int qrc = launch_quadtree(h->qt, h->d_compact.p, h->d_img_base.p, h->d_level_count.p, h->d_label.p, h->d_sel_pt.p,
-                                        h->d_sel_n.p, sel_stride, h->scales, lap0, lap1, capacity, h->d_sel.p, h->d_sel_count.p,
-                                        h->d_mono.p, n_images, s, h->row_job, nullptr, nullptr, h->qt_global ? h->d_qt_ws.p : nullptr,
-                                        h->qt_global ? h->d_label_wide.p : nullptr);
-        if (qrc) return qrc;
-        mark(5);
-        if (overlap_blur) HIPCHK(hipStreamWaitEvent(s, h->ev_blur, 0));
-        launch_describe(pyr, blur, h->d_sel.p, h->d_sel_count.p, sel_stride, h->scales, d_kps, d_desc, capacity,
-                        std::min(capacity, sel_stride), n_images, s, h->sem);
-        mark(6);
-        HIPCHK(hipMemcpyAsync(h->h_sel_count.p, h->d_sel_count.p, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h->h_mono.p, h->d_mono.p, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipGetLastError());
-        for (int i = 0; i < n_images; i++) {
-            if (h->h_sel_count.p[i] < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-            h_counts[i] = h->h_sel_count.p[i];
-            if (h_mono) h_mono[i] = h->h_mono.p[i];
-        }
-    } else {
-        int rc;
-        if ((rc = fetch_candidates(h, n_images))) return rc;
-        // host selection, one task per image
-        std::atomic<int> overflow{0};
-        std::function<void(int)> task = [&](int img) {
-            const Cand16* c = h->h_compact.p + h->h_img_base.p[img];
-            const int* lc = h->h_level_count.p + (size_t)img * nl;
-            SelRec* out = h->h_sel.p + (size_t)img * sel_stride;
-            std::vector<int> kept;
-            int n = 0;
-            // pass 1: quadtree per level, records in level-major / quadtree order
-            for (int l = 0; l < nl; l++) {
-                const LevelGeom& lg = g.lv[l];
-                distribute_quadtree(c, lc[l], lg.min_x, lg.max_x, lg.min_y, lg.max_y, lg.quota, kept);
-                for (int k : kept) {
-                    if (n >= sel_stride || n >= capacity) { overflow.store(1); break; }
-                    SelRec r;
-                    r.x = (uint16_t)(c[k].x + kMinBorder);
-                    r.y = (uint16_t)(c[k].y + kMinBorder);
-                    r.score = c[k].score;
-                    r.level = (uint8_t)l;
-                    r.pad = 0;
-                    r.dst = 0;
-                    out[n++] = r;
-                }
-                c += lc[l];
-            }
-            // pass 2: output rows (ORBextractor.cc:1122-1163): inside [lap0,lap1] from the back, else from the front
-            int mono = 0, stereo = n - 1;
-            for (int i = 0; i < n; i++) {
-                SelRec& r = out[i];
-                const float fx = r.level ? (float)r.x * h->P.scale[r.level] : (float)r.x;
-                if (fx >= (float)lap0 && fx <= (float)lap1) r.dst = stereo--;
-                else r.dst = mono++;
-            }
-            h->h_sel_count.p[img] = n;
-            h_counts[img] = n;
-            if (h_mono) h_mono[img] = mono;
-        };
-        if (!h->pool) {   // the worker threads of the host-quadtree path (MSORB_QUADTREE=host) exist only once that path has run
-            int nthreads = h->knobs.host_threads > 0 ? h->knobs.host_threads : (int)std::thread::hardware_concurrency();
-            h->pool.reset(new Pool(std::max(1, std::min(nthreads, 64))));
-        }
-        h->pool->parallel_for(n_images, task);
-        if (overflow.load()) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-        int max_sel = 0;
-        for (int i = 0; i < n_images; i++) max_sel = std::max(max_sel, h->h_sel_count.p[i]);
-        HIPCHK(hipMemcpyAsync(h->d_sel.p, h->h_sel.p, (size_t)n_images * sel_stride * sizeof(SelRec), hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(h->d_sel_count.p, h->h_sel_count.p, (size_t)n_images * sizeof(int), hipMemcpyHostToDevice, s));
-        t1 = std::chrono::steady_clock::now();
-        mark(5);
-        if (overlap_blur) HIPCHK(hipStreamWaitEvent(s, h->ev_blur, 0));
-        launch_describe(pyr, blur, h->d_sel.p, h->d_sel_count.p, sel_stride, h->scales, d_kps, d_desc, capacity, max_sel,
-                        n_images, s, h->sem);
-        mark(6);
-        HIPCHK(hipStreamSynchronize(s));
-        HIPCHK(hipGetLastError());
-    }
-    if (prof) {
-        float ms = 0;
-        const int map[5][3] = {{MSORB_STAGE_PYRAMID, 0, 1}, {MSORB_STAGE_FAST, 1, 2}, {MSORB_STAGE_COMPACT, 2, 3},
-                               {MSORB_STAGE_BLUR, overlap_blur ? 7 : 3, overlap_blur ? 8 : 4}, {MSORB_STAGE_DESCRIBE, 5, 6}};
-        for (auto& m : map) {
-            HIPCHK(hipEventElapsedTime(&ms, h->pe[m[1]], h->pe[m[2]]));
-            h->stage_ms[m[0]] = ms;
-        }
-        if (h->device_quadtree) {
-            HIPCHK(hipEventElapsedTime(&ms, h->pe[4], h->pe[5]));
-            h->stage_ms[MSORB_STAGE_SELECT] = ms;
-        } else {
-            h->stage_ms[MSORB_STAGE_SELECT] = std::chrono::duration<float, std::milli>(t1 - t0).count();
-        }
-    }
-    return MSORB_OK;
+    b.A.mb = mb; b.A.mbf = mbf;
+    b.A.u_right = reinterpret_cast<float*>(blk + fb.o_ur); b.A.depth = reinterpret_cast<float*>(blk + fb.o_dp);
+    b.A.sad = h->d_st_sad.p; b.A.n_oob = reinterpret_cast<int*>(blk + fb.o_oob);
+    b.capacity = (int)fb.cap;
+    b.counts_out = reinterpret_cast<int*>(blk + fb.o_cnt);
+    return b;
 }
 
 }  // namespace
@@ -970,15 +965,11 @@ int msorb_extractor_create(int nfeatures, float scale_factor, int nlevels, int i
     const int prio_blur = prio_least;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithPriority(&h->copy_stream, hipStreamNonBlocking, prio_blur) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_compact, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_pyramid, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_blur, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&h->ev_compact, hipEventDisableTiming) != hipSuccess) {
         set_last_error("stream/event creation failed");
         delete h;
         return MSORB_E_HIP;
     }
-    for (auto& e : h->pe)
-        if (hipEventCreate(&e) != hipSuccess) { delete h; return MSORB_E_HIP; }
     upload_patch_tables(kPattern, h->P.umax, h->stream);
     // the environment is read here and nowhere else in this file
     {
@@ -1006,14 +997,13 @@ void msorb_extractor_destroy(msorb_extractor* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->pool.reset();
-    h->d_pyr.release(); h->d_blur.release(); h->d_desc1.release(); h->d_taps.release(); h->d_cells.release(); h->d_ttab.release();
+    h->d_pyr.release(); h->d_blur.release(); h->d_taps.release(); h->d_cells.release(); h->d_ttab.release();
     h->d_level_cell_begin.release(); h->d_cell_count.release(); h->d_cell_off.release(); h->d_level_count.release();
     h->d_img_total.release(); h->d_img_base.release(); h->d_sel_count.release(); h->d_slots.release();
-    h->d_compact.release(); h->d_sel.release(); h->d_kps1.release();
+    h->d_compact.release(); h->d_sel.release();
     h->d_st_sad.release(); h->d_st_rows.release(); h->d_st_list.release(); h->d_st_block.release(); h->d_st_img.release(); h->d_out1.release();
     h->d_gather_pyr.release(); h->d_gather_cnt.release();
     if (h->ev_split) (void)hipEventDestroy(h->ev_split);
-    if (h->ev_pyr_done) (void)hipEventDestroy(h->ev_pyr_done);
     if (h->pyr_stream) { (void)hipStreamSynchronize(h->pyr_stream); (void)hipStreamDestroy(h->pyr_stream); }
     h->h_level_count.release(); h->h_img_base.release(); h->h_sel_count.release(); h->h_compact.release();
     h->h_sel.release(); h->h_pyr.release(); h->h_img_pin.release(); h->h_out_pin.release(); h->h_gather.release();
@@ -1021,13 +1011,10 @@ void msorb_extractor_destroy(msorb_extractor* h) {
         if (!G.ready) continue;
         (void)hipStreamSynchronize(G.s);
         for (auto& e : G.pe) if (e) (void)hipEventDestroy(e);
-        (void)hipEventDestroy(G.ev_pyr); (void)hipEventDestroy(G.ev_blur); (void)hipEventDestroy(G.ev_fast);
+        (void)hipEventDestroy(G.ev_pyr); (void)hipEventDestroy(G.ev_blur);
         if (G.own_stream) (void)hipStreamDestroy(G.s);
     }
-    for (auto& e : h->pe) if (e) (void)hipEventDestroy(e);
     if (h->ev_compact) (void)hipEventDestroy(h->ev_compact);
-    if (h->ev_pyramid) (void)hipEventDestroy(h->ev_pyramid);
-    if (h->ev_blur) (void)hipEventDestroy(h->ev_blur);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     delete h;
@@ -1102,7 +1089,7 @@ static int extract_batch_common(msorb_extractor* h, const uint8_t* d_images, int
         set_last_error("bad strides");
         return MSORB_E_INVALID;
     }
-    if (submit_only && (!h->device_quadtree || h->knobs.serial_pipeline)) {
+    if (submit_only && !device_pipeline(h)) {
         set_last_error("msorb_extract_batch_submit needs the device pipeline");
         return MSORB_E_INVALID;
     }
@@ -1123,11 +1110,13 @@ static int extract_batch_common(msorb_extractor* h, const uint8_t* d_images, int
         launch_stage_level0(l0, h->d_pyr.p + g0.plane_off, g0.pitch, h->G.pyramid_bytes, n_images, h->stream);
         l0 = LevelView{h->d_pyr.p + g0.plane_off, h->G.pyramid_bytes, g0.pitch, cols, rows};
     }
-    if (!submit_only) return run_pipeline(h, l0, n_images, lap0, lap1, d_kps, d_desc, capacity, h_counts, h_mono);
-    h->defer_sync = true;
-    rc = run_pipeline(h, l0, n_images, lap0, lap1, d_kps, d_desc, capacity, nullptr, nullptr);
-    h->defer_sync = false;
-    if (rc == MSORB_OK) h->pending_batch = n_images;
+    PipelineCall call;
+    call.lap0 = lap0; call.lap1 = lap1;
+    call.d_kps = d_kps; call.d_desc = d_desc; call.capacity = capacity;
+    call.h_counts = h_counts; call.h_mono = h_mono;
+    call.defer_sync = submit_only;
+    rc = run_pipeline(h, l0, n_images, call);
+    if (submit_only && rc == MSORB_OK) h->pending_batch = n_images;
     return rc;
 }
 
@@ -1167,50 +1156,36 @@ int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, 
     if ((rc = ensure_geometry(h, rows, cols))) return rc;
     if ((rc = ensure_batch(h, 1))) return rc;
     const int cap = capacity_of(h);
-    if ((rc = h->d_kps1.ensure(cap))) return rc;
-    if ((rc = h->d_desc1.ensure((size_t)cap * 32))) return rc;
     const LevelGeom& g0 = h->G.lv[0];
-    // level 0 = copy of the caller's image (ORBextractor.cc:1190: the input is never modified or aliased).  Pageable
-    // memory is staged through pinned buffers owned by the handle: a plain hipMemcpy from pageable memory makes the
-    // driver pin/unpin per call, which costs more than the whole kernel chain.
+    // keypoints + descriptors of the frame as one block, on the device and in pinned memory (its own layout: one image, the
+    // descriptors at a 16-byte boundary)
+    const size_t o_desc = up16((size_t)cap * sizeof(msorb_keypoint)), blk_bytes = o_desc + (size_t)cap * 32;
+    if ((rc = h->d_out1.ensure(blk_bytes)) || (rc = h->h_out_pin.ensure(blk_bytes))) return rc;
+    // level 0 = copy of the caller's image (ORBextractor.cc:1190: the input is never modified or aliased)
     const bool staged = h->h_img_pin.p && image == h->h_img_pin.p && stride == (size_t)g0.pitch;   // msorb_stage_image did the copy
     if ((rc = h->h_img_pin.ensure(staged ? 1 : (size_t)g0.pitch * rows))) return rc;
-    if ((rc = h->h_out_pin.ensure((size_t)cap * (sizeof(msorb_keypoint) + 32)))) return rc;
-    // An image in admitted host memory (msorb_host_alloc / msorb_host_register) is read where it lies by the upload kernel: no copy
-    // in front of the upload.  Everything else is staged as before.
+    // device pipeline: nothing in it needs the host, so the whole frame is enqueued, the full-capacity output block (~120 KB)
+    // follows in ONE copy and the call synchronises once.  Otherwise (stage timing, host selection, serial) the pipeline
+    // synchronises itself and the n keypoints it found are fetched afterwards.
+    const bool one_sync = device_pipeline(h) && !h->profiling;
     DirectInputs in;
-    const bool direct = !staged && in.admit(h, 0, image, rows, cols, stride);
-    if (direct) {
-        h->in_stats.images_direct++;
-    } else if (!staged) {
-        copy_rows(h->h_img_pin.p, g0.pitch, image, stride, rows, cols);
-        h->in_stats.images_staged++;
-        h->in_stats.bytes_staged += (uint64_t)rows * cols;
-    }
-    h->in_stats.upload_launches++;
-    LevelView l0{h->d_pyr.p + g0.plane_off, h->G.pyramid_bytes, g0.pitch, cols, rows};
-    msorb_keypoint* pk = reinterpret_cast<msorb_keypoint*>(h->h_out_pin.p);
-    uint8_t* pd = h->h_out_pin.p + (size_t)cap * sizeof(msorb_keypoint);
+    const int plane0 = 0;
+    const uint8_t* host_l0[2] = {nullptr, nullptr};
+    if ((rc = in.level0(h, 1, &image, &stride, staged ? 1 : 0, &plane0, rows, cols, h->d_pyr.p + g0.plane_off, 0, /*by_memcpy=*/!one_sync, h->stream, host_l0)))
+        return rc;
+    const LevelView l0{h->d_pyr.p + g0.plane_off, h->G.pyramid_bytes, g0.pitch, cols, rows};
+    msorb_keypoint* const pk = reinterpret_cast<msorb_keypoint*>(h->h_out_pin.p);
+    uint8_t* const pd = h->h_out_pin.p + o_desc;
     int n = 0, mono = 0;
-
-    if (h->device_quadtree && !h->knobs.serial_pipeline && !h->profiling) {
-        // device pipeline: nothing in it needs the host, so the whole frame is enqueued, the full-capacity output block
-        // (keypoints + descriptors, ~120 KB) follows in ONE copy and the call synchronises once
-        const size_t o_desc = ((size_t)cap * sizeof(msorb_keypoint) + 15) & ~(size_t)15, blk_bytes = o_desc + (size_t)cap * 32;
-        if ((rc = h->d_out1.ensure(blk_bytes))) return rc;
-        if ((rc = h->h_out_pin.ensure(blk_bytes))) return rc;
-        pk = reinterpret_cast<msorb_keypoint*>(h->h_out_pin.p);
-        pd = h->h_out_pin.p + o_desc;
-        if (direct) in.upload(1, h->d_pyr.p + g0.plane_off, 0, g0.pitch, rows, cols, h->stream);
-        else if ((rc = frame_copy(h, h->d_pyr.p + g0.plane_off, h->h_img_pin.p, (size_t)g0.pitch * rows, hipMemcpyHostToDevice, h->stream))) return rc;
-        h->defer_sync = true;
-        rc = run_pipeline(h, l0, 1, lap0, lap1, reinterpret_cast<msorb_keypoint*>(h->d_out1.p), h->d_out1.p + o_desc, cap, &n, &mono);
-        h->defer_sync = false;
-        if (rc) return rc;
-        if ((rc = frame_copy(h, h->h_out_pin.p, h->d_out1.p, blk_bytes, hipMemcpyDeviceToHost, h->stream))) return rc;
-        // host level 0 (msorb_pyramid_level hands out the handle's plane, never the caller's pointer): the copy the staged path makes
-        // in front of the upload, made here while the host would wait for the device anyway
-        if (direct && h->h_pyr_async) copy_rows(h->h_img_pin.p, g0.pitch, image, stride, rows, cols);
+    PipelineCall call;
+    call.lap0 = lap0; call.lap1 = lap1;
+    call.d_kps = reinterpret_cast<msorb_keypoint*>(h->d_out1.p); call.d_desc = h->d_out1.p + o_desc; call.capacity = cap;
+    call.h_counts = &n; call.h_mono = &mono;
+    call.defer_sync = one_sync;
+    if ((rc = run_pipeline(h, l0, 1, call))) return rc;
+    if (one_sync && (rc = frame_copy(h->h_out_pin.p, h->d_out1.p, blk_bytes, hipMemcpyDeviceToHost, h->stream))) return rc;
+    if (h->h_pyr_async) in.late_level0(h, rows, cols, host_l0);
+    if (one_sync) {
         HIPCHK(hipStreamSynchronize(h->stream));
         in.done();
         if (h->h_pyr_async) HIPCHK(hipStreamSynchronize(h->pyr_stream));
@@ -1218,19 +1193,14 @@ int msorb_extract(msorb_extractor* h, const uint8_t* image, int rows, int cols, 
         n = h->h_sel_count.p[0];
         mono = h->h_mono.p[0];
         if (n < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-        if (n > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
     } else {
-        if (direct) in.upload(1, h->d_pyr.p + g0.plane_off, 0, g0.pitch, rows, cols, h->stream);
-        else HIPCHK(hipMemcpyAsync(h->d_pyr.p + g0.plane_off, h->h_img_pin.p, (size_t)g0.pitch * rows, hipMemcpyHostToDevice, h->stream));
-        if ((rc = run_pipeline(h, l0, 1, lap0, lap1, h->d_kps1.p, h->d_desc1.p, cap, &n, &mono))) return rc;   // (synchronises the stream)
-        if (direct && h->h_pyr_async) copy_rows(h->h_img_pin.p, g0.pitch, image, stride, rows, cols);
-        in.done();
-        if (n > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
-        if (n > 0) {
-            HIPCHK(hipMemcpyAsync(pk, h->d_kps1.p, (size_t)n * sizeof(msorb_keypoint), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipMemcpyAsync(pd, h->d_desc1.p, (size_t)n * 32, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-        }
+        in.done();   // (run_pipeline synchronised the stream)
+    }
+    if (n > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
+    if (!one_sync && n > 0) {
+        HIPCHK(hipMemcpyAsync(pk, call.d_kps, (size_t)n * sizeof(msorb_keypoint), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(pd, call.d_desc, (size_t)n * 32, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
     }
     if (n > 0) {
         memcpy(keypoints, pk, (size_t)n * sizeof(msorb_keypoint));
@@ -1250,93 +1220,44 @@ int msorb_extract_pair(msorb_extractor* h, const uint8_t* image_a, const uint8_t
     *mono_a = *mono_b = -1;
     if (!image_a || !image_b || rows <= 0 || cols <= 0) return MSORB_E_EMPTY;
     if (!kps_a || !desc_a || !kps_b || !desc_b || (int)stride_a < cols || (int)stride_b < cols) return MSORB_E_INVALID;
-    if (!h->device_quadtree || h->knobs.serial_pipeline || h->profiling) { set_last_error("msorb_extract_pair needs the device pipeline"); return MSORB_E_INVALID; }
+    if (!device_pipeline(h) || h->profiling) { set_last_error("msorb_extract_pair needs the device pipeline"); return MSORB_E_INVALID; }
     HIPCHK(hipSetDevice(h->device));
     int rc;
     if ((rc = ensure_geometry(h, rows, cols))) return rc;
     if ((rc = ensure_batch(h, 2))) return rc;
     const int cap = capacity_of(h);
-    const FrameGeom& g = h->G;
-    const LevelGeom& g0 = g.lv[0];
-    const size_t kp_bytes = (size_t)cap * sizeof(msorb_keypoint), o_desc = 2 * kp_bytes, out_bytes = o_desc + (size_t)2 * cap * 32;
+    const LevelGeom& g0 = h->G.lv[0];
+    const FrameBlock fb(cap, /*stereo=*/false);
     const size_t plane = (size_t)g0.pitch * rows;
-    if ((rc = h->d_st_block.ensure(out_bytes)) || (rc = h->d_st_img.ensure(2 * plane + 256)) || (rc = h->h_img_pin.ensure(2 * plane)) ||
-        (rc = h->h_out_pin.ensure(out_bytes)))
+    if ((rc = h->d_st_block.ensure(fb.out_bytes)) || (rc = h->d_st_img.ensure(2 * plane + 256)) || (rc = h->h_img_pin.ensure(2 * plane)) ||
+        (rc = h->h_out_pin.ensure(fb.out_bytes)))
         return rc;
     hipStream_t s = h->stream;
-    const uint8_t* src[2] = {image_a, image_b};
+    const uint8_t* const src[2] = {image_a, image_b};
     const size_t stride[2] = {stride_a, stride_b};
-    // A staged image may lie in THIS handle's own staging block (msorb_stage_image stages into plane 0): the plane an un-staged
-    // image is copied into must not be one a staged image of this call still has to be uploaded from.
-    int own_plane[2] = {-1, -1};   // plane of h_img_pin a staged image occupies (overlaps), -1: memory of another handle
-    for (int i = 0; i < 2; i++) {
-        if (!(staged & (1 << i))) continue;
-        if (stride[i] != (size_t)g0.pitch) { set_last_error("msorb_extract_pair: a staged image must have the staging pitch"); return MSORB_E_INVALID; }
-        const uint8_t* lo = h->h_img_pin.p;
-        if (src[i] + plane > lo && src[i] < lo + 2 * plane) {
-            if (src[i] != lo && src[i] != lo + plane) { set_last_error("msorb_extract_pair: a staged pointer inside this handle's staging block must be a plane msorb_stage_image returned"); return MSORB_E_INVALID; }
-            own_plane[i] = src[i] == lo ? 0 : 1;
-        }
-    }
-    // An image without a `staged` bit that lies in admitted host memory is read in place; then ONE launch uploads both images, the
-    // other one from wherever it lies in pinned memory (its msorb_stage_image plane, or the plane it is staged into here).
+    int dst_plane[2];
+    if (const char* why = pair_staging_planes(h->h_img_pin.p, plane, (size_t)g0.pitch, src, stride, staged, dst_plane)) { set_last_error(why); return MSORB_E_INVALID; }
     DirectInputs in;
-    bool any_direct = false;
-    for (int i = 0; i < 2; i++) any_direct = (!(staged & (1 << i)) && in.admit(h, i, src[i], rows, cols, stride[i])) || any_direct;
-    uint8_t* late_l0[2] = {nullptr, nullptr};   // plane of h_img_pin a direct image's host level 0 goes to
-    for (int i = 0; i < 2; i++) {
-        const uint8_t* pin;
-        const int other = own_plane[1 - i];
-        const int dst_plane = other == i ? 1 - i : i;   // the partner's staged image sits in this image's usual plane: take the other one
-        uint8_t* d = h->h_img_pin.p + (size_t)dst_plane * plane;
-        if (staged & (1 << i)) {   // already in pinned memory at the library's pitch (msorb_stage_image)
-            pin = src[i];
-        } else if (in.direct(i)) {
-            pin = nullptr;   // (no host level 0 yet: see below)
-            late_l0[i] = d;
-            h->in_stats.images_direct++;
-        } else {
-            copy_rows(d, g0.pitch, src[i], stride[i], rows, cols);
-            h->in_stats.images_staged++;
-            h->in_stats.bytes_staged += (uint64_t)rows * cols;
-            pin = d;
-        }
-        h->pair_l0[i] = pin;
-        if (any_direct) {
-            if (!in.direct(i)) in.src[i] = Level0Src{pin, (size_t)g0.pitch};
-        } else {
-            h->in_stats.upload_launches++;
-            if ((rc = frame_copy(h, h->d_st_img.p + (size_t)i * plane, pin, plane, hipMemcpyHostToDevice, s))) return rc;
-        }
-    }
-    if (any_direct) {
-        h->in_stats.upload_launches++;
-        in.upload(2, h->d_st_img.p, plane, g0.pitch, rows, cols, s);
-    }
-    LevelView l0{h->d_st_img.p, plane, g0.pitch, cols, rows};
+    if ((rc = in.level0(h, 2, src, stride, staged, dst_plane, rows, cols, h->d_st_img.p, plane, /*by_memcpy=*/false, s, h->pair_l0))) return rc;
+    const LevelView l0{h->d_st_img.p, plane, g0.pitch, cols, rows};
     uint8_t* const blk = h->d_st_block.p;
-    int counts[2] = {0, 0}, mono[2] = {0, 0};
-    h->pair_request = 2;
-    h->defer_sync = true;
-    rc = run_pipeline(h, l0, 2, lap0, lap1, reinterpret_cast<msorb_keypoint*>(blk), blk + o_desc, cap, counts, mono);
-    h->defer_sync = false;
-    if (rc) { h->pair_pyramids = 0; return rc; }
+    PipelineCall call;
+    call.lap0 = lap0; call.lap1 = lap1;
+    call.d_kps = reinterpret_cast<msorb_keypoint*>(blk); call.d_desc = blk + fb.o_desc; call.capacity = cap;
+    call.defer_sync = true;
+    call.pair_pyramids = 2;
+    if ((rc = run_pipeline(h, l0, 2, call))) { h->pair_pyramids = 0; return rc; }
     uint8_t* o = h->h_out_pin.p;
-    if ((rc = frame_copy(h, o, blk, out_bytes, hipMemcpyDeviceToHost, s))) return rc;
-    for (int i = 0; i < 2; i++)   // host level 0 of a direct image, copied while the device works (as in msorb_extract)
-        if (late_l0[i] && h->h_pyr_async) { copy_rows(late_l0[i], g0.pitch, src[i], stride[i], rows, cols); h->pair_l0[i] = late_l0[i]; }
+    if ((rc = frame_copy(o, blk, fb.out_bytes, hipMemcpyDeviceToHost, s))) return rc;
+    if (h->h_pyr_async) in.late_level0(h, rows, cols, h->pair_l0);   // (while the device works, as in msorb_extract)
     HIPCHK(hipStreamSynchronize(s));
     in.done();
     if (h->h_pyr_async) HIPCHK(hipStreamSynchronize(h->pyr_stream));
     HIPCHK(hipGetLastError());
-    const int na = h->h_sel_count.p[0], nb = h->h_sel_count.p[1];
-    if (na < 0 || nb < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-    if (na > capacity || nb > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
-    memcpy(kps_a, o, (size_t)na * sizeof(msorb_keypoint));
-    memcpy(kps_b, o + kp_bytes, (size_t)nb * sizeof(msorb_keypoint));
-    memcpy(desc_a, o + o_desc, (size_t)na * 32);
-    memcpy(desc_b, o + o_desc + (size_t)cap * 32, (size_t)nb * 32);
-    *n_a = na; *n_b = nb;
+    msorb_keypoint* const kps[2] = {kps_a, kps_b};
+    uint8_t* const desc[2] = {desc_a, desc_b};
+    if (const char* why = fb.copy_out(o, h->h_sel_count.p, capacity, kps, desc, nullptr, nullptr, nullptr)) { set_last_error(why); return MSORB_E_CAPACITY; }
+    *n_a = h->h_sel_count.p[0]; *n_b = h->h_sel_count.p[1];
     *mono_a = h->h_mono.p[0]; *mono_b = h->h_mono.p[1];
     return MSORB_OK;
 }
@@ -1349,7 +1270,7 @@ int msorb_stage_image(msorb_extractor* h, const uint8_t* image, int rows, int co
     if ((rc = ensure_geometry(h, rows, cols))) return rc;
     const LevelGeom& g0 = h->G.lv[0];
     if ((rc = h->h_img_pin.ensure(2 * (size_t)g0.pitch * rows))) return rc;   // (two planes: msorb_extract_pair stages here too)
-    for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + (size_t)y * g0.pitch, image + (size_t)y * stride, cols);
+    copy_rows(h->h_img_pin.p, g0.pitch, image, stride, rows, cols);
     h->in_stats.images_staged++;
     h->in_stats.bytes_staged += (uint64_t)rows * cols;
     *pinned = h->h_img_pin.p;
@@ -1364,19 +1285,9 @@ int msorb_pyramid_level_image(msorb_extractor* h, int image, int level, const ui
         return MSORB_E_INVALID;
     HIPCHK(hipSetDevice(h->device));
     const FrameGeom& g = h->G;
-    if (!h->h_pyr_async) {   // the pair call ran without msorb_extractor_set_host_pyramid: fetch both pyramids now, once
-        int rc;
-        if ((rc = h->h_pyr.ensure(2 * g.pyramid_bytes))) return rc;
-        if (g.nlevels > 1)
-            for (int i = 0; i < 2; i++)
-                HIPCHK(hipMemcpy(h->h_pyr.p + (size_t)i * g.pyramid_bytes + g.lv[1].plane_off,
-                                 h->d_pyr.p + (size_t)i * g.pyramid_bytes + g.lv[1].plane_off, g.pyramid_bytes - g.lv[1].plane_off, hipMemcpyDeviceToHost));
-        if (!h->pyr_stream) {
-            HIPCHK(hipStreamCreateWithFlags(&h->pyr_stream, hipStreamNonBlocking));
-            HIPCHK(hipEventCreateWithFlags(&h->ev_pyr_done, hipEventDisableTiming));
-        }
-        h->h_pyr_async = true;
-    }
+    int rc;
+    // the pair call ran without msorb_extractor_set_host_pyramid: fetch both pyramids now, once
+    if (!h->h_pyr_async && (rc = host_pyramid_copies(h, 2, nullptr))) return rc;
     HIPCHK(hipStreamSynchronize(h->pyr_stream));
     if (level == 0 && !h->pair_l0[image]) {   // an image that was read in place and has no host copy yet: level 0 comes back from the device
         const LevelView& v = h->last_pyr.lv[0];
@@ -1417,7 +1328,7 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
     if (!kps_left || !desc_left || !kps_right || !desc_right || !u_right || !depth || (int)stride_left < cols ||
         (int)stride_right < cols)
         return MSORB_E_INVALID;
-    if (!h->device_quadtree || h->knobs.serial_pipeline) {
+    if (!device_pipeline(h)) {
         set_last_error("msorb_extract_stereo needs the device pipeline");
         return MSORB_E_INVALID;
     }
@@ -1433,90 +1344,48 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
     const int row_cap = cap * ((int)std::ceil(4.0f * smax) + 3);
     const bool bands = rows <= 4095;   // (a band record holds 12-bit rows; taller images — none of the BASELINE configs — take the row table)
     if (!bands && (size_t)(2 * rows + 1) * sizeof(int) > 60000) { set_last_error("image too tall for the stereo row table"); return MSORB_E_INVALID; }
-    // one device block for everything that travels back: [kps 2*cap][desc 2*cap*32][u_right cap][depth cap][n_oob], and
-    // one device block for the two level-0 planes (read in place by the pipeline): one copy each way
-    const size_t kp_bytes = (size_t)cap * sizeof(msorb_keypoint);
-    const size_t o_desc = 2 * kp_bytes, o_ur = o_desc + (size_t)2 * cap * 32, o_dp = o_ur + (size_t)cap * 4,
-                 o_oob = o_dp + (size_t)cap * 4, o_cnt = o_oob + 4, out_bytes = o_oob + 16;  // [n_oob][n_left][n_right]
+    // one device block for everything that travels back (FrameBlock), and one device block for the two level-0 planes (read in
+    // place by the pipeline): one copy each way
+    const FrameBlock fb(cap, /*stereo=*/true);
     const size_t plane = (size_t)g0.pitch * rows;
-    if ((rc = h->d_st_block.ensure(out_bytes)) || (rc = h->d_st_img.ensure(2 * plane + 256)) ||
-        (rc = h->h_img_pin.ensure(2 * plane)) || (rc = h->h_out_pin.ensure(out_bytes)) || (rc = h->d_st_sad.ensure(cap)) ||
+    if ((rc = h->d_st_block.ensure(fb.out_bytes)) || (rc = h->d_st_img.ensure(2 * plane + 256)) ||
+        (rc = h->h_img_pin.ensure(2 * plane)) || (rc = h->h_out_pin.ensure(fb.out_bytes)) || (rc = h->d_st_sad.ensure(cap)) ||
         (rc = h->d_st_rows.ensure((size_t)rows + 1)) || (rc = h->d_st_list.ensure((size_t)row_cap * 2)))
         return rc;
-    // pageable rows -> pinned planes -> device, one eye at a time: the left plane rides PCIe while the right one is staged
     hipStream_t s = h->stream;
-    // An eye in admitted host memory is read in place; with at least one such eye ONE launch uploads both (a pageable eye is staged
-    // first and rides that launch from its staging plane).
     DirectInputs in;
-    const bool direct_l = in.admit(h, 0, left, rows, cols, stride_left), direct_r = in.admit(h, 1, right, rows, cols, stride_right);
-    if (direct_l || direct_r) {
-        const uint8_t* const eye[2] = {left, right};
-        const size_t eye_stride[2] = {stride_left, stride_right};
-        for (int i = 0; i < 2; i++) {
-            if (in.direct(i)) { h->in_stats.images_direct++; continue; }
-            copy_rows(h->h_img_pin.p + (size_t)i * plane, g0.pitch, eye[i], eye_stride[i], rows, cols);
-            in.src[i] = Level0Src{h->h_img_pin.p + (size_t)i * plane, (size_t)g0.pitch};
-            h->in_stats.images_staged++;
-            h->in_stats.bytes_staged += (uint64_t)rows * cols;
-        }
-        h->in_stats.upload_launches++;
-        in.upload(2, h->d_st_img.p, plane, g0.pitch, rows, cols, s);
-    } else {
-        for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + (size_t)y * g0.pitch, left + (size_t)y * stride_left, cols);
-        if ((rc = frame_copy(h, h->d_st_img.p, h->h_img_pin.p, plane, hipMemcpyHostToDevice, s))) return rc;
-        for (int y = 0; y < rows; y++) memcpy(h->h_img_pin.p + plane + (size_t)y * g0.pitch, right + (size_t)y * stride_right, cols);
-        if ((rc = frame_copy(h, h->d_st_img.p + plane, h->h_img_pin.p + plane, plane, hipMemcpyHostToDevice, s))) return rc;
-        h->in_stats.images_staged += 2;
-        h->in_stats.bytes_staged += 2 * (uint64_t)rows * cols;
-        h->in_stats.upload_launches += 2;
-    }
-    LevelView l0{h->d_st_img.p, plane, g0.pitch, cols, rows};
+    const uint8_t* const eye[2] = {left, right};
+    const size_t eye_stride[2] = {stride_left, stride_right};
+    const int eye_plane[2] = {0, 1};
+    const uint8_t* host_l0[2];
+    if ((rc = in.level0(h, 2, eye, eye_stride, 0, eye_plane, rows, cols, h->d_st_img.p, plane, /*by_memcpy=*/false, s, host_l0))) return rc;
+    const LevelView l0{h->d_st_img.p, plane, g0.pitch, cols, rows};
     uint8_t* const blk = h->d_st_block.p;
-    msorb_keypoint* const d_kps = reinterpret_cast<msorb_keypoint*>(blk);
-    uint8_t* const d_desc = blk + o_desc;
-    int counts[2] = {0, 0}, mono[2] = {0, 0};
     // (n_oob is zeroed by the layout launch that writes the band records — or by the row-table kernel of launch_stereo_match_batch)
     // what vRowIndices (Frame.cc:757-776) would hold about the right keypoints leaves the selection-layout launch as band records
-    const StereoRowJob row_job{1, rows, reinterpret_cast<int2*>(h->d_st_list.p), h->d_st_list.p + 2 * (size_t)cap, reinterpret_cast<int*>(blk + o_oob)};
-    h->row_job = bands ? &row_job : nullptr;
-    h->defer_sync = h->skip_count_copies = true;
-    rc = run_pipeline(h, l0, 2, 0, 0, d_kps, d_desc, cap, counts, mono);
-    h->defer_sync = h->skip_count_copies = false;
-    h->row_job = nullptr;
-    if (rc) return rc;
-    // stereo association on the device outputs (pair 0 = images 0 / 1)
-    StereoBatchArgs b{};
-    b.A.kpL = d_kps;
-    b.A.descL = d_desc;
-    b.A.rows0 = rows;
-    for (int l = 0; l < g.nlevels; l++) {
-        const LevelView& v = h->last_pyr.lv[l];
-        b.A.pyrL[l] = v.base; b.A.pyrR[l] = v.base + v.img_stride;
-        b.A.pitchL[l] = b.A.pitchR[l] = v.pitch;
-        b.A.rows[l] = v.h; b.A.cols[l] = v.w;
-        b.A.scale[l] = h->scales.scale[l]; b.A.inv_scale[l] = h->P.inv_scale[l];
-        b.img_strideL[l] = b.img_strideR[l] = v.img_stride;
-    }
-    b.A.mb = mb; b.A.mbf = mbf;
-    b.A.u_right = reinterpret_cast<float*>(blk + o_ur); b.A.depth = reinterpret_cast<float*>(blk + o_dp);
-    b.A.sad = h->d_st_sad.p; b.A.n_oob = reinterpret_cast<int*>(blk + o_oob);
-    b.capacity = cap;
+    const StereoRowJob row_job{1, rows, reinterpret_cast<int2*>(h->d_st_list.p), h->d_st_list.p + 2 * (size_t)cap, reinterpret_cast<int*>(blk + fb.o_oob)};
+    PipelineCall call;
+    call.d_kps = reinterpret_cast<msorb_keypoint*>(blk); call.d_desc = blk + fb.o_desc; call.capacity = cap;
+    call.row_job = bands ? &row_job : nullptr;
+    call.defer_sync = call.skip_count_copies = true;
+    if ((rc = run_pipeline(h, l0, 2, call))) return rc;
+    // stereo association on the device outputs (pair 0 = images 0 / 1 of the pyramid)
+    PyramidView right_pyr = h->last_pyr;
+    for (int l = 0; l < g.nlevels; l++) right_pyr.lv[l].base += right_pyr.lv[l].img_stride;
+    StereoBatchArgs b = stereo_frame_args(h, fb, blk, right_pyr, h->d_sel_count.p + 1, rows, mb, mbf);
     b.pair_step = 2;
-    b.A.kpR = d_kps + cap; b.A.descR = d_desc + (size_t)cap * 32;
-    b.countsL = h->d_sel_count.p; b.countsR = h->d_sel_count.p + 1;
     if (bands) {
         b.band = reinterpret_cast<const int2*>(h->d_st_list.p);
         b.band_level_begin = h->d_st_list.p + 2 * (size_t)cap;
     } else {
         b.row_begin = h->d_st_rows.p; b.row_list = reinterpret_cast<int2*>(h->d_st_list.p); b.row_cap = row_cap;
     }
-    b.counts_out = reinterpret_cast<int*>(blk + o_cnt);
     uint8_t* o = h->h_out_pin.p;
     // Without a sink the median rule rides the read-back launch (stereo_median_readback_kernel; in-process A/B, alternating blocks
     // of 100 frames, three processes: msorb_extract_stereo through the Python mirror 0.2404 / 0.2450 / 0.2414 -> 0.2368 / 0.2407 /
     // 0.2376 ms) — unless the copies are SDMA's (MSORB_FRAME_COPIES=sdma) or the block's tail is not 16-byte aligned (odd capacity).
     static const bool sdma_copies = [] { const char* e = getenv("MSORB_FRAME_COPIES"); return e && std::string(e) == "sdma"; }();
-    b.median_with_readback = !sink && !sdma_copies && (o_ur & 15) == 0 &&
+    b.median_with_readback = !sink && !sdma_copies && (fb.o_ur & 15) == 0 &&
                              ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(blk)) & 15) == 0;
     launch_stereo_match_batch(b, 1, cap, s, /*row_table_built=*/bands);
     if (sink) {
@@ -1527,30 +1396,24 @@ int msorb::extract_stereo_sink(msorb_extractor* h, const uint8_t* left, const ui
         // frames, three processes: msorb_extract_stereo_frame 0.1999 -> 0.1969 ms, the motion-model call 0.2341 -> 0.2335;
         // the same order with hipMemcpyAsync: no different from before).
         HIPCHK(hipEventRecord(h->ev_split, s));
-        const StereoDeviceOutputs so{d_kps, d_desc, b.A.u_right, reinterpret_cast<const int*>(blk + o_cnt), cap, s};
+        const StereoDeviceOutputs so{call.d_kps, call.d_desc, b.A.u_right, b.counts_out, cap, s};
         if ((rc = sink(ctx, so))) { (void)hipStreamSynchronize(s); return rc; }
         HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_split, 0));
-        HIPCHK(small_copy(o, blk, out_bytes, hipMemcpyDeviceToHost, h->copy_stream));
+        HIPCHK(small_copy(o, blk, fb.out_bytes, hipMemcpyDeviceToHost, h->copy_stream));
         HIPCHK(hipStreamSynchronize(h->copy_stream));
     } else {
-        if (b.median_with_readback) launch_stereo_median_readback(b, o, blk, o_ur, out_bytes, s);
-        else if ((rc = frame_copy(h, o, blk, out_bytes, hipMemcpyDeviceToHost, s))) return rc;
+        if (b.median_with_readback) launch_stereo_median_readback(b, o, blk, fb.o_ur, fb.out_bytes, s);
+        else if ((rc = frame_copy(o, blk, fb.out_bytes, hipMemcpyDeviceToHost, s))) return rc;
     }
     HIPCHK(hipStreamSynchronize(s));
     in.done();
     HIPCHK(hipGetLastError());
-    const int nl = reinterpret_cast<const int*>(o + o_cnt)[0], nr = reinterpret_cast<const int*>(o + o_cnt)[1];
-    if (nl < 0 || nr < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-    if (nl > capacity || nr > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
-    memcpy(kps_left, o, (size_t)nl * sizeof(msorb_keypoint));
-    memcpy(kps_right, o + kp_bytes, (size_t)nr * sizeof(msorb_keypoint));
-    memcpy(desc_left, o + o_desc, (size_t)nl * 32);
-    memcpy(desc_right, o + o_desc + (size_t)cap * 32, (size_t)nr * 32);
-    memcpy(u_right, o + o_ur, (size_t)nl * sizeof(float));
-    memcpy(depth, o + o_dp, (size_t)nl * sizeof(float));
-    if (n_oob) *n_oob = *reinterpret_cast<const int*>(o + o_oob);
-    *n_left = nl;
-    *n_right = nr;
+    const int* const n = reinterpret_cast<const int*>(o + fb.o_cnt);   // [n_left][n_right]
+    msorb_keypoint* const kps[2] = {kps_left, kps_right};
+    uint8_t* const desc[2] = {desc_left, desc_right};
+    if (const char* why = fb.copy_out(o, n, capacity, kps, desc, u_right, depth, n_oob)) { set_last_error(why); return MSORB_E_CAPACITY; }
+    *n_left = n[0];
+    *n_right = n[1];
     return MSORB_OK;
 }
 
@@ -1585,23 +1448,21 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
     for (msorb_extractor* h : {R, L}) {
         HIPCHK(hipSetDevice(h->device));
         if ((rc = ensure_geometry(h, rows, cols))) return rc;
-        if (!h->device_quadtree) { set_last_error("msorb_extract_stereo_split needs the device pipeline"); return MSORB_E_INVALID; }
+        if (!device_pipeline(h)) { set_last_error("msorb_extract_stereo_split needs the device pipeline"); return MSORB_E_INVALID; }   // (the selection is known once the geometry is)
         if ((rc = ensure_batch(h, 1))) return rc;
         if ((rc = h->h_img_pin.ensure((size_t)h->G.lv[0].pitch * rows))) return rc;
     }
     const FrameGeom& g = L->G;
     const LevelGeom& g0 = g.lv[0];
-    const size_t plane = (size_t)g0.pitch * rows;
     if ((size_t)(2 * rows + 1) * sizeof(int) > 60000) { set_last_error("image too tall for the stereo row table"); return MSORB_E_INVALID; }
     float smax = 0;
     for (int l = 0; l < g.nlevels; l++) smax = std::max(smax, L->scales.scale[l]);
     const int row_cap = cap * ((int)std::ceil(4.0f * smax) + 3);
-    // left device: one block for everything that travels back: [kps 2*cap][desc 2*cap*32][u_right cap][depth cap][n_oob][n_left][n_right]
-    const size_t kp_bytes = (size_t)cap * sizeof(msorb_keypoint);
-    const size_t o_desc = 2 * kp_bytes, o_ur = o_desc + (size_t)2 * cap * 32, o_dp = o_ur + (size_t)cap * 4,
-                 o_oob = o_dp + (size_t)cap * 4, o_cnt = o_oob + 4, out_bytes = o_oob + 16;
+    // left device: one block for everything that travels back (FrameBlock)
+    const FrameBlock fb(cap, /*stereo=*/true);
+    const size_t kp_bytes = fb.kp_bytes;
     HIPCHK(hipSetDevice(L->device));
-    if ((rc = L->d_st_block.ensure(out_bytes)) || (rc = L->h_out_pin.ensure(out_bytes)) || (rc = L->d_st_sad.ensure(cap)) ||
+    if ((rc = L->d_st_block.ensure(fb.out_bytes)) || (rc = L->h_out_pin.ensure(fb.out_bytes)) || (rc = L->d_st_sad.ensure(cap)) ||
         (rc = L->d_st_rows.ensure((size_t)rows + 1)) || (rc = L->d_st_list.ensure((size_t)row_cap * 2)) ||
         (rc = L->d_gather_pyr.ensure(g.pyramid_bytes + 256)) || (rc = L->d_gather_cnt.ensure(4)))
         return rc;
@@ -1638,32 +1499,26 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
         HIPCHK(hipSetDevice(L->device));
         if ((rc = L->h_gather.ensure(g_total))) return rc;
     }
-    int counts[1] = {0}, mono[1] = {0};
     // ---- right eye: upload + chain on device B (enqueued first: the join waits for it)
     HIPCHK(hipSetDevice(R->device));
     DirectInputs in_r, in_l;   // each eye is read in place by its own handle's device (portable pinning: one block, every device)
-    if (in_r.admit(R, 0, right, rows, cols, stride_right)) {
-        R->in_stats.images_direct++;
-        in_r.upload(1, R->d_pyr.p + R->G.lv[0].plane_off, 0, g0.pitch, rows, cols, R->stream);
-    } else {
-        for (int y = 0; y < rows; y++) memcpy(R->h_img_pin.p + (size_t)y * g0.pitch, right + (size_t)y * stride_right, cols);
-        HIPCHK(hipMemcpyAsync(R->d_pyr.p + R->G.lv[0].plane_off, R->h_img_pin.p, plane, hipMemcpyHostToDevice, R->stream));
-        R->in_stats.images_staged++;
-        R->in_stats.bytes_staged += (uint64_t)rows * cols;
-    }
-    R->in_stats.upload_launches++;
+    const int plane0 = 0;
+    const uint8_t* host_l0[2];
+    PipelineCall call;
+    call.capacity = cap;
+    call.defer_sync = call.skip_count_copies = true;
     {
-        LevelView l0{R->d_pyr.p + R->G.lv[0].plane_off, R->G.pyramid_bytes, g0.pitch, cols, rows};
-        R->defer_sync = R->skip_count_copies = true;
-        rc = run_pipeline(R, l0, 1, 0, 0, reinterpret_cast<msorb_keypoint*>(R->d_out1.p), R->d_out1.p + kp_bytes, cap, counts, mono);
-        R->defer_sync = R->skip_count_copies = false;
-        if (rc) return rc;
+        const LevelView l0{R->d_pyr.p + R->G.lv[0].plane_off, R->G.pyramid_bytes, g0.pitch, cols, rows};
+        if ((rc = in_r.level0(R, 1, &right, &stride_right, 0, &plane0, rows, cols, R->d_pyr.p + R->G.lv[0].plane_off, 0, /*by_memcpy=*/true, R->stream, host_l0)))
+            return rc;
+        call.d_kps = reinterpret_cast<msorb_keypoint*>(R->d_out1.p); call.d_desc = R->d_out1.p + kp_bytes;
+        if ((rc = run_pipeline(R, l0, 1, call))) return rc;
     }
     uint8_t* const blk = L->d_st_block.p;
     // gather onto device A, on B's stream behind its chain
     if (peer) {
         HIPCHK(hipMemcpyPeerAsync(blk + kp_bytes, L->device, R->d_out1.p, R->device, kp_bytes, R->stream));
-        HIPCHK(hipMemcpyPeerAsync(blk + o_desc + (size_t)cap * 32, L->device, R->d_out1.p + kp_bytes, R->device, (size_t)cap * 32, R->stream));
+        HIPCHK(hipMemcpyPeerAsync(blk + fb.o_descs(1), L->device, R->d_out1.p + kp_bytes, R->device, (size_t)cap * 32, R->stream));
         HIPCHK(hipMemcpyPeerAsync(L->d_gather_cnt.p, L->device, R->d_sel_count.p, R->device, sizeof(int), R->stream));
         HIPCHK(hipMemcpyPeerAsync(L->d_gather_pyr.p, L->device, R->d_pyr.p, R->device, g.pyramid_bytes, R->stream));
     } else {
@@ -1676,76 +1531,38 @@ int msorb_extract_stereo_split(msorb_extractor* L, msorb_extractor* R, const uin
     // ---- left eye: upload + chain on device A
     HIPCHK(hipSetDevice(L->device));
     hipStream_t s = L->stream;
-    if (in_l.admit(L, 0, left, rows, cols, stride_left)) {
-        L->in_stats.images_direct++;
-        in_l.upload(1, L->d_pyr.p + g0.plane_off, 0, g0.pitch, rows, cols, s);
-    } else {
-        for (int y = 0; y < rows; y++) memcpy(L->h_img_pin.p + (size_t)y * g0.pitch, left + (size_t)y * stride_left, cols);
-        HIPCHK(hipMemcpyAsync(L->d_pyr.p + g0.plane_off, L->h_img_pin.p, plane, hipMemcpyHostToDevice, s));
-        L->in_stats.images_staged++;
-        L->in_stats.bytes_staged += (uint64_t)rows * cols;
-    }
-    L->in_stats.upload_launches++;
     // (n_oob is zeroed by the row-table kernel of launch_stereo_match_batch)
     {
-        LevelView l0{L->d_pyr.p + g0.plane_off, g.pyramid_bytes, g0.pitch, cols, rows};
-        L->defer_sync = L->skip_count_copies = true;
-        rc = run_pipeline(L, l0, 1, 0, 0, reinterpret_cast<msorb_keypoint*>(blk), blk + o_desc, cap, counts, mono);
-        L->defer_sync = L->skip_count_copies = false;
-        if (rc) return rc;
+        const LevelView l0{L->d_pyr.p + g0.plane_off, g.pyramid_bytes, g0.pitch, cols, rows};
+        if ((rc = in_l.level0(L, 1, &left, &stride_left, 0, &plane0, rows, cols, L->d_pyr.p + g0.plane_off, 0, /*by_memcpy=*/true, s, host_l0))) return rc;
+        call.d_kps = reinterpret_cast<msorb_keypoint*>(blk); call.d_desc = blk + fb.o_desc;
+        if ((rc = run_pipeline(L, l0, 1, call))) return rc;
     }
     // ---- join (Frame.cc:126-127) + ComputeStereoMatches on device A
     HIPCHK(hipStreamWaitEvent(s, R->ev_split, 0));
     if (!peer) {   // second half of the staged gather: pinned block -> device A, behind the event
         const uint8_t* hg = L->h_gather.p;
         HIPCHK(hipMemcpyAsync(blk + kp_bytes, hg + g_kp, kp_bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(blk + o_desc + (size_t)cap * 32, hg + g_desc, (size_t)cap * 32, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(blk + fb.o_descs(1), hg + g_desc, (size_t)cap * 32, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(L->d_gather_cnt.p, hg + g_cnt, sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(L->d_gather_pyr.p, hg + g_pyr, g.pyramid_bytes, hipMemcpyHostToDevice, s));
     }
-    StereoBatchArgs b{};
+    StereoBatchArgs b = stereo_frame_args(L, fb, blk, make_view(L, L->d_gather_pyr.p, nullptr), L->d_gather_cnt.p, rows, mb, mbf);
     b.pair_step = 1;
-    b.A.kpL = reinterpret_cast<msorb_keypoint*>(blk);
-    b.A.kpR = b.A.kpL + cap;
-    b.A.descL = blk + o_desc;
-    b.A.descR = b.A.descL + (size_t)cap * 32;
-    b.countsL = L->d_sel_count.p;
-    b.countsR = L->d_gather_cnt.p;
-    b.A.rows0 = rows;
-    for (int l = 0; l < g.nlevels; l++) {
-        const LevelView& v = L->last_pyr.lv[l];
-        b.A.pyrL[l] = v.base;
-        b.A.pyrR[l] = L->d_gather_pyr.p + g.lv[l].plane_off;
-        b.A.pitchL[l] = v.pitch; b.A.pitchR[l] = g.lv[l].pitch;
-        b.A.rows[l] = v.h; b.A.cols[l] = v.w;
-        b.A.scale[l] = L->scales.scale[l]; b.A.inv_scale[l] = L->P.inv_scale[l];
-        b.img_strideL[l] = v.img_stride; b.img_strideR[l] = g.pyramid_bytes;
-    }
-    b.A.mb = mb; b.A.mbf = mbf;
-    b.A.u_right = reinterpret_cast<float*>(blk + o_ur); b.A.depth = reinterpret_cast<float*>(blk + o_dp);
-    b.A.sad = L->d_st_sad.p; b.A.n_oob = reinterpret_cast<int*>(blk + o_oob);
-    b.capacity = cap;
     b.row_begin = L->d_st_rows.p; b.row_list = reinterpret_cast<int2*>(L->d_st_list.p); b.row_cap = row_cap;
-    b.counts_out = reinterpret_cast<int*>(blk + o_cnt);
     launch_stereo_match_batch(b, 1, cap, s);
     uint8_t* o = L->h_out_pin.p;
-    HIPCHK(hipMemcpyAsync(o, blk, out_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(o, blk, fb.out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));   // (the left stream waited for the right eye's event: both chains are done)
     in_l.done();
     in_r.done();
     HIPCHK(hipGetLastError());
-    const int nl = reinterpret_cast<const int*>(o + o_cnt)[0], nr = reinterpret_cast<const int*>(o + o_cnt)[1];
-    if (nl < 0 || nr < 0) { set_last_error("keypoint capacity exceeded"); return MSORB_E_CAPACITY; }
-    if (nl > capacity || nr > capacity) { set_last_error("caller capacity too small"); return MSORB_E_CAPACITY; }
-    memcpy(kps_left, o, (size_t)nl * sizeof(msorb_keypoint));
-    memcpy(kps_right, o + kp_bytes, (size_t)nr * sizeof(msorb_keypoint));
-    memcpy(desc_left, o + o_desc, (size_t)nl * 32);
-    memcpy(desc_right, o + o_desc + (size_t)cap * 32, (size_t)nr * 32);
-    memcpy(u_right, o + o_ur, (size_t)nl * sizeof(float));
-    memcpy(depth, o + o_dp, (size_t)nl * sizeof(float));
-    if (n_oob) *n_oob = *reinterpret_cast<const int*>(o + o_oob);
-    *n_left = nl;
-    *n_right = nr;
+    const int* const n = reinterpret_cast<const int*>(o + fb.o_cnt);   // [n_left][n_right]
+    msorb_keypoint* const kps[2] = {kps_left, kps_right};
+    uint8_t* const desc[2] = {desc_left, desc_right};
+    if (const char* why = fb.copy_out(o, n, capacity, kps, desc, u_right, depth, n_oob)) { set_last_error(why); return MSORB_E_CAPACITY; }
+    *n_left = n[0];
+    *n_right = n[1];
     return MSORB_OK;
 }
 
