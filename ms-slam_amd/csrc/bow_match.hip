@@ -9,38 +9,33 @@
 // spread over the lanes (position p = chunk*64 + lane, chunk 0's descriptors stay in registers), the node's queries
 // are visited in list order, each one a wave-wide masked top-2 (key = dist<<20 | position, so the minimum is the
 // first strict minimum of the reference's scan), the claim is one bit in LDS.  The rotation histogram and
-// ComputeThreeMaxima (:340-353, :396-418) are replayed on the host in the reference's visiting order.
+// ComputeThreeMaxima (:340-353, :396-418) run on the host for the per-call entries (bow_pairs.h), on the device for resident KeyFrames.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <iterator>
-#include <map>
 #include <mutex>
 #include <shared_mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/msorb.h"
+#include "block_trip.h"
+#include "bow_pairs.h"
 #include "hip_host.h"
 #include "matcher_device.h"
 #include "matcher_rules.h"
 #include "store_arena.h"
 
-namespace msorb {
-// pinned host <-> device on a stream by the copy kernel (orb_kernels.hip; hipMemcpyAsync for unaligned pointers / MSORB_FRAME_COPIES=sdma):
-// a block of 100-300 KB is across before an SDMA copy has started
-hipError_t small_copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s);
-}
 using msorb::set_last_error;
 using msorb::kHistoLength;
-using msorb::rotation_bin;
 using msorb::ThreadScratch;
-using msorb::up16;
+using msorb::BlockLayout;
+using msorb::BlockTrip;
+using msorb::round_trip;
+using msorb::FeatVec;
+using msorb::check_feature_vector;
 
 namespace {
 
@@ -333,223 +328,186 @@ __global__ __launch_bounds__(256) void pair_histogram_kernel(const PairPost* __r
     if (t == 0) nmatches[blockIdx.x] = total;
 }
 
-struct FeatVec {  // DBoW2::FeatureVector as CSR
-    int nodes;
-    const int *node, *begin, *feat;
-};
-struct Common { int r1, r2; };  // rows of the two vectors holding the same node id
+// ------------------------------------------------------------------------------------------------------------------
+// Host side.  Every entry goes through the same four stages: validate its pairs, walk their FeatureVectors into
+// (pair, common node) items (NodeWork), lay out and stage one pinned block (BlockLayout), run it through the stream
+// (round_trip).  What is plain C++ about two FeatureVectors and a match list is in bow_pairs.h.
+// ------------------------------------------------------------------------------------------------------------------
 
-bool check_feature_vector(int n, const FeatVec& v, std::vector<uint8_t>& seen) {
-    if (v.nodes < 0 || (v.nodes > 0 && (!v.node || !v.begin))) return false;
-    if (v.nodes == 0) return true;
-    if (v.begin[0] < 0) return false;
-    for (int r = 0; r < v.nodes; r++) {
-        if (v.begin[r + 1] < v.begin[r]) return false;
-        if (r > 0 && v.node[r] <= v.node[r - 1]) return false;
-    }
-    if (v.begin[v.nodes] > v.begin[0] && !v.feat) return false;
-    seen.assign((size_t)n, 0);
-    for (int k = v.begin[0]; k < v.begin[v.nodes]; k++) {
-        const int i = v.feat[k];
-        if (i < 0 || i >= n || seen[i]) return false;
-        seen[i] = 1;
-    }
-    return true;
-}
+// A set of a pair has its FeatureVector lists either in a device array that holds the whole vector (a resident KeyFrame, the
+// frame block of a call: feat = where the vector's feat[0] sits in that array) or among the lists this call stages, the common
+// nodes' lists one behind the other (kStaged).
+constexpr int kStaged = INT32_MIN;
 
-// the merge walk of :239-243 / :385-392: nodes both vectors hold (with non-empty lists), ascending
-bool merge_walk(const FeatVec& a, const FeatVec& b, std::vector<Common>& out, size_t& totf1, size_t& totf2, int& max_chunks) {
-    int i = 0, j = 0;
-    while (i < a.nodes && j < b.nodes) {
-        if (a.node[i] == b.node[j]) {
-            const int l1 = a.begin[i + 1] - a.begin[i], l2 = b.begin[j + 1] - b.begin[j];
-            if (l1 > 0 && l2 > 0) {
-                if (l2 >= (1 << 20)) return false;
-                out.push_back({i, j});
-                totf1 += (size_t)l1;
-                totf2 += (size_t)l2;
-                max_chunks = std::max(max_chunks, (l2 + 63) >> 6);
-            }
-            i++; j++;
-        } else if (a.node[i] < b.node[j]) i++;
-        else j++;
-    }
-    return true;
-}
+struct NodeWork {   // the items of one call
+    std::vector<BowItem> items;
+    std::vector<std::pair<const int*, const int*>> lists;   // per item: its staged query / train list on the host
+    size_t totf1 = 0, totf2 = 0;                            // staged list entries
+    int max_chunks = 1;
 
-// copies the common nodes' lists of one pair behind k1 / k2 and appends their items
-void stage_lists(const FeatVec& a, const FeatVec& b, const std::vector<Common>& common, int pi, size_t r1, size_t r2, int* f1,
-                 int* f2, size_t& k1, size_t& k2, BowItem* items, size_t& ni) {
-    for (const Common& c : common) {
-        const int l1 = a.begin[c.r1 + 1] - a.begin[c.r1], l2 = b.begin[c.r2 + 1] - b.begin[c.r2];
-        std::memcpy(f1 + k1, a.feat + a.begin[c.r1], (size_t)l1 * 4);
-        std::memcpy(f2 + k2, b.feat + b.begin[c.r2], (size_t)l2 * 4);
-        items[ni++] = BowItem{(int)r1, (int)r2, (int)k1, l1, (int)k2, l2, pi, (int)r1, (int)r2};
-        k1 += (size_t)l1;
-        k2 += (size_t)l2;
+    // appends the items of pair pi (BowItem: base1 / base2, m1 / m2); false: a train list too long for the kernels
+    bool add(const FeatVec& a, const FeatVec& b, int pi, int base1, int base2, int m1, int m2, int feat1 = kStaged, int feat2 = kStaged) {
+        return msorb::for_each_common_node(a, b, max_chunks, [&](int r1, int r2, int l1, int l2) {
+            const int b1 = feat1 == kStaged ? (int)totf1 : feat1 + a.begin[r1], b2 = feat2 == kStaged ? (int)totf2 : feat2 + b.begin[r2];
+            items.push_back(BowItem{base1, base2, b1, l1, b2, l2, pi, m1, m2});
+            lists.push_back({feat1 == kStaged ? a.feat + a.begin[r1] : nullptr, feat2 == kStaged ? b.feat + b.begin[r2] : nullptr});
+            if (feat1 == kStaged) totf1 += (size_t)l1;
+            if (feat2 == kStaged) totf2 += (size_t)l2;
+        });
     }
-}
-
-// The rotation histogram in the reference's visiting order (:340-353 / :1342-1354) and the ComputeThreeMaxima filter
-// (:396-418 / :1360-1381).  m = the kernel's raw matches of this pair; angle(i1, i2) = the two keypoint angles.
-template <class Angles>
-int replay_histogram(const FeatVec& a, const std::vector<Common>& common, const int* m, int check_orientation, Angles angle,
-                     int* match12) {
-    // rotHist[bin] only decides which matches survive (the three fullest bins, ComputeThreeMaxima): a bin index per match
-    // and 30 counters replace the reference's 30 vectors — this runs once per pair on the calling thread, and with the
-    // vectors it cost 23 us per pair, seven times the whole device part of a 32-pair batch
-    static thread_local std::vector<int8_t> bin_of;
-    int sizes[kHistoLength] = {0};
-    int nm = 0, n_feat = 0;
-    for (const Common& c : common) n_feat = std::max(n_feat, a.begin[c.r1 + 1]);
-    if (check_orientation && (int)bin_of.size() < n_feat) bin_of.resize(n_feat);
-    for (const Common& c : common)
-        for (int k = a.begin[c.r1]; k < a.begin[c.r1 + 1]; k++) {
-            const int idx1 = a.feat[k], idx2 = m[idx1];
-            if (idx2 < 0) continue;
-            match12[idx1] = idx2;
-            nm++;
-            if (check_orientation) {
-                float a1, a2;
-                angle(idx1, idx2, a1, a2);
-                const int bin = rotation_bin(a1, a2);
-                if (bin >= 0) { bin_of[k] = (int8_t)bin; sizes[bin]++; }
-                else { match12[idx1] = -1; nm--; }  // NaN / out-of-range angle: the reference asserts
-            }
+    size_t item_bytes() const { return items.size() * sizeof(BowItem); }
+    void stage(void* h_items, int* f1, int* f2) const {
+        std::memcpy(h_items, items.data(), item_bytes());
+        for (size_t i = 0; i < items.size(); i++) {
+            if (lists[i].first) std::memcpy(f1 + items[i].b1, lists[i].first, (size_t)items[i].n1l * 4);
+            if (lists[i].second) std::memcpy(f2 + items[i].b2, lists[i].second, (size_t)items[i].n2l * 4);
         }
-    if (check_orientation) {
-        int ind[3];
-        msorb_three_maxima(sizes, kHistoLength, ind);
-        for (const Common& c : common)
-            for (int k = a.begin[c.r1]; k < a.begin[c.r1 + 1]; k++) {
-                const int idx1 = a.feat[k];
-                if (match12[idx1] < 0) continue;
-                const int bin = bin_of[k];
-                if (bin != ind[0] && bin != ind[1] && bin != ind[2]) { match12[idx1] = -1; nm--; }
-            }
     }
+    dim3 grid() const { return dim3((unsigned)items.size()); }
+    size_t lds() const { return (size_t)max_chunks * 8; }   // one bit per train of the longest list
+};
+
+template <class P> FeatVec fv1_of(const P& p) { return FeatVec{p.fv1_nodes, p.fv1_node, p.fv1_begin, p.fv1_feat}; }
+template <class P> FeatVec fv2_of(const P& p) { return FeatVec{p.fv2_nodes, p.fv2_node, p.fv2_begin, p.fv2_feat}; }
+
+bool check_bow_pair(const msorb_bow_pair& P, int check_orientation, bool need_match12, std::vector<uint8_t>& seen) {
+    return P.n1 >= 0 && P.n2 >= 0 && (P.match12 || !need_match12 || P.n1 == 0) && (P.n1 == 0 || (P.desc1 && P.valid1)) &&
+           (P.n2 == 0 || P.desc2) && (!check_orientation || ((P.n1 == 0 || P.angle1) && (P.n2 == 0 || P.angle2))) &&
+           check_feature_vector(P.n1, fv1_of(P), seen) && check_feature_vector(P.n2, fv2_of(P), seen);
+}
+
+void stage_flags(uint8_t* dst, const uint8_t* flags, size_t n) {   // nullptr: every feature
+    if (flags) std::memcpy(dst, flags, n);
+    else std::memset(dst, 1, n);
+}
+void stage_const(TriConst& c, const float* F12, const float* ep) {
+    std::memcpy(c.F, F12, sizeof(c.F));
+    c.ep[0] = ep[0];
+    c.ep[1] = ep[1];
+}
+
+// The inputs of the per-call SearchByBoW forms (msorb_search_by_bow, msorb_search_for_triangulation_cb): validation, walk, and the
+// regions [desc1 | desc2 | feat1 | feat2 | items | valid1 | avail2] of the block.
+struct BowCall {
+    NodeWork w;
+    size_t tot1 = 0, tot2 = 0;
+    size_t o_d1, o_d2, o_f1, o_f2, o_it, o_v1, o_a2;
+    BlockLayout L;
+
+    // validates and walks the pairs (-1 or the first bad pair), sets every match12 / match21 to -1
+    int walk(msorb_bow_pair* pairs, int n_pairs, int check_orientation) {
+        std::vector<uint8_t> seen;
+        for (int pi = 0; pi < n_pairs; pi++) {
+            msorb_bow_pair& P = pairs[pi];
+            P.nmatches = 0;
+            if (!check_bow_pair(P, check_orientation, true, seen) ||
+                !w.add(fv1_of(P), fv2_of(P), pi, (int)tot1, (int)tot2, (int)tot1, (int)tot2)) return pi;
+            tot1 += (size_t)P.n1;
+            tot2 += (size_t)P.n2;
+        }
+        for (int pi = 0; pi < n_pairs; pi++) {
+            std::fill_n(pairs[pi].match12, pairs[pi].n1, -1);
+            if (pairs[pi].match21) std::fill_n(pairs[pi].match21, pairs[pi].n2, -1);
+        }
+        return -1;
+    }
+    void plan() {
+        o_d1 = L.take(tot1 * 32); o_d2 = L.take(tot2 * 32); o_f1 = L.take(w.totf1 * 4); o_f2 = L.take(w.totf2 * 4);
+        o_it = L.take(w.item_bytes()); o_v1 = L.take(tot1); o_a2 = L.take(tot2);
+        L.outputs_begin();
+    }
+    void stage(uint8_t* h, const msorb_bow_pair* pairs, int n_pairs) const {
+        size_t r1 = 0, r2 = 0;
+        for (int pi = 0; pi < n_pairs; pi++) {
+            const msorb_bow_pair& P = pairs[pi];
+            if (P.n1) { std::memcpy(h + o_d1 + r1 * 32, P.desc1, (size_t)P.n1 * 32); std::memcpy(h + o_v1 + r1, P.valid1, (size_t)P.n1); }
+            if (P.n2) { std::memcpy(h + o_d2 + r2 * 32, P.desc2, (size_t)P.n2 * 32); stage_flags(h + o_a2 + r2, P.avail2, (size_t)P.n2); }
+            r1 += (size_t)P.n1;
+            r2 += (size_t)P.n2;
+        }
+        w.stage(h + o_it, (int*)(h + o_f1), (int*)(h + o_f2));
+    }
+};
+
+// The raw matches of a call are read feature by feature: out of the pinned block first (one streaming copy) — scattered 4-byte
+// reads of pinned host memory cost ~10 ns each, 0.8 ms for a 32-pair batch.
+const int* out_of_pinned(const void* pinned, size_t n) {
+    static thread_local std::vector<int> m_local;
+    m_local.resize(n);
+    std::memcpy(m_local.data(), pinned, n * 4);
+    return m_local.data();
+}
+
+// a pair's raw matches (the kernel's; -1 where no feature was matched or visited) through the rotation filter into match12 / match21;
+// angles(i1, i2, a1, a2) = the angles of the two keypoints
+template <class Angles>
+int finish_pair(int n1, const int* raw, int check_orientation, int* match12, int* match21, Angles angles) {
+    if (n1) std::memcpy(match12, raw, (size_t)n1 * 4);
+    const int nm = msorb::rotation_filter(n1, check_orientation, match12, [&](int i) { return raw[i] >= 0 ? i : -1; },
+                                          [&](int i, float& a1, float& a2) { angles(i, raw[i], a1, a2); });
+    if (match21)
+        for (int i = 0; i < n1; i++)
+            if (match12[i] >= 0) match21[match12[i]] = i;
     return nm;
 }
-
-int hip_fail(ThreadScratch& scr, const char* what, hipError_t e) {
-    set_last_error(std::string(what) + ": " + hipGetErrorString(e));
-    scr.release();
-    return MSORB_E_HIP;
+// (a per-call SearchByBoW pair keeps its angles in two arrays)
+int finish_bow_pair(msorb_bow_pair& P, const int* raw, int check_orientation) {
+    return finish_pair(P.n1, raw, check_orientation, P.match12, P.match21,
+                       [&](int i1, int i2, float& a1, float& a2) { a1 = P.angle1[i1]; a2 = P.angle2[i2]; });
 }
 
-}  // namespace
+void launch_bow(hipStream_t s, const NodeWork& w, const uint8_t* d_items, const uint4* desc1, const uint4* desc2, const uint8_t* valid1,
+                const uint8_t* avail2, const int* feat1, const int* feat2, int th_low, int flags, float nnratio, uint8_t* match12,
+                uint8_t* best1 = nullptr) {
+    hipLaunchKernelGGL(bow_match_kernel, w.grid(), dim3(64), w.lds(), s, (const BowItem*)d_items, desc1, desc2, valid1, avail2, feat1,
+                       feat2, th_low, flags, nnratio, (int*)match12, (int*)best1);
+}
 
-namespace {
 // msorb_search_by_bow's body.  flags: bit 0 inclusive, bit 1 no ratio test; best1 (optional): per pair the kernel's best1 output.
 int search_by_bow_impl(int device, msorb_bow_pair* pairs, int n_pairs, int th_low, int flags, float nnratio, int check_orientation,
                        float* elapsed_ms, std::vector<std::vector<int>>* best1) {
-    const int inclusive = flags;   // (passed through to the kernel, which reads the bits)
     if (best1) { best1->assign(n_pairs, {}); for (int pi = 0; pi < n_pairs; pi++) (*best1)[pi].assign(std::max(pairs[pi].n1, 0), 256); }
     if (elapsed_ms) *elapsed_ms = 0;
     if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return MSORB_E_INVALID;
     if (n_pairs == 0) return MSORB_OK;
-    std::vector<std::vector<Common>> common(n_pairs);
-    std::vector<FeatVec> fa(n_pairs), fb(n_pairs);
-    std::vector<uint8_t> seen;
-    size_t tot1 = 0, tot2 = 0, totf1 = 0, totf2 = 0, n_items = 0;
-    int max_chunks = 1;
-    for (int pi = 0; pi < n_pairs; pi++) {
-        msorb_bow_pair& P = pairs[pi];
-        P.nmatches = 0;
-        fa[pi] = FeatVec{P.fv1_nodes, P.fv1_node, P.fv1_begin, P.fv1_feat};
-        fb[pi] = FeatVec{P.fv2_nodes, P.fv2_node, P.fv2_begin, P.fv2_feat};
-        if (P.n1 < 0 || P.n2 < 0 || (!P.match12 && P.n1 > 0) || (P.n1 > 0 && (!P.desc1 || !P.valid1)) || (P.n2 > 0 && !P.desc2) ||
-            (check_orientation && ((P.n1 > 0 && !P.angle1) || (P.n2 > 0 && !P.angle2))) ||
-            !check_feature_vector(P.n1, fa[pi], seen) || !check_feature_vector(P.n2, fb[pi], seen) ||
-            !merge_walk(fa[pi], fb[pi], common[pi], totf1, totf2, max_chunks)) {
-            set_last_error("search_by_bow: pair " + std::to_string(pi) +
-                           ": bad sizes / null arrays / feature vector not ascending, out of range or with a repeated feature");
-            return MSORB_E_INVALID;
-        }
-        n_items += common[pi].size();
-        tot1 += (size_t)P.n1;
-        tot2 += (size_t)P.n2;
+    BowCall c;
+    const int bad = c.walk(pairs, n_pairs, check_orientation);
+    if (bad >= 0) {
+        set_last_error("search_by_bow: pair " + std::to_string(bad) +
+                       ": bad sizes / null arrays / feature vector not ascending, out of range or with a repeated feature");
+        return MSORB_E_INVALID;
     }
-    for (int pi = 0; pi < n_pairs; pi++) {
-        msorb_bow_pair& P = pairs[pi];
-        for (int i = 0; i < P.n1; i++) P.match12[i] = -1;
-        if (P.match21) for (int j = 0; j < P.n2; j++) P.match21[j] = -1;
-    }
-    if (n_items == 0) return MSORB_OK;
-    if (tot1 > (size_t)INT32_MAX / 2 || tot2 > (size_t)INT32_MAX / 2) return MSORB_E_INVALID;
+    if (c.w.items.empty()) return MSORB_OK;
+    const size_t tot1 = c.tot1;
+    if (tot1 > (size_t)INT32_MAX / 2 || c.tot2 > (size_t)INT32_MAX / 2) return MSORB_E_INVALID;
     if (int rc = msorb::require_device(device)) return rc;
-    // ---- staging: [desc1 | desc2 | feat1 | feat2 | items | valid1 | avail2] in, [match12] out ----
-    const size_t o_d1 = 0, o_d2 = o_d1 + tot1 * 32, o_f1 = o_d2 + tot2 * 32, o_f2 = o_f1 + up16(totf1 * 4),
-                 o_it = o_f2 + up16(totf2 * 4), o_v1 = o_it + up16(n_items * sizeof(BowItem)), o_a2 = o_v1 + up16(tot1),
-                 in_bytes = o_a2 + up16(tot2), o_m = in_bytes, o_b = o_m + up16(tot1 * 4), total = o_b + (best1 ? up16(tot1 * 4) : 0);
+    c.plan();   // [match12 | best1] out
+    const size_t o_m = c.L.take(tot1 * 4), o_b = best1 ? c.L.take(tot1 * 4) : c.L.end;
     static thread_local ThreadScratch scr(true, 2);
-    if (int rc = scr.acquire(device, total, total)) return rc;
-    {
-        uint8_t* h = scr.h.p;
-        size_t r1 = 0, r2 = 0, k1 = 0, k2 = 0, ni = 0;
-        for (int pi = 0; pi < n_pairs; pi++) {
-            const msorb_bow_pair& P = pairs[pi];
-            if (P.n1) std::memcpy(h + o_d1 + r1 * 32, P.desc1, (size_t)P.n1 * 32);
-            if (P.n2) std::memcpy(h + o_d2 + r2 * 32, P.desc2, (size_t)P.n2 * 32);
-            if (P.n1) std::memcpy(h + o_v1 + r1, P.valid1, (size_t)P.n1);
-            if (P.n2) {
-                if (P.avail2) std::memcpy(h + o_a2 + r2, P.avail2, (size_t)P.n2);
-                else std::memset(h + o_a2 + r2, 1, (size_t)P.n2);
+    if (int rc = scr.acquire(device, c.L.end, c.L.end)) return rc;
+    uint8_t *h = scr.h.p, *d = scr.d.p;
+    c.stage(h, pairs, n_pairs);
+    const BlockTrip trip{d, h, c.L.in_bytes, d + o_m, tot1 * 4, h + o_m, d + o_m, (best1 ? o_b - o_m : 0) + tot1 * 4};
+    if (int rc = round_trip(scr, "search_by_bow", trip, elapsed_ms, [&](hipStream_t s) {
+            launch_bow(s, c.w, d + c.o_it, (const uint4*)(d + c.o_d1), (const uint4*)(d + c.o_d2), d + c.o_v1, d + c.o_a2,
+                       (const int*)(d + c.o_f1), (const int*)(d + c.o_f2), th_low, flags, nnratio, d + o_m, best1 ? d + o_b : nullptr);
+        })) return rc;
+    if (best1)   // written for the visited features only (the valid ones of the common nodes): the others keep 256
+        for (size_t k = 0; k < c.w.items.size(); k++) {
+            const BowItem& it = c.w.items[k];
+            for (int q = 0; q < it.n1l; q++) {
+                const int i1 = c.w.lists[k].first[q];
+                if (pairs[it.pair].valid1[i1]) (*best1)[it.pair][i1] = ((const int*)(h + o_b))[it.m1 + i1];
             }
-            stage_lists(fa[pi], fb[pi], common[pi], pi, r1, r2, (int*)(h + o_f1), (int*)(h + o_f2), k1, k2,
-                        (BowItem*)(h + o_it), ni);
-            r1 += (size_t)P.n1;
-            r2 += (size_t)P.n2;
         }
-    }
-    hipStream_t s = scr.s;
-    uint8_t* d = scr.d.p;
-    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, tot1 * 4, s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(bow_match_kernel, dim3((unsigned)n_items), dim3(64), (size_t)max_chunks * 8, s,
-                           (const BowItem*)(d + o_it), (const uint4*)(d + o_d1), (const uint4*)(d + o_d2),
-                           (const uint8_t*)(d + o_v1), (const uint8_t*)(d + o_a2), (const int*)(d + o_f1),
-                           (const int*)(d + o_f2), th_low, inclusive, nnratio, (int*)(d + o_m), best1 ? (int*)(d + o_b) : nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, (best1 ? o_b - o_m : 0) + tot1 * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
-    if (e != hipSuccess) return hip_fail(scr, "search_by_bow", e);
-    if (best1) {   // (features of nodes the two vectors do not share were never visited: they keep 256)
-        size_t r = 0;
-        for (int pi = 0; pi < n_pairs; pi++) {
-            const int* b = (const int*)(scr.h.p + o_b) + r;
-            for (const Common& c : common[pi])
-                for (int k = fa[pi].begin[c.r1]; k < fa[pi].begin[c.r1 + 1]; k++) {
-                    const int i1 = fa[pi].feat[k];
-                    if (pairs[pi].valid1[i1]) (*best1)[pi][i1] = b[i1];
-                }
-            r += (size_t)pairs[pi].n1;
-        }
-    }
-    // the raw matches are read feature by feature below: out of the pinned block first (one streaming copy) — scattered 4-byte
-    // reads of pinned host memory cost ~10 ns each, 0.8 ms for a 32-pair batch
-    static thread_local std::vector<int> m_local;
-    m_local.resize(tot1);
-    std::memcpy(m_local.data(), scr.h.p + o_m, tot1 * 4);
-    const int* m_all = m_local.data();
-    size_t r1 = 0;
+    const int* raw = out_of_pinned(h + o_m, tot1);
     for (int pi = 0; pi < n_pairs; pi++) {
-        msorb_bow_pair& P = pairs[pi];
-        P.nmatches = replay_histogram(fa[pi], common[pi], m_all + r1, check_orientation,
-                                      [&](int i1, int i2, float& a1, float& a2) { a1 = P.angle1[i1]; a2 = P.angle2[i2]; },
-                                      P.match12);
-        r1 += (size_t)P.n1;
-        if (P.match21)
-            for (int i = 0; i < P.n1; i++)
-                if (P.match12[i] >= 0) P.match21[P.match12[i]] = i;
+        pairs[pi].nmatches = finish_bow_pair(pairs[pi], raw, check_orientation);
+        raw += pairs[pi].n1;
     }
     return MSORB_OK;
 }
+
 }  // namespace
 
 extern "C" int msorb_search_by_bow(int device, msorb_bow_pair* pairs, int n_pairs, int th_low, int inclusive, float nnratio,
@@ -563,296 +521,174 @@ extern "C" int msorb_search_by_bow(int device, msorb_bow_pair* pairs, int n_pair
 // taken as on a one-camera frame (<= TH_LOW, ratio test); the right match — only looked at when the LEFT best distance was <= TH_LOW,
 // whatever the ratio test said (:330 encloses :357) — is taken at <= TH_LOW without a ratio test (`|| true`).  Left and right claims
 // touch disjoint features, so the two arms are two runs of the node kernel: the left one also reports every KeyFrame feature's
-// left best distance, which gates the right one.  Both feed ONE rotation histogram, per KeyFrame feature the left entry first.
+// left best distance, which gates the right one.  Both feed ONE rotation histogram (:338-353, :361-378, :396-418).
 //   pair: as msorb_search_by_bow (set 1 = the KeyFrame, set 2 = the frame's n2 = N features, left camera first; avail2 unused);
 //   match21[n2]: the KeyFrame feature matched to frame feature j (vpMapPointMatches[j] = its map point), -1 none.
 extern "C" int msorb_search_by_bow_rig(int device, msorb_bow_pair* pair, int n_left, int th_low, float nnratio, int check_orientation) {
-    if (!pair || n_left < 0 || n_left > pair->n2 || !pair->match21 || (pair->n1 > 0 && !pair->valid1)) return MSORB_E_INVALID;
+    if (!pair || n_left < 0 || n_left > pair->n2 || !pair->match21) return MSORB_E_INVALID;
     msorb_bow_pair& P = *pair;
     P.nmatches = 0;
-    FeatVec fb{P.fv2_nodes, P.fv2_node, P.fv2_begin, P.fv2_feat}, fa{P.fv1_nodes, P.fv1_node, P.fv1_begin, P.fv1_feat};
     std::vector<uint8_t> seen;
-    if (P.n1 < 0 || P.n2 < 0 || !check_feature_vector(P.n2, fb, seen) || !check_feature_vector(P.n1, fa, seen) ||
-        (check_orientation && ((P.n1 > 0 && !P.angle1) || (P.n2 > 0 && !P.angle2)))) {
+    if (!check_bow_pair(P, check_orientation, false, seen)) {
         set_last_error("search_by_bow_rig: bad sizes / null arrays / feature vector not ascending, out of range or with a repeated feature");
         return MSORB_E_INVALID;
     }
-    // the frame's FeatureVector split by camera (the node ids and the order inside a node stay)
-    std::vector<int> nodeL, beginL{0}, featL, nodeR, beginR{0}, featR;
-    for (int r = 0; r < fb.nodes; r++) {
-        const size_t l0 = featL.size(), r0 = featR.size();
-        for (int k = fb.begin[r]; k < fb.begin[r + 1]; k++) (fb.feat[k] < n_left ? featL : featR).push_back(fb.feat[k]);
-        if (featL.size() > l0) { nodeL.push_back(fb.node[r]); beginL.push_back((int)featL.size()); }
-        if (featR.size() > r0) { nodeR.push_back(fb.node[r]); beginR.push_back((int)featR.size()); }
-    }
-    std::vector<int> m12L(std::max(P.n1, 1), -1), m12R(std::max(P.n1, 1), -1), m21(std::max(P.n2, 1), -1);
-    msorb_bow_pair A = P;
-    A.avail2 = nullptr; A.match12 = m12L.data(); A.match21 = nullptr;
-    A.fv2_nodes = (int)nodeL.size(); A.fv2_node = nodeL.data(); A.fv2_begin = beginL.data(); A.fv2_feat = featL.data();
+    const msorb::CameraSplit cam = msorb::split_by_camera(fv2_of(P), n_left);
+    std::vector<int> m12L(std::max(P.n1, 1), -1), m12R(std::max(P.n1, 1), -1);
+    auto arm = [&](const FeatVec& fv2, const uint8_t* valid1, int* match12) {
+        msorb_bow_pair A = P;
+        A.valid1 = valid1; A.avail2 = nullptr; A.match12 = match12; A.match21 = nullptr;
+        A.fv2_nodes = fv2.nodes; A.fv2_node = fv2.node; A.fv2_begin = fv2.begin; A.fv2_feat = fv2.feat;
+        return A;
+    };
+    msorb_bow_pair A = arm(cam.left.view(), P.valid1, m12L.data());
     std::vector<std::vector<int>> best1;
     int rc = search_by_bow_impl(device, &A, 1, th_low, 1, nnratio, 0, nullptr, &best1);
     if (rc) return rc;
     std::vector<uint8_t> validR(std::max(P.n1, 1), 0);
     for (int i = 0; i < P.n1; i++) validR[i] = P.valid1[i] && best1[0][i] <= th_low;                // :330
-    msorb_bow_pair B = P;
-    B.valid1 = validR.data(); B.avail2 = nullptr; B.match12 = m12R.data(); B.match21 = nullptr;
-    B.fv2_nodes = (int)nodeR.size(); B.fv2_node = nodeR.data(); B.fv2_begin = beginR.data(); B.fv2_feat = featR.data();
+    msorb_bow_pair B = arm(cam.right.view(), validR.data(), m12R.data());
     rc = search_by_bow_impl(device, &B, 1, th_low, 1 | 2, nnratio, 0, nullptr, nullptr);
     if (rc) return rc;
-    // the rotation histogram in the reference's order: the nodes both full vectors hold, the KeyFrame's features of a node in list
-    // order, the left match of a feature before its right match (:338-353, :361-378); then ComputeThreeMaxima (:396-418)
-    for (int j = 0; j < P.n2; j++) P.match21[j] = -1;
-    std::vector<std::pair<int, int>> hist[kHistoLength];   // (frame feature, KeyFrame feature)
-    int nm = 0;
-    int i = 0, j = 0;
-    while (i < fa.nodes && j < fb.nodes) {
-        if (fa.node[i] == fb.node[j]) {
-            for (int k = fa.begin[i]; k < fa.begin[i + 1]; k++) {
-                const int i1 = fa.feat[k];
-                for (int side = 0; side < 2; side++) {
-                    const int i2 = side ? m12R[i1] : m12L[i1];
-                    if (i2 < 0) continue;
-                    P.match21[i2] = i1;
-                    nm++;
-                    if (check_orientation) {
-                        const int bin = rotation_bin(P.angle1[i1], P.angle2[i2]);
-                        if (bin >= 0) hist[bin].push_back({i2, i1});
-                        else { P.match21[i2] = -1; nm--; }
-                    }
-                }
-            }
-            i++; j++;
-        } else if (fa.node[i] < fb.node[j]) i++;
-        else j++;
-    }
-    if (check_orientation) {
-        int sizes[kHistoLength], ind[3];
-        for (int b = 0; b < kHistoLength; b++) sizes[b] = (int)hist[b].size();
-        msorb_three_maxima(sizes, kHistoLength, ind);
-        for (int b = 0; b < kHistoLength; b++)
-            if (b != ind[0] && b != ind[1] && b != ind[2])
-                for (auto& e : hist[b]) { P.match21[e.first] = -1; nm--; }
-    }
+    // two entries per KeyFrame feature, its left match and its right match, into the one histogram
+    auto partner = [&](int k) { return (k & 1 ? m12R : m12L)[k >> 1]; };
+    std::fill_n(P.match21, P.n2, -1);
+    for (int k = 0; k < 2 * P.n1; k++)
+        if (partner(k) >= 0) P.match21[partner(k)] = k >> 1;
+    P.nmatches = msorb::rotation_filter(2 * P.n1, check_orientation, P.match21, partner,
+                                        [&](int k, float& a1, float& a2) { a1 = P.angle1[k >> 1]; a2 = P.angle2[partner(k)]; });
     if (P.match12) {   // the left partner of every KeyFrame feature (the right one is in match21 only)
-        for (int k = 0; k < P.n1; k++) P.match12[k] = -1;
+        std::fill_n(P.match12, P.n1, -1);
         for (int f2 = 0; f2 < n_left; f2++) if (P.match21[f2] >= 0) P.match12[P.match21[f2]] = f2;
     }
-    P.nmatches = nm;
     return MSORB_OK;
 }
 
 // ORBmatcher::SearchForTriangulation (:1168-1402) with the geometric test of :1332 left to the caller — the form the two-camera arms
 // (:1294-1330: one of four relative poses and two camera models per candidate, KannalaBrandt8::epipolarConstrain) need, and any
 // camera model this library does not restate.  The device lists, per common node, every (query, train) within th_low among the
-// visited / eligible features (node_candidates_kernel: count, then fill); the replay below walks them in the reference's order.
-// For one query the reference scans the trains in list order, keeps `bestDist` (initially th_low) and takes a train when
-// dist <= bestDist and the test passes: the winner is the passing train of smallest distance, the LAST of equal ones — here the
-// candidates sorted by (distance, position descending), the first unclaimed one that accept() passes.  accept() is a pure
-// predicate of the two features (the reference's is: a const camera, two keypoints, a relative pose), so asking it for fewer
-// or other candidates than the reference's running-minimum scan reaches changes nothing.
+// visited / eligible features (node_candidates_kernel: count, then fill); msorb::pick_candidates replays the reference's scan over
+// them.  accept() is a pure predicate of the two features (the reference's is: a const camera, two keypoints, a relative pose), so
+// asking it for fewer or other candidates than the reference's running-minimum scan reaches changes nothing.
 extern "C" int msorb_search_for_triangulation_cb(int device, msorb_bow_pair* pair, int th_low, int check_orientation, msorb_pair_accept accept,
                                                  void* ctx) {
     if (!pair || !accept || th_low < 0) return MSORB_E_INVALID;
     msorb_bow_pair& P = *pair;
-    P.nmatches = 0;
-    FeatVec fa{P.fv1_nodes, P.fv1_node, P.fv1_begin, P.fv1_feat}, fb{P.fv2_nodes, P.fv2_node, P.fv2_begin, P.fv2_feat};
-    std::vector<Common> common;
-    std::vector<uint8_t> seen;
-    size_t totf1 = 0, totf2 = 0;
-    int max_chunks = 1;
-    if (P.n1 < 0 || P.n2 < 0 || (!P.match12 && P.n1 > 0) || (P.n1 > 0 && (!P.desc1 || !P.valid1)) || (P.n2 > 0 && !P.desc2) ||
-        (check_orientation && ((P.n1 > 0 && !P.angle1) || (P.n2 > 0 && !P.angle2))) || !check_feature_vector(P.n1, fa, seen) ||
-        !check_feature_vector(P.n2, fb, seen) || !merge_walk(fa, fb, common, totf1, totf2, max_chunks)) {
+    BowCall c;
+    if (c.walk(pair, 1, check_orientation) >= 0) {
         set_last_error("search_for_triangulation_cb: bad sizes / null arrays / feature vector not ascending, out of range or with a repeated feature");
         return MSORB_E_INVALID;
     }
-    for (int i = 0; i < P.n1; i++) P.match12[i] = -1;
-    if (P.match21) for (int j = 0; j < P.n2; j++) P.match21[j] = -1;
-    const size_t n_items = common.size(), tot1 = (size_t)P.n1, tot2 = (size_t)P.n2;
+    const size_t n_items = c.w.items.size();
     if (n_items == 0) return MSORB_OK;
     if (int rc = msorb::require_device(device)) return rc;
-    // ---- staging: [desc1 | desc2 | feat1 | feat2 | items | valid1 | avail2 | begin] in, [count] out; the lists in their own block ----
-    const size_t o_d1 = 0, o_d2 = o_d1 + tot1 * 32, o_f1 = o_d2 + tot2 * 32, o_f2 = o_f1 + up16(totf1 * 4), o_it = o_f2 + up16(totf2 * 4),
-                 o_v1 = o_it + up16(n_items * sizeof(BowItem)), o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2), o_cnt = in_bytes,
-                 o_beg = o_cnt + up16(n_items * 4), total = o_beg + up16(n_items * 4);
+    c.plan();   // [count] out, [begin] in for the second trip; the lists in their own block
+    const size_t o_cnt = c.L.take(n_items * 4), o_beg = c.L.take(n_items * 4);
     static thread_local ThreadScratch scr(true, 2), lists(true, 2);
-    if (int rc = scr.acquire(device, total, total)) return rc;
-    {
-        uint8_t* h = scr.h.p;
-        size_t k1 = 0, k2 = 0, ni = 0;
-        if (P.n1) { std::memcpy(h + o_d1, P.desc1, tot1 * 32); std::memcpy(h + o_v1, P.valid1, tot1); }
-        if (P.n2) {
-            std::memcpy(h + o_d2, P.desc2, tot2 * 32);
-            if (P.avail2) std::memcpy(h + o_a2, P.avail2, tot2);
-            else std::memset(h + o_a2, 1, tot2);
-        }
-        stage_lists(fa, fb, common, 0, 0, 0, (int*)(h + o_f1), (int*)(h + o_f2), k1, k2, (BowItem*)(h + o_it), ni);
-    }
-    hipStream_t s = scr.s;
-    uint8_t* d = scr.d.p;
-    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(node_candidates_kernel<false>, dim3((unsigned)n_items), dim3(64), 0, s, (const BowItem*)(d + o_it), (const uint4*)(d + o_d1),
-                           (const uint4*)(d + o_d2), (const uint8_t*)(d + o_v1), (const uint8_t*)(d + o_a2), (const int*)(d + o_f1),
-                           (const int*)(d + o_f2), th_low, (int*)(d + o_cnt), (const int*)nullptr, (int4*)nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_cnt, d + o_cnt, n_items * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_cb", e);
-    const int* cnt = (const int*)(scr.h.p + o_cnt);
-    int* beg = (int*)(scr.h.p + o_beg);
+    if (int rc = scr.acquire(device, c.L.end, c.L.end)) return rc;
+    uint8_t *h = scr.h.p, *d = scr.d.p;
+    c.stage(h, pair, 1);
+    auto launch = [&](auto kernel, hipStream_t s) {
+        hipLaunchKernelGGL(kernel, c.w.grid(), dim3(64), 0, s, (const BowItem*)(d + c.o_it), (const uint4*)(d + c.o_d1),
+                           (const uint4*)(d + c.o_d2), (const uint8_t*)(d + c.o_v1), (const uint8_t*)(d + c.o_a2), (const int*)(d + c.o_f1),
+                           (const int*)(d + c.o_f2), th_low, (int*)(d + o_cnt), (const int*)(d + o_beg), (int4*)lists.d.p);
+    };
+    const BlockTrip count{d, h, c.L.in_bytes, nullptr, 0, h + o_cnt, d + o_cnt, n_items * 4};
+    if (int rc = round_trip(scr, "search_for_triangulation_cb", count, nullptr, [&](hipStream_t s) { launch(node_candidates_kernel<false>, s); }))
+        return rc;
+    const int* cnt = (const int*)(h + o_cnt);
+    int* beg = (int*)(h + o_beg);
     size_t n_cand = 0;
     for (size_t i = 0; i < n_items; i++) { beg[i] = (int)n_cand; n_cand += (size_t)cnt[i]; }
-    std::vector<int> raw(tot1, -1);
+    std::vector<int> raw((size_t)P.n1, -1);
     if (n_cand > 0) {
         if (n_cand > (size_t)INT32_MAX / 16) { set_last_error("search_for_triangulation_cb: too many candidates"); return MSORB_E_CAPACITY; }
         if (int rc = lists.acquire(device, n_cand * sizeof(int4), n_cand * sizeof(int4))) return rc;
-        e = msorb::small_copy(d + o_beg, beg, n_items * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(node_candidates_kernel<true>, dim3((unsigned)n_items), dim3(64), 0, s, (const BowItem*)(d + o_it), (const uint4*)(d + o_d1),
-                               (const uint4*)(d + o_d2), (const uint8_t*)(d + o_v1), (const uint8_t*)(d + o_a2), (const int*)(d + o_f1),
-                               (const int*)(d + o_f2), th_low, (int*)nullptr, (const int*)(d + o_beg), (int4*)lists.d.p);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = msorb::small_copy(lists.h.p, lists.d.p, n_cand * sizeof(int4), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_cb", e);
-        // ---- the replay: nodes ascending, a node's queries in list order (:1230-1358) ----
-        std::vector<int4> all((const int4*)lists.h.p, (const int4*)lists.h.p + n_cand);   // (out of the pinned block: read repeatedly below)
-        std::vector<uint8_t> matched2(tot2, 0);                                        // vbMatched2 (:1212)
-        std::vector<int4> group;
-        size_t k = 0;
-        while (k < n_cand) {
-            size_t k_end = k;
-            while (k_end < n_cand && all[k_end].x == all[k].x) k_end++;                // one query's candidates (contiguous: the fill order)
-            group.assign(all.begin() + k, all.begin() + k_end);
-            std::sort(group.begin(), group.end(), [](const int4& a, const int4& b) { return a.z != b.z ? a.z < b.z : a.w > b.w; });
-            for (const int4& c : group) {
-                if (matched2[c.y]) continue;                                            // :1262
-                if (!accept(ctx, c.x, c.y)) continue;                                  // :1332
-                raw[c.x] = c.y;
-                matched2[c.y] = 1;                                                      // :1345
-                break;
-            }
-            k = k_end;
-        }
+        const BlockTrip fill{d + o_beg, beg, n_items * 4, nullptr, 0, lists.h.p, lists.d.p, n_cand * sizeof(int4)};
+        if (int rc = round_trip(scr, "search_for_triangulation_cb", fill, nullptr, [&](hipStream_t s) { launch(node_candidates_kernel<true>, s); }))
+            return rc;
+        static_assert(sizeof(msorb::NodeCand) == sizeof(int4), "node_candidates_kernel writes int4");
+        std::vector<msorb::NodeCand> all((const msorb::NodeCand*)lists.h.p, (const msorb::NodeCand*)lists.h.p + n_cand);   // (out of the pinned block: read repeatedly)
+        std::vector<uint8_t> matched2((size_t)P.n2, 0);
+        msorb::pick_candidates(all.data(), n_cand, matched2.data(), raw.data(), [&](int i1, int i2) { return accept(ctx, i1, i2) != 0; });
     }
-    P.nmatches = replay_histogram(fa, common, raw.data(), check_orientation,
-                                  [&](int i1, int i2, float& a1, float& a2) { a1 = P.angle1[i1]; a2 = P.angle2[i2]; }, P.match12);
-    if (P.match21)
-        for (int i = 0; i < P.n1; i++)
-            if (P.match12[i] >= 0) P.match21[P.match12[i]] = i;
+    P.nmatches = finish_bow_pair(P, raw.data(), check_orientation);
     return MSORB_OK;
 }
+
+namespace {
+void launch_triangulation(hipStream_t s, const NodeWork& w, const uint8_t* d_items, const uint8_t* d_consts, const uint4* desc1,
+                          const uint4* desc2, const uint8_t* flags1, const uint8_t* flags2, const float2* xy1, const float4* tr2,
+                          const int* feat1, const int* feat2, int coarse, uint8_t* match12) {
+    hipLaunchKernelGGL(triangulation_match_kernel, w.grid(), dim3(64), w.lds(), s, (const BowItem*)d_items, (const TriConst*)d_consts,
+                       desc1, desc2, flags1, flags2, xy1, tr2, feat1, feat2, coarse, (int*)match12);
+}
+}  // namespace
 
 extern "C" int msorb_search_for_triangulation(int device, msorb_triangulation_pair* pairs, int n_pairs, int coarse,
                                               int check_orientation, float* elapsed_ms) {
     if (elapsed_ms) *elapsed_ms = 0;
     if (n_pairs < 0 || (n_pairs > 0 && !pairs)) return MSORB_E_INVALID;
     if (n_pairs == 0) return MSORB_OK;
-    std::vector<std::vector<Common>> common(n_pairs);
-    std::vector<FeatVec> fa(n_pairs), fb(n_pairs);
+    NodeWork w;
     std::vector<uint8_t> seen;
-    size_t tot1 = 0, tot2 = 0, totf1 = 0, totf2 = 0, n_items = 0;
-    int max_chunks = 1;
+    size_t tot1 = 0, tot2 = 0;
     for (int pi = 0; pi < n_pairs; pi++) {
         msorb_triangulation_pair& P = pairs[pi];
         P.nmatches = 0;
-        fa[pi] = FeatVec{P.fv1_nodes, P.fv1_node, P.fv1_begin, P.fv1_feat};
-        fb[pi] = FeatVec{P.fv2_nodes, P.fv2_node, P.fv2_begin, P.fv2_feat};
         bool ok = P.n1 >= 0 && P.n2 >= 0 && (P.n1 == 0 || (P.match12 && P.desc1 && P.valid1 && P.stereo1 && P.kp1)) &&
                   (P.n2 == 0 || (P.desc2 && P.avail2 && P.stereo2 && P.kp2 && P.scale_factors2 && P.level_sigma2_2 &&
                                  P.n_levels2 > 0));
         for (int j = 0; ok && j < P.n2; j++) ok = P.kp2[j].octave >= 0 && P.kp2[j].octave < P.n_levels2;
-        if (!ok || !check_feature_vector(P.n1, fa[pi], seen) || !check_feature_vector(P.n2, fb[pi], seen) ||
-            !merge_walk(fa[pi], fb[pi], common[pi], totf1, totf2, max_chunks)) {
+        if (!ok || !check_feature_vector(P.n1, fv1_of(P), seen) || !check_feature_vector(P.n2, fv2_of(P), seen) ||
+            !w.add(fv1_of(P), fv2_of(P), pi, (int)tot1, (int)tot2, (int)tot1, (int)tot2)) {
             set_last_error("search_for_triangulation: pair " + std::to_string(pi) +
                            ": bad sizes / null arrays / octave out of range / feature vector not ascending, out of range or "
                            "with a repeated feature");
             return MSORB_E_INVALID;
         }
-        n_items += common[pi].size();
         tot1 += (size_t)P.n1;
         tot2 += (size_t)P.n2;
     }
-    for (int pi = 0; pi < n_pairs; pi++)
-        for (int i = 0; i < pairs[pi].n1; i++) pairs[pi].match12[i] = -1;
-    if (n_items == 0) return MSORB_OK;
+    for (int pi = 0; pi < n_pairs; pi++) std::fill_n(pairs[pi].match12, pairs[pi].n1, -1);
+    if (w.items.empty()) return MSORB_OK;
     if (tot1 > (size_t)INT32_MAX / 2 || tot2 > (size_t)INT32_MAX / 2) return MSORB_E_INVALID;
     if (int rc = msorb::require_device(device)) return rc;
-    // ---- staging: [desc1 | desc2 | tr2 (x, y, 100*scale, sigma2) | xy1 | feat1 | feat2 | items | consts | flags1 | flags2] ----
-    const size_t o_d1 = 0, o_d2 = o_d1 + tot1 * 32, o_t2 = o_d2 + tot2 * 32, o_x1 = o_t2 + tot2 * 16, o_f1 = o_x1 + up16(tot1 * 8),
-                 o_f2 = o_f1 + up16(totf1 * 4), o_it = o_f2 + up16(totf2 * 4), o_c = o_it + up16(n_items * sizeof(BowItem)),
-                 o_v1 = o_c + up16((size_t)n_pairs * sizeof(TriConst)), o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2),
-                 o_m = in_bytes, total = o_m + up16(tot1 * 4);
+    // [desc1 | desc2 | tr2 (x, y, 100*scale, sigma2) | xy1 | feat1 | feat2 | items | consts | flags1 | flags2] in, [match12] out
+    BlockLayout L;
+    const size_t o_d1 = L.take(tot1 * 32), o_d2 = L.take(tot2 * 32), o_t2 = L.take(tot2 * 16), o_x1 = L.take(tot1 * 8),
+                 o_f1 = L.take(w.totf1 * 4), o_f2 = L.take(w.totf2 * 4), o_it = L.take(w.item_bytes()),
+                 o_c = L.take((size_t)n_pairs * sizeof(TriConst)), o_v1 = L.take(tot1), o_a2 = L.take(tot2);
+    L.outputs_begin();
+    const size_t o_m = L.take(tot1 * 4);
     static thread_local ThreadScratch scr(true, 2);
-    if (int rc = scr.acquire(device, total, total)) return rc;
-    {
-        uint8_t* h = scr.h.p;
-        size_t r1 = 0, r2 = 0, k1 = 0, k2 = 0, ni = 0;
-        TriConst* consts = (TriConst*)(h + o_c);
-        for (int pi = 0; pi < n_pairs; pi++) {
-            const msorb_triangulation_pair& P = pairs[pi];
-            if (P.n1) std::memcpy(h + o_d1 + r1 * 32, P.desc1, (size_t)P.n1 * 32);
-            if (P.n2) std::memcpy(h + o_d2 + r2 * 32, P.desc2, (size_t)P.n2 * 32);
-            float* xy = (float*)(h + o_x1) + 2 * r1;
-            uint8_t* f1 = (uint8_t*)(h + o_v1) + r1;
-            for (int i = 0; i < P.n1; i++) {
-                xy[2 * i] = P.kp1[i].x;
-                xy[2 * i + 1] = P.kp1[i].y;
-                f1[i] = (uint8_t)((P.valid1[i] ? 1 : 0) | (P.stereo1[i] ? 2 : 0));
-            }
-            float* tr = (float*)(h + o_t2) + 4 * r2;
-            uint8_t* f2 = (uint8_t*)(h + o_a2) + r2;
-            for (int j = 0; j < P.n2; j++) {
-                const int oct = P.kp2[j].octave;
-                tr[4 * j] = P.kp2[j].x;
-                tr[4 * j + 1] = P.kp2[j].y;
-                tr[4 * j + 2] = 100 * P.scale_factors2[oct];  // :1287 (int * float -> float)
-                tr[4 * j + 3] = P.level_sigma2_2[oct];        // :1332
-                f2[j] = (uint8_t)((P.avail2[j] ? 1 : 0) | (P.stereo2[j] ? 2 : 0));
-            }
-            std::memcpy(consts[pi].F, P.F12, sizeof(P.F12));
-            consts[pi].ep[0] = P.ep[0];
-            consts[pi].ep[1] = P.ep[1];
-            stage_lists(fa[pi], fb[pi], common[pi], pi, r1, r2, (int*)(h + o_f1), (int*)(h + o_f2), k1, k2,
-                        (BowItem*)(h + o_it), ni);
-            r1 += (size_t)P.n1;
-            r2 += (size_t)P.n2;
-        }
+    if (int rc = scr.acquire(device, L.end, L.end)) return rc;
+    uint8_t *h = scr.h.p, *d = scr.d.p;
+    size_t r1 = 0, r2 = 0;
+    for (int pi = 0; pi < n_pairs; pi++) {
+        const msorb_triangulation_pair& P = pairs[pi];
+        if (P.n1) std::memcpy(h + o_d1 + r1 * 32, P.desc1, (size_t)P.n1 * 32);
+        if (P.n2) std::memcpy(h + o_d2 + r2 * 32, P.desc2, (size_t)P.n2 * 32);
+        msorb::pack_triangulation_side(P.n1, P.kp1, nullptr, nullptr, P.valid1, P.stereo1, (float*)(h + o_x1) + 2 * r1, nullptr, h + o_v1 + r1);
+        msorb::pack_triangulation_side(P.n2, P.kp2, P.scale_factors2, P.level_sigma2_2, P.avail2, P.stereo2, nullptr,
+                                       (float*)(h + o_t2) + 4 * r2, h + o_a2 + r2);
+        stage_const(((TriConst*)(h + o_c))[pi], P.F12, P.ep);
+        r1 += (size_t)P.n1;
+        r2 += (size_t)P.n2;
     }
-    hipStream_t s = scr.s;
-    uint8_t* d = scr.d.p;
-    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, tot1 * 4, s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(triangulation_match_kernel, dim3((unsigned)n_items), dim3(64), (size_t)max_chunks * 8, s,
-                           (const BowItem*)(d + o_it), (const TriConst*)(d + o_c), (const uint4*)(d + o_d1),
-                           (const uint4*)(d + o_d2), (const uint8_t*)(d + o_v1), (const uint8_t*)(d + o_a2),
-                           (const float2*)(d + o_x1), (const float4*)(d + o_t2), (const int*)(d + o_f1), (const int*)(d + o_f2),
-                           coarse, (int*)(d + o_m));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, tot1 * 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
-    if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation", e);
-    // the raw matches are read feature by feature below: out of the pinned block first (one streaming copy) — scattered 4-byte
-    // reads of pinned host memory cost ~10 ns each, 0.8 ms for a 32-pair batch
-    static thread_local std::vector<int> m_local;
-    m_local.resize(tot1);
-    std::memcpy(m_local.data(), scr.h.p + o_m, tot1 * 4);
-    const int* m_all = m_local.data();
-    size_t r1 = 0;
+    w.stage(h + o_it, (int*)(h + o_f1), (int*)(h + o_f2));
+    const BlockTrip trip{d, h, L.in_bytes, d + o_m, tot1 * 4, h + o_m, d + o_m, tot1 * 4};
+    if (int rc = round_trip(scr, "search_for_triangulation", trip, elapsed_ms, [&](hipStream_t s) {
+            launch_triangulation(s, w, d + o_it, d + o_c, (const uint4*)(d + o_d1), (const uint4*)(d + o_d2), d + o_v1, d + o_a2,
+                                 (const float2*)(d + o_x1), (const float4*)(d + o_t2), (const int*)(d + o_f1), (const int*)(d + o_f2),
+                                 coarse, d + o_m);
+        })) return rc;
+    const int* raw = out_of_pinned(h + o_m, tot1);
     for (int pi = 0; pi < n_pairs; pi++) {
         msorb_triangulation_pair& P = pairs[pi];
-        P.nmatches = replay_histogram(
-            fa[pi], common[pi], m_all + r1, check_orientation,
-            [&](int i1, int i2, float& a1, float& a2) { a1 = P.kp1[i1].angle; a2 = P.kp2[i2].angle; }, P.match12);
-        r1 += (size_t)P.n1;
+        P.nmatches = finish_pair(P.n1, raw, check_orientation, P.match12, nullptr,
+                                 [&](int i1, int i2, float& a1, float& a2) { a1 = P.kp1[i1].angle; a2 = P.kp2[i2].angle; });
+        raw += P.n1;
     }
     return MSORB_OK;
 }
@@ -875,8 +711,9 @@ struct msorb_kf_store {
         bool alive = false;
         int row0 = 0, n = 0, feat0 = 0, nfeat = 0;
         std::vector<int> node, begin;   // FeatureVector: node ids ascending, list r = feat[begin[r] .. begin[r+1]) (offsets relative to feat0)
-        std::vector<int> feat;          // host copy of the lists (the rotation-histogram replay walks them)
+        std::vector<int> feat;          // host copy of the lists
         std::vector<float> angle;
+        FeatVec fv() const { return FeatVec{(int)node.size(), node.data(), begin.data(), feat.data()}; }
     };
     std::vector<Entry> kf;
     std::vector<int> dead_ids;   // indices of `kf` whose KeyFrame was removed: handed out again by the next add
@@ -888,6 +725,7 @@ struct msorb_kf_store {
     float4* d_tr = nullptr;     // x, y, 100 * scale[octave], sigma2[octave] (SearchForTriangulation, set 2)
     float* d_angle = nullptr;   // keypoint angles (rotation histogram)
     int* d_feat = nullptr;
+    const Entry* alive(int id) const { return id >= 0 && id < (int)kf.size() && kf[id].alive ? &kf[id] : nullptr; }
 };
 
 using msorb::grow;
@@ -931,13 +769,9 @@ extern "C" int msorb_kf_store_add(msorb_kf_store* s, int n, const msorb_keypoint
     for (int i = 0; i < n; i++)
         if (kps[i].octave < 0 || kps[i].octave >= n_levels) { set_last_error("kf_store_add: keypoint octave out of range"); return MSORB_E_INVALID; }
     const int f_lo = fv_nodes ? fv_begin[0] : 0, f_hi = fv_nodes ? fv_begin[fv_nodes] : 0, nf = f_hi - f_lo;
-    std::vector<float> xy((size_t)2 * n), tr((size_t)4 * n);
-    for (int i = 0; i < n; i++) {
-        xy[2 * i] = kps[i].x; xy[2 * i + 1] = kps[i].y;
-        tr[4 * i] = kps[i].x; tr[4 * i + 1] = kps[i].y;
-        tr[4 * i + 2] = 100 * scale_factors[kps[i].octave];   // ORBmatcher.cc:1287
-        tr[4 * i + 3] = level_sigma2[kps[i].octave];          // :1332
-    }
+    std::vector<float> xy((size_t)2 * n), tr((size_t)4 * n), ang(n);
+    msorb::pack_triangulation_side(n, kps, scale_factors, level_sigma2, nullptr, nullptr, xy.data(), tr.data(), nullptr);
+    for (int i = 0; i < n; i++) ang[i] = kps[i].angle;
     std::unique_lock<std::shared_mutex> lk(s->mu);
     if (hipSetDevice(s->device) != hipSuccess) return MSORB_E_HIP;
     hipError_t e = hipSuccess;
@@ -955,11 +789,7 @@ extern "C" int msorb_kf_store_add(msorb_kf_store* s, int n, const msorb_keypoint
     if (e == hipSuccess && n) e = hipMemcpy(s->d_xy + row0, xy.data(), (size_t)n * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && n) e = hipMemcpy(s->d_tr + row0, tr.data(), (size_t)n * 16, hipMemcpyHostToDevice);
     if (e == hipSuccess && nf) e = hipMemcpy(s->d_feat + feat0, fv_feat + f_lo, (size_t)nf * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n) {
-        std::vector<float> ang(n);
-        for (int i = 0; i < n; i++) ang[i] = kps[i].angle;
-        e = hipMemcpy(s->d_angle + row0, ang.data(), (size_t)n * 4, hipMemcpyHostToDevice);
-    }
+    if (e == hipSuccess && n) e = hipMemcpy(s->d_angle + row0, ang.data(), (size_t)n * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         s->rows_a.give(row0, (size_t)n); s->feats_a.give(feat0, (size_t)nf);
         set_last_error(std::string("kf_store_add: ") + hipGetErrorString(e));
@@ -971,8 +801,7 @@ extern "C" int msorb_kf_store_add(msorb_kf_store* s, int n, const msorb_keypoint
     E.begin.resize(fv_nodes + 1);
     for (int r = 0; r <= fv_nodes; r++) E.begin[r] = (fv_nodes ? fv_begin[r] : 0) - f_lo;
     E.feat.assign(fv_feat + f_lo, fv_feat + f_hi);
-    E.angle.resize(n);
-    for (int i = 0; i < n; i++) E.angle[i] = kps[i].angle;
+    E.angle = std::move(ang);
     s->n_alive++;
     if (!s->dead_ids.empty()) {   // ids of removed KeyFrames come back: the table does not grow with the length of the sequence
         *kf_id = s->dead_ids.back();
@@ -1010,27 +839,55 @@ extern "C" int msorb_kf_store_rows(const msorb_kf_store* s, size_t* rows_in_use,
 }
 
 namespace {
-// items of one pair from the stores' host copies of the two FeatureVectors; lists are addressed inside the resident /
-// staged feat arrays through absolute offsets
-void items_of(const std::vector<int>& node1, const std::vector<int>& begin1, int feat0_1, const int* node2, const int* begin2, int nodes2,
-              int feat0_2, int base1, int base2, int m1, int m2, int pi, std::vector<BowItem>& items, std::vector<Common>& common,
-              int& max_chunks, bool& ok) {
-    int i = 0, j = 0;
-    const int nodes1 = (int)node1.size();
-    while (i < nodes1 && j < nodes2) {
-        if (node1[i] == node2[j]) {
-            const int l1 = begin1[i + 1] - begin1[i], l2 = begin2[j + 1] - begin2[j];
-            if (l1 > 0 && l2 > 0) {
-                if (l2 >= (1 << 20)) { ok = false; return; }
-                common.push_back({i, j});
-                items.push_back(BowItem{base1, base2, feat0_1 + begin1[i], l1, feat0_2 + begin2[j], l2, pi, m1, m2});
-                max_chunks = std::max(max_chunks, (l2 + 63) >> 6);
-            }
-            i++; j++;
-        } else if (node1[i] < node2[j]) i++;
-        else j++;
+// One pair of a resident search.  Set 1 is KeyFrame A; set 2 KeyFrame B, or the call's frame (B == nullptr: n2 features staged at
+// row 0 of the frame block).  m1 / m2: the pair's first entry in the per-call arrays [flags1 of pair 0 | pair 1 | ...] and
+// [flags2 ...], [match12 ...] and [match21 ...].
+struct KfPair {
+    const msorb_kf_store::Entry *A, *B;
+    int n2, m1, m2;
+    int *match12, *match21, *nmatches;
+    int row2() const { return B ? B->row0 : 0; }
+};
+
+struct KfCall {   // the pairs of one resident search and their items
+    std::vector<KfPair> pairs;
+    NodeWork w;
+    size_t tot1 = 0, tot2 = 0;
+
+    // fv2 / feat2: the FeatureVector of set 2 and where its feat[0] sits in the device array the kernel reads its lists from
+    bool add(const KfPair& p, const FeatVec& fv2, int feat2) {
+        pairs.push_back(p);
+        KfPair& P = pairs.back();
+        P.m1 = (int)tot1; P.m2 = (int)tot2;
+        tot1 += (size_t)P.A->n;
+        tot2 += (size_t)P.n2;
+        return w.add(P.A->fv(), fv2, (int)pairs.size() - 1, P.A->row0, P.row2(), P.m1, P.m2, P.A->feat0, feat2);
     }
-}
+    bool add(const KfPair& p) { return add(p, p.B->fv(), p.B->feat0); }
+    void unmatched() const {   // no common node anywhere: nothing is launched, every feature stays unmatched
+        for (const KfPair& P : pairs) {
+            std::fill_n(P.match12, P.A->n, -1);
+            if (P.match21) std::fill_n(P.match21, P.n2, -1);
+        }
+    }
+    void stage_posts(void* h_posts) const {
+        PairPost* posts = (PairPost*)h_posts;
+        for (const KfPair& P : pairs) *posts++ = PairPost{P.m1, P.A->n, P.m2, P.n2, P.A->row0, P.row2()};
+    }
+    void launch_histogram(hipStream_t s, const uint8_t* d_posts, const float* angle1, const float* angle2, int check_orientation,
+                          uint8_t* match12, uint8_t* match21, uint8_t* nmatches) const {
+        hipLaunchKernelGGL(pair_histogram_kernel, dim3((unsigned)pairs.size()), dim3(256), 0, s, (const PairPost*)d_posts, angle1, angle2,
+                           check_orientation, (int*)match12, (int*)match21, (int*)nmatches);
+    }
+    void deliver(const uint8_t* h_m12, const uint8_t* h_m21, const uint8_t* h_nm) const {
+        for (size_t pi = 0; pi < pairs.size(); pi++) {
+            const KfPair& P = pairs[pi];
+            if (P.A->n) std::memcpy(P.match12, h_m12 + (size_t)P.m1 * 4, (size_t)P.A->n * 4);
+            if (h_m21 && P.match21 && P.n2) std::memcpy(P.match21, h_m21 + (size_t)P.m2 * 4, (size_t)P.n2 * 4);
+            *P.nmatches = ((const int*)h_nm)[pi];
+        }
+    }
+};
 }  // namespace
 
 extern "C" int msorb_search_by_bow_kf(msorb_kf_store* st, msorb_bow_kf_pair* pairs, int n_pairs, const msorb_bow_frame* frame,
@@ -1049,107 +906,51 @@ extern "C" int msorb_search_by_bow_kf(msorb_kf_store* st, msorb_bow_kf_pair* pai
             return MSORB_E_INVALID;
         }
     }
-    // per-call flag arrays: [valid1 of pair 0 | pair 1 | ...] and [avail2 of pair 0 | ...]
-    std::vector<BowItem> items;
-    std::vector<std::vector<Common>> common(n_pairs);
-    std::vector<int> m1(n_pairs), m2(n_pairs);
-    size_t tot1 = 0, tot2 = 0;
-    int max_chunks = 1;
-    const int fr_feat_lo = frame && frame->fv_nodes ? frame->fv_begin[0] : 0;
+    // the frame's lists are staged from its first list entry on, its descriptors at row 0 of the frame block
+    const int fr_feat_lo = ff.nodes ? ff.begin[0] : 0;
+    const size_t fr_rows = frame ? (size_t)frame->n : 0, fr_feats = ff.nodes ? (size_t)(ff.begin[ff.nodes] - fr_feat_lo) : 0;
+    KfCall c;
     for (int pi = 0; pi < n_pairs; pi++) {
         msorb_bow_kf_pair& P = pairs[pi];
         P.nmatches = 0;
-        const bool vs_frame = P.kf2 < 0;
-        if (P.kf1 < 0 || P.kf1 >= (int)st->kf.size() || !st->kf[P.kf1].alive || (vs_frame && !frame) ||
-            (!vs_frame && (P.kf2 >= (int)st->kf.size() || !st->kf[P.kf2].alive)) || (vs_frame != (frame != nullptr))) {
+        const msorb_kf_store::Entry *A = st->alive(P.kf1), *B = P.kf2 < 0 ? nullptr : st->alive(P.kf2);
+        if (!A || (P.kf2 >= 0 && !B) || (P.kf2 < 0) != (frame != nullptr)) {
             set_last_error("search_by_bow_kf: pair " + std::to_string(pi) + ": unknown KeyFrame id, or KeyFrame / frame trains mixed in one call");
             return MSORB_E_INVALID;
         }
-        const msorb_kf_store::Entry& A = st->kf[P.kf1];
-        const int n2 = vs_frame ? frame->n : st->kf[P.kf2].n;
-        if ((A.n > 0 && (!P.valid1 || !P.match12))) { set_last_error("search_by_bow_kf: null valid1 / match12"); return MSORB_E_INVALID; }
-        m1[pi] = (int)tot1; m2[pi] = (int)tot2;
-        bool ok = true;
-        if (vs_frame) {
-            // the frame's lists are staged at feat offset 0 of the per-call frame block; descriptors at row 0 of that block
-            std::vector<int> rel(frame->fv_nodes + 1);
-            for (int r = 0; r <= frame->fv_nodes; r++) rel[r] = (frame->fv_nodes ? frame->fv_begin[r] : 0) - fr_feat_lo;
-            items_of(A.node, A.begin, A.feat0, frame->fv_node, rel.data(), frame->fv_nodes, 0, A.row0, 0, m1[pi], m2[pi], pi, items,
-                     common[pi], max_chunks, ok);
-        } else {
-            const msorb_kf_store::Entry& B = st->kf[P.kf2];
-            items_of(A.node, A.begin, A.feat0, B.node.data(), B.begin.data(), (int)B.node.size(), B.feat0, A.row0, B.row0, m1[pi], m2[pi],
-                     pi, items, common[pi], max_chunks, ok);
-        }
-        if (!ok) { set_last_error("search_by_bow_kf: node list too long"); return MSORB_E_INVALID; }
-        tot1 += (size_t)A.n;
-        tot2 += (size_t)n2;
+        if ((A->n > 0 && (!P.valid1 || !P.match12))) { set_last_error("search_by_bow_kf: null valid1 / match12"); return MSORB_E_INVALID; }
+        const KfPair K{A, B, B ? B->n : frame->n, 0, 0, P.match12, P.match21, &P.nmatches};
+        if (!(B ? c.add(K) : c.add(K, ff, -fr_feat_lo))) { set_last_error("search_by_bow_kf: node list too long"); return MSORB_E_INVALID; }
     }
-    if (items.empty()) {   // no common node anywhere: nothing is launched, every feature stays unmatched
-        for (int pi = 0; pi < n_pairs; pi++) {
-            msorb_bow_kf_pair& P = pairs[pi];
-            const int n1 = st->kf[P.kf1].n, n2 = P.kf2 < 0 ? frame->n : st->kf[P.kf2].n;
-            for (int i = 0; i < n1; i++) P.match12[i] = -1;
-            if (P.match21) for (int j = 0; j < n2; j++) P.match21[j] = -1;
-        }
-        return MSORB_OK;
-    }
-    const size_t n_items = items.size();
-    const size_t fr_rows = frame ? (size_t)frame->n : 0, fr_feats = frame && frame->fv_nodes ? (size_t)(frame->fv_begin[frame->fv_nodes] - fr_feat_lo) : 0;
-    // staging: [frame desc | frame feat | frame angle | items | posts | valid1 | avail2] in, [match12 | match21 | nmatches] out
-    const size_t o_fd = 0, o_ff = o_fd + fr_rows * 32, o_fa = o_ff + up16(fr_feats * 4), o_it = o_fa + up16(fr_rows * 4),
-                 o_po = o_it + up16(n_items * sizeof(BowItem)), o_v1 = o_po + up16((size_t)n_pairs * sizeof(PairPost)),
-                 o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2), o_m = in_bytes, o_m21 = o_m + up16(tot1 * 4),
-                 o_nm = o_m21 + up16(tot2 * 4), total = o_nm + up16((size_t)n_pairs * 4), out_bytes = total - o_m;
+    if (c.w.items.empty()) { c.unmatched(); return MSORB_OK; }
+    const size_t tot1 = c.tot1, tot2 = c.tot2;
+    // [frame desc | frame feat | frame angle | items | posts | valid1 | avail2] in, [match12 | match21 | nmatches] out
+    BlockLayout L;
+    const size_t o_fd = L.take(fr_rows * 32), o_ff = L.take(fr_feats * 4), o_fa = L.take(fr_rows * 4), o_it = L.take(c.w.item_bytes()),
+                 o_po = L.take((size_t)n_pairs * sizeof(PairPost)), o_v1 = L.take(tot1), o_a2 = L.take(tot2);
+    L.outputs_begin();
+    const size_t o_m = L.take(tot1 * 4), o_m21 = L.take(tot2 * 4), o_nm = L.take((size_t)n_pairs * 4);
     static thread_local ThreadScratch scr(true, 2);
-    if (int rc = scr.acquire(st->device, total, total)) return rc;
-    {
-        uint8_t* h = scr.h.p;
-        if (fr_rows) std::memcpy(h + o_fd, frame->desc, fr_rows * 32);
-        if (fr_feats) std::memcpy(h + o_ff, frame->fv_feat + fr_feat_lo, fr_feats * 4);
-        if (fr_rows && frame->angle) std::memcpy(h + o_fa, frame->angle, fr_rows * 4);
-        std::memcpy(h + o_it, items.data(), n_items * sizeof(BowItem));
-        PairPost* posts = (PairPost*)(h + o_po);
-        for (int pi = 0; pi < n_pairs; pi++) {
-            const msorb_bow_kf_pair& P = pairs[pi];
-            const msorb_kf_store::Entry& A = st->kf[P.kf1];
-            const int n1 = A.n, n2 = P.kf2 < 0 ? frame->n : st->kf[P.kf2].n;
-            if (n1) std::memcpy(h + o_v1 + m1[pi], P.valid1, (size_t)n1);
-            if (n2) {
-                if (P.avail2) std::memcpy(h + o_a2 + m2[pi], P.avail2, (size_t)n2);
-                else std::memset(h + o_a2 + m2[pi], 1, (size_t)n2);
-            }
-            posts[pi] = PairPost{m1[pi], n1, m2[pi], n2, A.row0, P.kf2 < 0 ? 0 : st->kf[P.kf2].row0};
-        }
-    }
-    hipStream_t s = scr.s;
-    uint8_t* d = scr.d.p;
-    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, o_nm - o_m, s);   // match12 and match21 = -1
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
-    if (e == hipSuccess) {
-        const uint4* desc2 = frame ? (const uint4*)(d + o_fd) : st->d_desc;
-        const int* feat2 = frame ? (const int*)(d + o_ff) : st->d_feat;
-        hipLaunchKernelGGL(bow_match_kernel, dim3((unsigned)n_items), dim3(64), (size_t)max_chunks * 8, s, (const BowItem*)(d + o_it),
-                           st->d_desc, desc2, (const uint8_t*)(d + o_v1), (const uint8_t*)(d + o_a2), st->d_feat, feat2, th_low,
-                           inclusive ? 1 : 0, nnratio, (int*)(d + o_m));
-        hipLaunchKernelGGL(pair_histogram_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, (const PairPost*)(d + o_po), st->d_angle,
-                           frame ? (const float*)(d + o_fa) : st->d_angle, check_orientation, (int*)(d + o_m), (int*)(d + o_m21),
-                           (int*)(d + o_nm));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, out_bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
-    if (e != hipSuccess) return hip_fail(scr, "search_by_bow_kf", e);
+    if (int rc = scr.acquire(st->device, L.end, L.end)) return rc;
+    uint8_t *h = scr.h.p, *d = scr.d.p;
+    if (fr_rows) std::memcpy(h + o_fd, frame->desc, fr_rows * 32);
+    if (fr_feats) std::memcpy(h + o_ff, frame->fv_feat + fr_feat_lo, fr_feats * 4);
+    if (fr_rows && frame->angle) std::memcpy(h + o_fa, frame->angle, fr_rows * 4);
+    c.w.stage(h + o_it, nullptr, nullptr);
+    c.stage_posts(h + o_po);
     for (int pi = 0; pi < n_pairs; pi++) {
-        msorb_bow_kf_pair& P = pairs[pi];
-        const int n1 = st->kf[P.kf1].n, n2 = P.kf2 < 0 ? frame->n : st->kf[P.kf2].n;
-        if (n1) std::memcpy(P.match12, scr.h.p + o_m + (size_t)m1[pi] * 4, (size_t)n1 * 4);
-        if (P.match21 && n2) std::memcpy(P.match21, scr.h.p + o_m21 + (size_t)m2[pi] * 4, (size_t)n2 * 4);
-        P.nmatches = ((const int*)(scr.h.p + o_nm))[pi];
+        const KfPair& K = c.pairs[pi];
+        if (K.A->n) std::memcpy(h + o_v1 + K.m1, pairs[pi].valid1, (size_t)K.A->n);
+        if (K.n2) stage_flags(h + o_a2 + K.m2, pairs[pi].avail2, (size_t)K.n2);
     }
+    const BlockTrip trip{d, h, L.in_bytes, d + o_m, o_nm - o_m, h + o_m, d + o_m, L.end - o_m};   // match12 and match21 = -1
+    if (int rc = round_trip(scr, "search_by_bow_kf", trip, elapsed_ms, [&](hipStream_t s) {
+            launch_bow(s, c.w, d + o_it, st->d_desc, frame ? (const uint4*)(d + o_fd) : st->d_desc, d + o_v1, d + o_a2, st->d_feat,
+                       frame ? (const int*)(d + o_ff) : st->d_feat, th_low, inclusive ? 1 : 0, nnratio, d + o_m);
+            c.launch_histogram(s, d + o_po, st->d_angle, frame ? (const float*)(d + o_fa) : st->d_angle, check_orientation, d + o_m,
+                               d + o_m21, d + o_nm);
+        })) return rc;
+    c.deliver(h + o_m, h + o_m21, h + o_nm);
     return MSORB_OK;
 }
 
@@ -1159,85 +960,50 @@ extern "C" int msorb_search_for_triangulation_kf(msorb_kf_store* st, msorb_trian
     if (!st || n_pairs < 0 || (n_pairs > 0 && !pairs)) return MSORB_E_INVALID;
     if (n_pairs == 0) return MSORB_OK;
     std::shared_lock<std::shared_mutex> lk(st->mu);
-    std::vector<BowItem> items;
-    std::vector<std::vector<Common>> common(n_pairs);
-    std::vector<int> m1(n_pairs), m2(n_pairs);
-    size_t tot1 = 0, tot2 = 0;
-    int max_chunks = 1;
+    KfCall c;
     for (int pi = 0; pi < n_pairs; pi++) {
         msorb_triangulation_kf_pair& P = pairs[pi];
         P.nmatches = 0;
-        if (P.kf1 < 0 || P.kf1 >= (int)st->kf.size() || !st->kf[P.kf1].alive || P.kf2 < 0 || P.kf2 >= (int)st->kf.size() ||
-            !st->kf[P.kf2].alive) {
+        const msorb_kf_store::Entry *A = st->alive(P.kf1), *B = st->alive(P.kf2);
+        if (!A || !B) {
             set_last_error("search_for_triangulation_kf: pair " + std::to_string(pi) + ": unknown KeyFrame id");
             return MSORB_E_INVALID;
         }
-        const msorb_kf_store::Entry &A = st->kf[P.kf1], &B = st->kf[P.kf2];
-        if ((A.n > 0 && (!P.valid1 || !P.stereo1 || !P.match12)) || (B.n > 0 && (!P.avail2 || !P.stereo2))) {
+        if ((A->n > 0 && (!P.valid1 || !P.stereo1 || !P.match12)) || (B->n > 0 && (!P.avail2 || !P.stereo2))) {
             set_last_error("search_for_triangulation_kf: null flag arrays / match12");
             return MSORB_E_INVALID;
         }
-        m1[pi] = (int)tot1; m2[pi] = (int)tot2;
-        bool ok = true;
-        items_of(A.node, A.begin, A.feat0, B.node.data(), B.begin.data(), (int)B.node.size(), B.feat0, A.row0, B.row0, m1[pi], m2[pi], pi,
-                 items, common[pi], max_chunks, ok);
-        if (!ok) { set_last_error("search_for_triangulation_kf: node list too long"); return MSORB_E_INVALID; }
-        tot1 += (size_t)A.n;
-        tot2 += (size_t)B.n;
-    }
-    if (items.empty()) {
-        for (int pi = 0; pi < n_pairs; pi++)
-            for (int i = 0; i < st->kf[pairs[pi].kf1].n; i++) pairs[pi].match12[i] = -1;
-        return MSORB_OK;
-    }
-    const size_t n_items = items.size();
-    // staging: [items | consts | posts | flags1 | flags2] in, [match12 | nmatches] out
-    const size_t o_it = 0, o_c = o_it + up16(n_items * sizeof(BowItem)), o_po = o_c + up16((size_t)n_pairs * sizeof(TriConst)),
-                 o_v1 = o_po + up16((size_t)n_pairs * sizeof(PairPost)), o_a2 = o_v1 + up16(tot1), in_bytes = o_a2 + up16(tot2),
-                 o_m = in_bytes, o_nm = o_m + up16(tot1 * 4), total = o_nm + up16((size_t)n_pairs * 4), out_bytes = total - o_m;
-    static thread_local ThreadScratch scr(true, 2);
-    if (int rc = scr.acquire(st->device, total, total)) return rc;
-    {
-        uint8_t* h = scr.h.p;
-        std::memcpy(h + o_it, items.data(), n_items * sizeof(BowItem));
-        TriConst* consts = (TriConst*)(h + o_c);
-        PairPost* posts = (PairPost*)(h + o_po);
-        for (int pi = 0; pi < n_pairs; pi++) {
-            const msorb_triangulation_kf_pair& P = pairs[pi];
-            const msorb_kf_store::Entry &A = st->kf[P.kf1], &B = st->kf[P.kf2];
-            uint8_t* f1 = (uint8_t*)(h + o_v1) + m1[pi];
-            uint8_t* f2 = (uint8_t*)(h + o_a2) + m2[pi];
-            for (int i = 0; i < A.n; i++) f1[i] = (uint8_t)((P.valid1[i] ? 1 : 0) | (P.stereo1[i] ? 2 : 0));
-            for (int j = 0; j < B.n; j++) f2[j] = (uint8_t)((P.avail2[j] ? 1 : 0) | (P.stereo2[j] ? 2 : 0));
-            std::memcpy(consts[pi].F, P.F12, sizeof(P.F12));
-            consts[pi].ep[0] = P.ep[0];
-            consts[pi].ep[1] = P.ep[1];
-            posts[pi] = PairPost{m1[pi], A.n, m2[pi], B.n, A.row0, B.row0};
+        if (!c.add(KfPair{A, B, B->n, 0, 0, P.match12, nullptr, &P.nmatches})) {
+            set_last_error("search_for_triangulation_kf: node list too long");
+            return MSORB_E_INVALID;
         }
     }
-    hipStream_t s = scr.s;
-    uint8_t* d = scr.d.p;
-    hipError_t e = msorb::small_copy(d, scr.h.p, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d + o_m, 0xFF, tot1 * 4, s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(triangulation_match_kernel, dim3((unsigned)n_items), dim3(64), (size_t)max_chunks * 8, s,
-                           (const BowItem*)(d + o_it), (const TriConst*)(d + o_c), st->d_desc, st->d_desc, (const uint8_t*)(d + o_v1),
-                           (const uint8_t*)(d + o_a2), st->d_xy, st->d_tr, st->d_feat, st->d_feat, coarse, (int*)(d + o_m));
-        hipLaunchKernelGGL(pair_histogram_kernel, dim3((unsigned)n_pairs), dim3(256), 0, s, (const PairPost*)(d + o_po), st->d_angle,
-                           st->d_angle, check_orientation, (int*)(d + o_m), (int*)nullptr, (int*)(d + o_nm));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
-    if (e == hipSuccess) e = msorb::small_copy(scr.h.p + o_m, d + o_m, out_bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
-    if (e != hipSuccess) return hip_fail(scr, "search_for_triangulation_kf", e);
+    if (c.w.items.empty()) { c.unmatched(); return MSORB_OK; }
+    const size_t tot1 = c.tot1, tot2 = c.tot2;
+    // [items | consts | posts | flags1 | flags2] in, [match12 | nmatches] out
+    BlockLayout L;
+    const size_t o_it = L.take(c.w.item_bytes()), o_c = L.take((size_t)n_pairs * sizeof(TriConst)),
+                 o_po = L.take((size_t)n_pairs * sizeof(PairPost)), o_v1 = L.take(tot1), o_a2 = L.take(tot2);
+    L.outputs_begin();
+    const size_t o_m = L.take(tot1 * 4), o_nm = L.take((size_t)n_pairs * 4);
+    static thread_local ThreadScratch scr(true, 2);
+    if (int rc = scr.acquire(st->device, L.end, L.end)) return rc;
+    uint8_t *h = scr.h.p, *d = scr.d.p;
+    c.w.stage(h + o_it, nullptr, nullptr);
+    c.stage_posts(h + o_po);
     for (int pi = 0; pi < n_pairs; pi++) {
-        msorb_triangulation_kf_pair& P = pairs[pi];
-        const int n1 = st->kf[P.kf1].n;
-        if (n1) std::memcpy(P.match12, scr.h.p + o_m + (size_t)m1[pi] * 4, (size_t)n1 * 4);
-        P.nmatches = ((const int*)(scr.h.p + o_nm))[pi];
+        const msorb_triangulation_kf_pair& P = pairs[pi];
+        const KfPair& K = c.pairs[pi];
+        msorb::pack_triangulation_side(K.A->n, nullptr, nullptr, nullptr, P.valid1, P.stereo1, nullptr, nullptr, h + o_v1 + K.m1);
+        msorb::pack_triangulation_side(K.n2, nullptr, nullptr, nullptr, P.avail2, P.stereo2, nullptr, nullptr, h + o_a2 + K.m2);
+        stage_const(((TriConst*)(h + o_c))[pi], P.F12, P.ep);
     }
+    const BlockTrip trip{d, h, L.in_bytes, d + o_m, tot1 * 4, h + o_m, d + o_m, L.end - o_m};
+    if (int rc = round_trip(scr, "search_for_triangulation_kf", trip, elapsed_ms, [&](hipStream_t s) {
+            launch_triangulation(s, c.w, d + o_it, d + o_c, st->d_desc, st->d_desc, d + o_v1, d + o_a2, st->d_xy, st->d_tr, st->d_feat,
+                                 st->d_feat, coarse, d + o_m);
+            c.launch_histogram(s, d + o_po, st->d_angle, st->d_angle, check_orientation, d + o_m, nullptr, d + o_nm);
+        })) return rc;
+    c.deliver(h + o_m, nullptr, h + o_nm);
     return MSORB_OK;
 }
