@@ -757,6 +757,46 @@ int msorb_pose_optimization_batch(int device, int n_problems, const msorb_pose_p
 int msorb_frame_pose_optimization(msorb_frame* f, const msorb_pose_problem* p, const uint8_t* has_point, const float* pos_w,
                                   const float* inv_level_sigma2, int nlevels, uint8_t* outlier, msorb_pose_result* r);
 
+/* Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1040-1407) for pinhole KeyFrames without a second camera on the device:
+ * g2o's Levenberg-Marquardt over the KeyFrame poses and the map points (optimization_algorithm_levenberg.cpp:61-170 under
+ * sparse_optimizer.cpp:376-389), the points eliminated by the Schur complement (block_solver.hpp:354-486), in double, and the
+ * classification of :1331-1373.  Appended to ABI 6002 as the pose optimisation was: MSORB_ABI_VERSION stays 6002.  Not covered:
+ * the EdgeSE3ProjectXYZToBody arm (:1281-1317) and an inertial map (setUserLambdaInit, :1113); the caller keeps the reference's
+ * routine for those.  Two calls on the same input return the same bits.  Re-entrant: every calling thread has its own stream and
+ * staging. */
+#define MSORB_E_ARG MSORB_E_INVALID      /* an index out of range, edges that are not point-major, a missing array */
+typedef struct msorb_ba_keyframe { float q[4], t[3]; float fx, fy, cx, cy, mbf; int fixed; } msorb_ba_keyframe;
+typedef struct msorb_ba_result {
+    int status;             /* 0 optimised; 1 no fixed KeyFrame: nothing touched (:1098-1102); 2 stop flag set before the first iteration (:1323-1325): nothing touched */
+    int iterations;         /* solve() calls made (optimize's return value) */
+    int trials, rejected_trials;
+    int n_outliers;
+    double chi2_initial, chi2_final, lambda_final;
+} msorb_ba_result;
+/* The largest number of free (not fixed) KeyFrames a call accepts: the reduced system is solved densely by one workgroup.
+ * More: MSORB_E_CAPACITY, nothing launched.  Points and edges are bounded by device memory only. */
+int msorb_local_ba_capacity(void);
+/* kfs [n_kf]: GetPose() as unit quaternion x,y,z,w + translation, the camera, fixed != 0 for lFixedCameras and the InitKFid
+ * KeyFrame (:1136, :1152).  pos_w [3 per point].  Edges are point-major (all edges of point 0, then of point 1, ...: the order
+ * in which :1196-1320 makes them): edge_kf, edge_point, xy [2 per edge: kpUn.pt], u_right (>= 0 marks a stereo edge, :1246),
+ * inv_sigma2 (mvInvLevelSigma2[octave]).  max_iterations: the reference passes 10.  *stop_flag (may be NULL) is read where g2o
+ * calls terminate(): before every iteration and between the trials of one.  Outputs: kf_qt_out [7 per KeyFrame] the narrowed
+ * estimate that SetPose receives (:1393; a fixed KeyFrame's repeats its input), pos_out [3 per point] (:1402), kf_qt_d / pos_d
+ * (may be NULL) the doubles before the narrowing, edge_outlier [per edge] 1 where chi2 > 5.991 (mono) / 7.815 (stereo) or the
+ * depth is not positive at the final estimate: the pairs of vToErase.  With status 1 or 2 the outputs repeat the inputs and no
+ * flag is set.  Without an edge there is nothing to optimise: status 0, zero iterations.  MSORB_E_ARG: an index out of range or
+ * edges that are not point-major.  *elapsed_ms (may be NULL) = device time from the first launch to the classification. */
+int msorb_local_ba(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_points, const float* pos_w,
+                   int n_edges, const int* edge_kf, const int* edge_point, const float* xy, const float* u_right,
+                   const float* inv_sigma2, int max_iterations, const volatile int* stop_flag,
+                   float* kf_qt_out, double* kf_qt_d, float* pos_out, double* pos_d, uint8_t* edge_outlier, msorb_ba_result* r,
+                   float* elapsed_ms);
+/* For measurements: with MSORB_LOCAL_BA_STAGES=1 in the environment (read once per process) every msorb_local_ba call brackets
+ * its stages with events, and this returns the device ms of the calling thread's last call spent in: [0] the linearisations
+ * (errors, Jacobians, the per-vertex sums), [1] the Schur complements, [2] the dense solves, [3] the rest of the trials (update,
+ * errors, cost).  Without the variable: MSORB_E_ARG, zeros. */
+int msorb_local_ba_stage_ms(float ms[4]);
+
 /* Frame::ComputeStereoMatches (Frame.cc:743-913, median rejection :899-912 included) for every stereo pair of the last
  * msorb_extract_batch() call of `h`, all on the device: pair p = images 2p (left) and 2p+1 (right) of that batch.
  * d_keypoints / d_descriptors / capacity are the arrays that call filled, d_counts[2*n_pairs] the keypoint counts as a

@@ -24,9 +24,17 @@
 #ifndef MSORB_OPTIMIZER_DEVICE_H
 #define MSORB_OPTIMIZER_DEVICE_H
 
+#include <atomic>
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
+#include <list>
+#include <map>
+#include <memory>
 #include <mutex>
+#include <thread>
+#include <tuple>
+#include <utility>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -115,6 +123,198 @@ int PoseOptimization(FrameT* pFrame, msorb_frame* resident, int device = 0) {
 template <class FrameT>
 int PoseOptimization(FrameT* pFrame) {
     return PoseOptimization(pFrame, static_cast<msorb_frame*>(nullptr));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1040-1407) on msorb_local_ba.
+//
+//   bool ORB_SLAM3::msorb_host::LocalBundleAdjustment(pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges)
+//
+// the reference's signature (pKF is its shared_ptr<KeyFrame>), and its effects: the outlier observations erased, SetPose,
+// SetWorldPos, UpdateNormalAndDepth, mnOptimizedTimesInLBA++, IncreaseChangeIndex, all under mMutexMapUpdate; num_fixedKF,
+// num_OptKF and num_edges as the reference leaves them (it never writes num_MPs, nor does this).  true = done, including the
+// reference's two early returns (no fixed KeyFrame, :1098-1102; the stop flag already set, :1323-1325).
+//
+// false = NOT handled, the map as it was, the caller runs Optimizer::LocalBundleAdjustment: an inertial map (:1113), a KeyFrame
+// with a second camera anywhere in the problem (the EdgeSE3ProjectXYZToBody arm, :1281-1317), more free KeyFrames than
+// msorb_local_ba_capacity().  The marks mnBALocalForKF / mnBAFixedForKF that the walk sets are put back before a late `false`, so
+// the reference's own walk finds them as it would have.
+//
+// What runs where.  The covisibility walk and the gathering (:1042-1102, :1196-1320) stay host code, as the reference's.  The
+// optimisation and the classification (:1326-1373) are the device's.  *pbStopFlag is a bool another thread may set (LocalMapping::
+// InterruptBA); the C ABI reads an int, so a watcher thread mirrors the one into the other for the duration of the call.
+template <class KFPtr, class MPPtr>
+struct LocalBAProblem {
+    std::list<KFPtr> lLocalKeyFrames, lFixedCameras;
+    std::list<MPPtr> lLocalMapPoints;
+    std::vector<KFPtr> kf_of_index;        // local KeyFrames first, then the fixed cameras
+    std::vector<msorb_ba_keyframe> kfs;
+    std::vector<float> pos_w, xy, u_right, inv_sigma2;
+    std::vector<int> edge_kf, edge_point;
+    std::vector<std::pair<KFPtr, MPPtr>> edge_objects;
+    int num_fixedKF = 0;
+    bool two_cameras = false;
+    std::vector<std::pair<KFPtr, std::pair<unsigned long, unsigned long>>> kf_marks;   // what the walk overwrote
+    std::vector<std::pair<MPPtr, unsigned long>> mp_marks;
+    void restore_marks() {
+        for (auto it = kf_marks.rbegin(); it != kf_marks.rend(); ++it) { it->first->mnBALocalForKF = it->second.first; it->first->mnBAFixedForKF = it->second.second; }
+        for (auto it = mp_marks.rbegin(); it != mp_marks.rend(); ++it) it->first->mnBALocalForKF = it->second;
+    }
+};
+
+// :1042-1102 and :1196-1320.  Returns the problem as the arrays of msorb_local_ba; kfs / edges are empty when num_fixedKF == 0.
+template <class KFPtr, class MapT>
+auto GatherLocalBA(KFPtr pKF, MapT* pMap) {
+    typedef typename std::decay<decltype(pKF->GetMapPointMatches()[0])>::type MPPtr;
+    LocalBAProblem<KFPtr, MPPtr> B;
+    auto mark = [&](const KFPtr& k) { B.kf_marks.push_back({k, {k->mnBALocalForKF, k->mnBAFixedForKF}}); };
+    B.lLocalKeyFrames.push_back(pKF);
+    mark(pKF);
+    pKF->mnBALocalForKF = pKF->mnId;
+    auto* pCurrentMap = pKF->GetMap();
+    const auto vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+    for (size_t i = 0; i < vNeighKFs.size(); i++) {
+        KFPtr pKFi = vNeighKFs[i];
+        mark(pKFi);
+        pKFi->mnBALocalForKF = pKF->mnId;
+        if (pKFi->mnId == pMap->GetInitKFid()) B.num_fixedKF = 1;                                        // :1053
+        if (!pKFi->isBad() && pKFi->GetMap() == pCurrentMap) B.lLocalKeyFrames.push_back(pKFi);
+    }
+    for (const KFPtr& pKFi : B.lLocalKeyFrames) {                                                        // :1063-1077
+        const auto vpMPs = pKFi->GetMapPointMatches();
+        for (const MPPtr& pMP : vpMPs)
+            if (pMP && !pMP->isBad() && pMP->GetMap() == pCurrentMap && pMP->mnBALocalForKF != pKF->mnId) {
+                B.lLocalMapPoints.push_back(pMP);
+                B.mp_marks.push_back({pMP, pMP->mnBALocalForKF});
+                pMP->mnBALocalForKF = pKF->mnId;
+            }
+    }
+    for (const MPPtr& pMP : B.lLocalMapPoints) {                                                         // :1081-1094
+        const auto observations = pMP->GetObservations();
+        for (const auto& ob : observations) {
+            KFPtr pKFi = ob.first;
+            if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+                mark(pKFi);
+                pKFi->mnBAFixedForKF = pKF->mnId;
+                if (!pKFi->isBad() && pKFi->GetMap() == pCurrentMap) B.lFixedCameras.push_back(pKFi);
+            }
+        }
+    }
+    B.num_fixedKF = (int)B.lFixedCameras.size() + B.num_fixedKF;                                         // :1095
+    if (B.num_fixedKF == 0) return B;
+    std::map<KFPtr, int> index;
+    auto add_kf = [&](const KFPtr& k, bool fixed) {
+        const auto Tcw = k->GetPose();                                                                   // :1133, :1149
+        const auto& q = Tcw.unit_quaternion();
+        const auto& t = Tcw.translation();
+        msorb_ba_keyframe r;
+        r.q[0] = q.x(); r.q[1] = q.y(); r.q[2] = q.z(); r.q[3] = q.w();
+        r.t[0] = t(0); r.t[1] = t(1); r.t[2] = t(2);
+        r.fx = k->fx; r.fy = k->fy; r.cx = k->cx; r.cy = k->cy; r.mbf = k->mbf;                          // :1267-1271
+        r.fixed = fixed ? 1 : 0;
+        index[k] = (int)B.kfs.size();
+        B.kfs.push_back(r);
+        B.kf_of_index.push_back(k);
+        if (k->mpCamera2) B.two_cameras = true;
+    };
+    for (const KFPtr& k : B.lLocalKeyFrames) add_kf(k, k->mnId == pMap->GetInitKFid());                  // :1136
+    for (const KFPtr& k : B.lFixedCameras) add_kf(k, true);                                              // :1152
+    int nPoints = 0;
+    for (const MPPtr& pMP : B.lLocalMapPoints) {                                                         // :1196-1320
+        const auto Xw = pMP->GetWorldPos();
+        B.pos_w.push_back(Xw(0)); B.pos_w.push_back(Xw(1)); B.pos_w.push_back(Xw(2));
+        const auto observations = pMP->GetObservations();
+        for (const auto& ob : observations) {
+            KFPtr pKFi = ob.first;
+            if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) continue;                                // :1214
+            const auto at = index.find(pKFi);
+            if (at == index.end()) continue;   // (a KeyFrame that is in neither list has no vertex; the reference's setVertex would get NULL)
+            if (pKFi->mpCamera2) B.two_cameras = true;
+            const int leftIndex = std::get<0>(ob.second);
+            if (leftIndex == -1) continue;
+            const float kp_ur = pKFi->GetuRight(leftIndex);
+            const auto& kpUn = pKFi->GetKeyUn(leftIndex);
+            if (kpUn.octave > 10) continue;                                                              // :1220, :1249
+            B.edge_kf.push_back(at->second);
+            B.edge_point.push_back(nPoints);
+            B.xy.push_back(kpUn.pt.x); B.xy.push_back(kpUn.pt.y);
+            B.u_right.push_back(kp_ur < 0 ? -1.0f : kp_ur);                                              // :1218 / :1246
+            B.inv_sigma2.push_back(pKFi->mvInvLevelSigma2[kpUn.octave]);
+            B.edge_objects.push_back({pKFi, pMP});
+        }
+        nPoints++;
+    }
+    return B;
+}
+
+template <class KFPtr, class MapT>
+bool LocalBundleAdjustment(KFPtr pKF, bool* pbStopFlag, MapT* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges,
+                           int device = 0) {
+    (void)num_MPs;
+    if (pMap->IsInertial() || pKF->mpCamera2) return false;
+    auto B = GatherLocalBA(pKF, pMap);
+    if (B.two_cameras || (int)B.kfs.size() - B.num_fixedKF > msorb_local_ba_capacity()) {
+        B.restore_marks();
+        return false;
+    }
+    num_fixedKF = B.num_fixedKF;
+    if (B.num_fixedKF == 0) return true;                                                                 // :1098-1102
+    auto* pCurrentMap = pKF->GetMap();
+    pCurrentMap->msOptKFs.clear();                                                                       // :1125-1126, :1141, :1157
+    pCurrentMap->msFixedKFs.clear();
+    for (const KFPtr& k : B.lLocalKeyFrames) pCurrentMap->msOptKFs.insert(k->mnId);
+    for (const KFPtr& k : B.lFixedCameras) pCurrentMap->msFixedKFs.insert(k->mnId);
+    num_OptKF = (int)B.lLocalKeyFrames.size();                                                           // :1143
+    const int K = (int)B.kfs.size(), P = (int)B.lLocalMapPoints.size(), E = (int)B.edge_kf.size();
+    num_edges = E;                                                                                       // :1321
+    std::vector<float> kf_out(7 * (size_t)K), pos_out(3 * (size_t)P);
+    std::vector<uint8_t> outlier((size_t)E);
+    msorb_ba_result r;
+    volatile int stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+    std::atomic<bool> done(false);
+    std::thread watcher;
+    if (pbStopFlag && !stop)
+        watcher = std::thread([&] {
+            while (!done.load(std::memory_order_acquire)) {
+                if (*static_cast<volatile bool*>(pbStopFlag)) { stop = 1; return; }
+                std::this_thread::sleep_for(std::chrono::microseconds(50));
+            }
+        });
+    const int rc = msorb_local_ba(device, K, B.kfs.data(), P, B.pos_w.data(), E, B.edge_kf.data(), B.edge_point.data(), B.xy.data(),
+                                  B.u_right.data(), B.inv_sigma2.data(), 10, pbStopFlag ? &stop : nullptr, kf_out.data(), nullptr,
+                                  pos_out.data(), nullptr, outlier.data(), &r, nullptr);
+    done.store(true, std::memory_order_release);
+    if (watcher.joinable()) watcher.join();
+    if (rc == MSORB_E_CAPACITY) { B.restore_marks(); return false; }
+    if (rc != MSORB_OK) fail_call("msorb_local_ba");
+    if (r.status != 0) return true;                                                                      // :1323-1325
+    typedef typename std::decay<decltype(pKF->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(pKF->GetPose().unit_quaternion())>::type QuatT;
+    typedef typename std::decay<decltype(pKF->GetPose().translation())>::type VecT;
+    typedef typename std::decay<decltype(B.lLocalMapPoints.front()->GetWorldPos())>::type PosT;
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                                            // :1376
+    for (int pass = 0; pass < 2; pass++)                                                                 // vToErase: the mono edges, then the stereo edges
+        for (int e = 0; e < E; e++) {
+            if (!outlier[e] || (B.u_right[e] >= 0) != (pass == 1)) continue;
+            const auto& o = B.edge_objects[e];
+            if (o.second->isBad()) continue;                                                             // :1335, :1363
+            o.first->EraseMapPointMatch(o.second);                                                       // :1382-1383
+            o.second->EraseObservation(o.first);
+        }
+    int k = 0;
+    for (const KFPtr& pKFi : B.lLocalKeyFrames) {                                                        // :1388-1395
+        const float* o = kf_out.data() + 7 * (size_t)k++;
+        pKFi->SetPose(SE3T(QuatT(o[3], o[0], o[1], o[2]), VecT(o[4], o[5], o[6])));
+    }
+    int p = 0;
+    for (const auto& pMP : B.lLocalMapPoints) {                                                          // :1397-1405
+        const float* o = pos_out.data() + 3 * (size_t)p++;
+        pMP->SetWorldPos(PosT(o[0], o[1], o[2]));
+        pMP->UpdateNormalAndDepth();
+        pMP->mnOptimizedTimesInLBA++;
+    }
+    pMap->IncreaseChangeIndex();                                                                         // :1406
+    return true;
 }
 
 }  // namespace msorb_host

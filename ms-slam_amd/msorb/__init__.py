@@ -1893,3 +1893,77 @@ def _frame_pose_optimization(self, q, t, cam, has_point, pos_w, inv_level_sigma2
     _check(L.msorb_frame_pose_optimization(self.h, _np_ptr(p), _np_ptr(hp), _np_ptr(pw), _np_ptr(inv), len(inv), _np_ptr(out),
                                            _np_ptr(res)), "msorb_frame_pose_optimization")
     return res[0], out[:self.n]
+
+
+# ---- Optimizer::LocalBundleAdjustment on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_local_ba_capacity", "msorb_local_ba", "msorb_local_ba_stage_ms")
+E_ARG = E_INVALID      # MSORB_E_ARG
+
+BA_KEYFRAME_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"),
+                              ("mbf", "<f4"), ("fixed", "<i4")])                                  # msorb_ba_keyframe
+BA_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("rejected_trials", "<i4"),
+                            ("n_outliers", "<i4"), ("_pad", "<i4"), ("chi2_initial", "<f8"), ("chi2_final", "<f8"),
+                            ("lambda_final", "<f8")])                                             # msorb_ba_result
+assert BA_KEYFRAME_DTYPE.itemsize == 52 and BA_RESULT_DTYPE.itemsize == 48
+
+
+def _ba_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_local_ba_capacity.argtypes = []
+    L.msorb_local_ba.argtypes = [ci, ci, vp, ci, vp, ci] + [vp] * 5 + [ci] + [vp] * 8
+    L.msorb_local_ba_stage_ms.argtypes = [vp]
+    return L
+
+
+def local_ba_capacity():
+    """the largest number of free KeyFrames msorb_local_ba accepts"""
+    return _ba_lib().msorb_local_ba_capacity()
+
+
+def ba_keyframes(q, t, cam, fixed):
+    """msorb_ba_keyframe records: q [K, 4] (x, y, z, w), t [K, 3], cam: dict(fx, fy, cx, cy, mbf) for all, fixed [K]"""
+    k = np.zeros(len(fixed), BA_KEYFRAME_DTYPE)
+    k["q"], k["t"], k["fixed"] = np.asarray(q, np.float32), np.asarray(t, np.float32), np.asarray(fixed, np.int32)
+    for name in ("fx", "fy", "cx", "cy", "mbf"):
+        k[name] = cam[name]
+    return k
+
+
+def local_ba(keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, max_iterations=10, stop_flag=None, device=0,
+             timing=False):
+    """msorb_local_ba: Optimizer::LocalBundleAdjustment on the device.  keyframes: BA_KEYFRAME_DTYPE [K]; pos_w [P, 3]; the edges
+    point-major: edge_kf, edge_point [E], xy [E, 2], u_right [E] (>= 0: stereo), inv_sigma2 [E].  stop_flag: None or an int32
+    array of one element that another thread may set.
+    -> dict(result: BA_RESULT_DTYPE record, kf_qt float32 [K, 7], kf_qt_d float64 [K, 7], pos float32 [P, 3], pos_d float64 [P, 3],
+    outlier bool [E]) and, with timing, elapsed_ms (device time)."""
+    L = _ba_lib()
+    kf = _c(keyframes, BA_KEYFRAME_DTYPE).reshape(-1)
+    pw = _c(pos_w, np.float32).reshape(-1, 3)
+    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
+    ob, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
+    K, P, E = len(kf), len(pw), len(ek)
+    if [len(ep), len(ob), len(ur), len(inv)] != [E, 2 * E, E, E]:
+        raise ValueError("the edge arrays do not have one entry per edge")
+    if stop_flag is not None:
+        assert stop_flag.dtype == np.int32 and stop_flag.size == 1
+    qt, qtd = np.zeros((max(K, 1), 7), np.float32), np.zeros((max(K, 1), 7), np.float64)
+    po, pod = np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64)
+    out = np.zeros(max(E, 1), np.uint8)
+    res = np.zeros(1, BA_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_local_ba(device, K, _np_ptr(kf), P, _np_ptr(pw), E, _np_ptr(ek), _np_ptr(ep), _np_ptr(ob), _np_ptr(ur), _np_ptr(inv),
+                            int(max_iterations), None if stop_flag is None else _np_ptr(stop_flag), _np_ptr(qt), _np_ptr(qtd),
+                            _np_ptr(po), _np_ptr(pod), _np_ptr(out), _np_ptr(res), C.addressof(ms)), "msorb_local_ba")
+    r = dict(result=res[0], kf_qt=qt[:K], kf_qt_d=qtd[:K], pos=po[:P], pos_d=pod[:P], outlier=out[:E].astype(bool))
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r
+
+
+def local_ba_stage_ms():
+    """msorb_local_ba_stage_ms: dict(linearise, schur, solve, trial) in device ms of this thread's last local_ba call; needs
+    MSORB_LOCAL_BA_STAGES=1 in the environment before the library is loaded"""
+    ms = np.zeros(4, np.float32)
+    _check(_ba_lib().msorb_local_ba_stage_ms(_np_ptr(ms)), "msorb_local_ba_stage_ms")
+    return dict(zip(("linearise", "schur", "solve", "trial"), (float(v) for v in ms)))

@@ -249,6 +249,13 @@ def owner(classes, cls, name):
 FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_members.json")
 # members a later host header touches go to a second file beside it (`--write-extra`), so that the first one stays as it was pinned
 FIXTURE_EXTRA = os.path.join(ROOT, "tests", "golden", "reference_members_kf_database.json")
+# ... and each later one to a file of its own (`--write-extra NAME` -> reference_members_NAME.json): a pinned table is never rewritten
+FIXTURE_GLOB = os.path.join(ROOT, "tests", "golden", "reference_members_*.json")
+
+
+def extra_tables():
+    """the second file first, then the later ones by name"""
+    return [FIXTURE_EXTRA] * os.path.exists(FIXTURE_EXTRA) + sorted(f for f in glob.glob(FIXTURE_GLOB) if f != FIXTURE_EXTRA)
 PROBES = [("KeyFrame", "NLeft"), ("KeyFrame", "GetNLeft"), ("Frame", "mvKeysUn"), ("KeyFrame", "mvKeysUn"), ("MapPoint", "mfMaxDistance"),
           ("ORBmatcher", "SearchByProjection"), ("ORBmatcher", "mfNNratio"), ("ORBextractor", "mvImagePyramid")]
 
@@ -268,8 +275,8 @@ def table(classes):
 def load_table(path=FIXTURE):
     """-> the classes of the stored table, in parse_reference()'s form"""
     classes = json.load(open(path))
-    if path == FIXTURE and os.path.exists(FIXTURE_EXTRA):
-        for c, v in json.load(open(FIXTURE_EXTRA)).items():
+    for extra in extra_tables() if path == FIXTURE else []:
+        for c, v in json.load(open(extra)).items():
             classes.setdefault(c, {"bases": v["bases"], "file": v["file"], "n_members": v["n_members"], "members": {}})
             for name, e in v["members"].items():
                 classes[c]["members"].setdefault(name, e)
@@ -377,25 +384,28 @@ def type_check(classes, accesses):
 
 def main(argv):
     """no argument: the reference headers if present, else the stored table; --stored: the stored table;
-    --write-table: parse the reference headers and (re)write the stored table; --write-extra: write only the members the stored
-    table lacks to a second file, which --stored reads as well"""
+    --write-table: parse the reference headers and (re)write the stored table; --write-extra [NAME]: write only the members the
+    stored tables lack to a further file (reference_members_NAME.json; without NAME the second file), which --stored reads as well"""
     if "--write-table" in argv:
         with open(FIXTURE, "w") as f:
             json.dump(table(parse_reference()), f, indent=1, sort_keys=True)
             f.write("\n")
         print("wrote", os.path.relpath(FIXTURE, ROOT))
         return 0
-    if "--write-extra" in argv:   # what the host layer touches today and the stored table lacks
-        full, have = table(parse_reference()), json.load(open(FIXTURE))
+    if "--write-extra" in argv:   # what the host layer touches today and the stored tables lack
+        rest = [a for a in argv[argv.index("--write-extra") + 1:] if not a.startswith("-")]
+        target = os.path.join(ROOT, "tests", "golden", f"reference_members_{rest[0]}.json") if rest else FIXTURE_EXTRA
+        full = table(parse_reference())
+        have = [json.load(open(f)) for f in [FIXTURE] + [t for t in extra_tables() if t != target]]
         extra = {}
         for c, v in full.items():
-            new = {n: e for n, e in v["members"].items() if n not in have.get(c, {}).get("members", {})}
+            new = {n: e for n, e in v["members"].items() if not any(n in h.get(c, {}).get("members", {}) for h in have)}
             if new:
                 extra[c] = dict(v, members=new)
-        with open(FIXTURE_EXTRA, "w") as f:
+        with open(target, "w") as f:
             json.dump(extra, f, indent=1, sort_keys=True)
             f.write("\n")
-        print("wrote", os.path.relpath(FIXTURE_EXTRA, ROOT), sum(len(v["members"]) for v in extra.values()), "members")
+        print("wrote", os.path.relpath(target, ROOT), sum(len(v["members"]) for v in extra.values()), "members")
         return 0
     if "--stored" in argv or not os.path.isdir(os.path.join(REF, "include")):
         classes, source = load_table(), os.path.relpath(FIXTURE, ROOT)
