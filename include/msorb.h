@@ -675,6 +675,76 @@ typedef struct msorb_triangulation_kf_pair {
 int msorb_search_for_triangulation_kf(msorb_kf_store* s, msorb_triangulation_kf_pair* pairs, int n_pairs, int coarse,
                                       int check_orientation, float* elapsed_ms);
 
+/* The neighbour loop of LocalMapping::CreateNewMapPoints (LocalMapping.cc:460-731) for resident pinhole KeyFrames without a second
+ * camera: per neighbour, in the caller's order, SearchForTriangulation (:492), then for every matched pair the parallax test,
+ * GeometricTools::Triangulate or KeyFrame::UnprojectStereo, the depth tests, the reprojection gates and the scale-consistency gate
+ * (:578-712) — one upload, three small launches per neighbour on one stream, one read-back.  A query that got a point at neighbour i
+ * is no query of neighbour i+1 (mpCurrentKeyFrame->AddMapPoint, :722 -> ORBmatcher.cc:1237-1241), which also frees the train it
+ * would have claimed there: the result is the sequential loop's, not that of one msorb_search_for_triangulation_kf batch over all
+ * neighbours.  Appended to ABI 6002 as the local bundle adjustment was: MSORB_ABI_VERSION stays 6002.
+ *   geometry      Tcw = GetPose().matrix3x4() row major, Ow = GetCameraCenter(), fx .. mbf the KeyFrame's members,
+ *                 u_right[n] = GetuRight(i) (stereo when >= 0), depth[n] = GetDepth(i)
+ *   call          kf1 = mpCurrentKeyFrame; valid1[n1]: 1 = the feature has no map point now (bOnlyStereo = false);
+ *                 coarse = bCoarse (:490); inertial = mbInertial (the 0.9996 / 0.9998 bound of :604);
+ *                 th_far = mThFarPoints, <= 0 when mbFarPoints is off
+ *   neighbour     kf2 and avail2[n2] (1 = no map point), its geometry, F12 / ep as in msorb_triangulation_pair.  The caller has
+ *                 dropped the neighbours that fail the baseline test (:469-486).
+ *   outputs       match12[n1]: vMatchedIndices after the orientation filter, for the masks at that point of the loop;
+ *                 status[n1]: MSORB_NP_*; x3D[3 * n1]: the new point where the status is one of the three CREATED codes, 0 elsewhere;
+ *                 nmatches; n_created.  The points of neighbour k, in ascending feature index, are the reference's creation order.
+ * ratioFactor is 1.5f * mvScaleFactors[1] of kf1 (:454); mvLevelSigma2 / mvScaleFactors are the store's.  The arithmetic is float,
+ * one rounded operation per reference operator (csrc/new_points_device.h); the singular vector of Triangulate comes from a restated
+ * Jacobi SVD whose bit parity with a compiled Eigen is not pinned, and cos(2 atan2(mb/2, depth)) is evaluated as a rational
+ * expression in double.  Not covered: KeyFrames with mpCamera2 (:526-576), fisheye models.
+ * MSORB_E_INVALID, before anything is launched: unknown id, kf2 == kf1, a kf2 listed twice, a null required array, a KeyFrame with
+ * more than 64 pyramid levels.  n_nb == 0 is MSORB_OK.  Thread-safe as the resident searches are. */
+enum {
+    MSORB_NP_NONE = 0,           /* not matched */
+    MSORB_NP_TRIANGULATED = 1,   /* created (:606) */
+    MSORB_NP_STEREO1 = 2,        /* created from kf1's stereo measurement (:614) */
+    MSORB_NP_STEREO2 = 3,        /* created from kf2's stereo measurement (:620) */
+    MSORB_NP_LOW_PARALLAX = 4,   /* :624 */
+    MSORB_NP_NULL_W = 5,         /* :607, x3Dh(3) == 0 */
+    MSORB_NP_STEREO_DEPTH = 6,   /* :630, UnprojectStereo with depth <= 0 */
+    MSORB_NP_BEHIND1 = 7,        /* :635 */
+    MSORB_NP_BEHIND2 = 8,        /* :639 */
+    MSORB_NP_REPROJ1 = 9,        /* :654 / :666 */
+    MSORB_NP_REPROJ2 = 10,       /* :680 / :691 */
+    MSORB_NP_ZERO_DIST = 11,     /* :702 */
+    MSORB_NP_FAR = 12,           /* :705 */
+    MSORB_NP_SCALE_RATIO = 13    /* :711 */
+};
+typedef struct msorb_new_points_geometry {
+    float Tcw[12];
+    float Ow[3];
+    float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+    const float *u_right, *depth;
+} msorb_new_points_geometry;
+typedef struct msorb_new_points_call {
+    int kf1;
+    const uint8_t* valid1;
+    msorb_new_points_geometry g1;
+    int coarse, check_orientation, inertial;
+    float th_far;
+} msorb_new_points_call;
+typedef struct msorb_new_points_neighbour {
+    int kf2;
+    const uint8_t* avail2;
+    msorb_new_points_geometry g2;
+    float F12[9];
+    float ep[2];
+    int* match12;
+    uint8_t* status;
+    float* x3D;
+    int nmatches, n_created;
+} msorb_new_points_neighbour;
+int msorb_create_new_map_points_kf(msorb_kf_store* s, const msorb_new_points_call* call, msorb_new_points_neighbour* nb, int n_nb,
+                                   float* elapsed_ms);
+/* For measurements: with MSORB_NEW_POINTS_STAGES=1 in the environment (read once per process) a call that asks for elapsed_ms
+ * brackets every launch with events; ms[0..2] = the calling thread's last call, summed over its neighbours: match, histogram,
+ * new points. */
+int msorb_create_new_map_points_stage_ms(float ms[3]);
+
 /* KeyFrameDatabase on the device (src/KeyFrameDatabase.cc; the BowVectors are msorb_bow_transform's).  Appended to ABI 6002:
  * MSORB_ABI_VERSION is unchanged, so a caller that needs these entries asks the loader for them (a library built before them
  * reports 6002 as well).

@@ -26,6 +26,7 @@
 #include "hip_host.h"
 #include "matcher_device.h"
 #include "matcher_rules.h"
+#include "new_points_device.h"
 #include "store_arena.h"
 
 using msorb::set_last_error;
@@ -713,6 +714,8 @@ struct msorb_kf_store {
         std::vector<int> node, begin;   // FeatureVector: node ids ascending, list r = feat[begin[r] .. begin[r+1]) (offsets relative to feat0)
         std::vector<int> feat;          // host copy of the lists
         std::vector<float> angle;
+        std::vector<uint8_t> octave;    // per keypoint (msorb_create_new_map_points_kf: rides in the per-call flag byte)
+        std::vector<float> scale;       // mvScaleFactors
         FeatVec fv() const { return FeatVec{(int)node.size(), node.data(), begin.data(), feat.data()}; }
     };
     std::vector<Entry> kf;
@@ -802,6 +805,9 @@ extern "C" int msorb_kf_store_add(msorb_kf_store* s, int n, const msorb_keypoint
     for (int r = 0; r <= fv_nodes; r++) E.begin[r] = (fv_nodes ? fv_begin[r] : 0) - f_lo;
     E.feat.assign(fv_feat + f_lo, fv_feat + f_hi);
     E.angle = std::move(ang);
+    E.octave.resize(n);
+    for (int i = 0; i < n; i++) E.octave[i] = (uint8_t)std::min(kps[i].octave, 255);
+    E.scale.assign(scale_factors, scale_factors + n_levels);
     s->n_alive++;
     if (!s->dead_ids.empty()) {   // ids of removed KeyFrames come back: the table does not grow with the length of the sequence
         *kf_id = s->dead_ids.back();
@@ -824,6 +830,7 @@ extern "C" int msorb_kf_store_remove(msorb_kf_store* s, int kf_id) {
     s->feats_a.give((size_t)E.feat0, (size_t)E.nfeat);
     E.n = 0; E.nfeat = 0;
     std::vector<int>().swap(E.node); E.begin.assign(1, 0); std::vector<float>().swap(E.angle); std::vector<int>().swap(E.feat);
+    std::vector<uint8_t>().swap(E.octave); std::vector<float>().swap(E.scale);
     s->dead_ids.push_back(kf_id);
     s->n_alive--;
     return MSORB_OK;
@@ -1005,5 +1012,196 @@ extern "C" int msorb_search_for_triangulation_kf(msorb_kf_store* st, msorb_trian
             c.launch_histogram(s, d + o_po, st->d_angle, st->d_angle, check_orientation, d + o_m, nullptr, d + o_nm);
         })) return rc;
     c.deliver(h + o_m, nullptr, h + o_nm);
+    return MSORB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// LocalMapping::CreateNewMapPoints, the loop over the neighbours (LocalMapping.cc:460-731), for resident KeyFrames.
+// The reference matches neighbour i+1 against the current KeyFrame's map points AFTER neighbour i's new points were
+// added (:722), so the searches cannot share one launch: per neighbour, on one stream, [triangulation_match_kernel over
+// that pair's items | pair_histogram_kernel | new_points_kernel], all reading ONE working flag array of KeyFrame 1 in
+// the call's scratch, in which new_points_kernel clears the "visited" bit of every feature that got a point.
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+struct NpSide {   // one KeyFrame of the call
+    msorb::NpCam cam;
+    int row0;     // its first row in the store's arrays
+    int m;        // its first entry in the per-call arrays (flags, u_right, depth)
+    int lvl;      // its first entry in the per-call table of level scale factors
+    int n;
+};
+
+// One thread per feature of KeyFrame 1: a matched one runs LocalMapping.cc:578-712 for its pair (new_points_device.h).
+// flag byte: bit 0 visited / available, bit 1 stereo, bits 2..7 the keypoint's octave.
+__global__ __launch_bounds__(256) void new_points_kernel(const NpSide* __restrict__ sides, int k2, const float* __restrict__ lvl_scale,
+                                                         uint8_t* __restrict__ flags, const float* __restrict__ u_right,
+                                                         const float* __restrict__ depth, const float2* __restrict__ xy,
+                                                         const float4* __restrict__ tr, const int* __restrict__ match12, int inertial,
+                                                         float th_far, float ratio_factor, uint8_t* __restrict__ status,
+                                                         float* __restrict__ x3d) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int n1 = sides[0].n, n2 = sides[k2].n;
+    if (i >= n1) return;
+    const int i2 = match12[i];
+    uint8_t st = msorb::kNpNone;
+    float X[3] = {0.0f, 0.0f, 0.0f};
+    if (i2 >= 0 && i2 < n2) {
+        const NpSide& S1 = sides[0];
+        const NpSide& S2 = sides[k2];
+        const uint8_t fl1 = flags[S1.m + i], fl2 = flags[S2.m + i2];
+        const float2 p1 = xy[S1.row0 + i];
+        const float4 t2 = tr[S2.row0 + i2];
+        const msorb::NpFeature f1{p1.x, p1.y, u_right[S1.m + i], depth[S1.m + i], tr[S1.row0 + i].w, lvl_scale[S1.lvl + (fl1 >> 2)]};
+        const msorb::NpFeature f2{t2.x, t2.y, u_right[S2.m + i2], depth[S2.m + i2], t2.w, lvl_scale[S2.lvl + (fl2 >> 2)]};
+        st = msorb::new_point_pair(S1.cam, S2.cam, f1, f2, inertial, th_far, ratio_factor, X);
+        if (st >= msorb::kNpTriangulated && st <= msorb::kNpStereo2) flags[S1.m + i] = fl1 & ~1u;   // :722: no query of the next neighbour
+        else X[0] = X[1] = X[2] = 0.0f;
+    }
+    status[i] = st;
+    x3d[3 * i] = X[0];
+    x3d[3 * i + 1] = X[1];
+    x3d[3 * i + 2] = X[2];
+}
+
+bool np_geometry_ok(const msorb_new_points_geometry& g, int n) { return n == 0 || (g.u_right && g.depth); }
+void np_stage_side(NpSide& S, const msorb_new_points_geometry& g, const msorb_kf_store::Entry& E, int m, int lvl, const uint8_t* on,
+                   uint8_t* flags, float* ur, float* depth, float* lvl_scale) {
+    std::memcpy(S.cam.T, g.Tcw, sizeof(g.Tcw));
+    std::memcpy(S.cam.Ow, g.Ow, sizeof(g.Ow));
+    S.cam.fx = g.fx; S.cam.fy = g.fy; S.cam.cx = g.cx; S.cam.cy = g.cy;
+    S.cam.invfx = g.invfx; S.cam.invfy = g.invfy; S.cam.mb = g.mb; S.cam.mbf = g.mbf;
+    S.row0 = E.row0; S.m = m; S.lvl = lvl; S.n = E.n;
+    for (int i = 0; i < E.n; i++) flags[m + i] = (uint8_t)((on[i] ? 1 : 0) | (g.u_right[i] >= 0.0f ? 2 : 0) | (E.octave[i] << 2));
+    if (E.n) { std::memcpy(ur + m, g.u_right, (size_t)E.n * 4); std::memcpy(depth + m, g.depth, (size_t)E.n * 4); }
+    std::memcpy(lvl_scale + lvl, E.scale.data(), E.scale.size() * 4);
+}
+thread_local float g_np_stage_ms[3] = {0, 0, 0};
+bool np_stage_events() {
+    static const bool on = [] { const char* e = getenv("MSORB_NEW_POINTS_STAGES"); return e && e[0] == '1'; }();
+    return on;
+}
+}  // namespace
+
+extern "C" int msorb_create_new_map_points_stage_ms(float ms[3]) {
+    if (!ms) return MSORB_E_INVALID;
+    std::memcpy(ms, g_np_stage_ms, sizeof(g_np_stage_ms));
+    return MSORB_OK;
+}
+
+extern "C" int msorb_create_new_map_points_kf(msorb_kf_store* st, const msorb_new_points_call* call, msorb_new_points_neighbour* nb,
+                                              int n_nb, float* elapsed_ms) {
+    if (elapsed_ms) *elapsed_ms = 0;
+    if (!st || !call || n_nb < 0 || (n_nb > 0 && !nb)) return MSORB_E_INVALID;
+    std::shared_lock<std::shared_mutex> lk(st->mu);
+    const msorb_kf_store::Entry* A = st->alive(call->kf1);
+    if (!A || (A->n > 0 && !call->valid1) || !np_geometry_ok(call->g1, A->n) || A->scale.size() > 64) {
+        set_last_error("create_new_map_points_kf: unknown kf1 / null valid1, u_right or depth / more than 64 levels");
+        return MSORB_E_INVALID;
+    }
+    const int n1 = A->n;
+    NodeWork w;
+    std::vector<const msorb_kf_store::Entry*> B((size_t)n_nb);
+    std::vector<int> item0((size_t)n_nb + 1, 0), m2((size_t)n_nb), lvl((size_t)n_nb);
+    size_t tot = (size_t)n1, tot_lvl = A->scale.size();
+    for (int k = 0; k < n_nb; k++) {
+        msorb_new_points_neighbour& N = nb[k];
+        N.nmatches = 0;
+        N.n_created = 0;
+        B[k] = N.kf2 == call->kf1 ? nullptr : st->alive(N.kf2);
+        bool ok = B[k] != nullptr;
+        for (int j = 0; ok && j < k; j++) ok = nb[j].kf2 != N.kf2;
+        ok = ok && (B[k]->n == 0 || N.avail2) && np_geometry_ok(N.g2, B[k]->n) && (n1 == 0 || (N.match12 && N.status && N.x3D)) &&
+             B[k]->scale.size() <= 64;
+        if (!ok) {
+            set_last_error("create_new_map_points_kf: neighbour " + std::to_string(k) +
+                           ": unknown kf2 / kf2 == kf1 / kf2 listed twice / null array / more than 64 levels");
+            return MSORB_E_INVALID;
+        }
+        m2[k] = (int)tot;
+        lvl[k] = (int)tot_lvl;
+        tot += (size_t)B[k]->n;
+        tot_lvl += B[k]->scale.size();
+        if (tot > (size_t)INT32_MAX / 16 || (size_t)(k + 1) * (size_t)n1 > (size_t)INT32_MAX / 16) return MSORB_E_INVALID;
+        if (!w.add(A->fv(), B[k]->fv(), k, A->row0, B[k]->row0, 0, m2[k], A->feat0, B[k]->feat0)) {
+            set_last_error("create_new_map_points_kf: node list too long");
+            return MSORB_E_INVALID;
+        }
+        item0[k + 1] = (int)w.items.size();
+    }
+    for (int k = 0; k < n_nb && n1; k++) {
+        std::fill_n(nb[k].match12, n1, -1);
+        std::memset(nb[k].status, 0, (size_t)n1);
+        std::memset(nb[k].x3D, 0, (size_t)n1 * 12);
+    }
+    if (w.items.empty() || n1 == 0) return MSORB_OK;
+    const size_t K = (size_t)n_nb, kn1 = K * (size_t)n1;
+    // [items | consts | posts | sides | level scales | u_right | depth | flags] in, [match12 | nmatches | x3D | status] out
+    BlockLayout L;
+    const size_t o_it = L.take(w.item_bytes()), o_c = L.take(K * sizeof(TriConst)), o_po = L.take(K * sizeof(PairPost)),
+                 o_sd = L.take((K + 1) * sizeof(NpSide)), o_lv = L.take(tot_lvl * 4), o_ur = L.take(tot * 4), o_dp = L.take(tot * 4),
+                 o_fl = L.take(tot);
+    L.outputs_begin();
+    const size_t o_m = L.take(kn1 * 4), o_nm = L.take(K * 4), o_x = L.take(kn1 * 12), o_st = L.take(kn1);
+    static thread_local ThreadScratch scr(true, 2);
+    if (int rc = scr.acquire(st->device, L.end, L.end)) return rc;
+    uint8_t *h = scr.h.p, *d = scr.d.p;
+    w.stage(h + o_it, nullptr, nullptr);
+    NpSide* sides = (NpSide*)(h + o_sd);
+    np_stage_side(sides[0], call->g1, *A, 0, 0, call->valid1, h + o_fl, (float*)(h + o_ur), (float*)(h + o_dp), (float*)(h + o_lv));
+    for (size_t k = 0; k < K; k++) {
+        np_stage_side(sides[k + 1], nb[k].g2, *B[k], m2[k], lvl[k], nb[k].avail2, h + o_fl, (float*)(h + o_ur), (float*)(h + o_dp),
+                      (float*)(h + o_lv));
+        stage_const(((TriConst*)(h + o_c))[k], nb[k].F12, nb[k].ep);
+        ((PairPost*)(h + o_po))[k] = PairPost{(int)(k * (size_t)n1), n1, 0, B[k]->n, A->row0, B[k]->row0};
+    }
+    const float ratio_factor = 1.5f * (A->scale.size() > 1 ? A->scale[1] : 1.0f);   // 1.5f * mfScaleFactor (:454)
+    const bool stages = elapsed_ms && np_stage_events();
+    std::vector<hipEvent_t> ev;
+    if (stages) {
+        ev.assign(3 * K + 1, nullptr);
+        for (hipEvent_t& e : ev)
+            if (hipEventCreate(&e) != hipSuccess) { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); return MSORB_E_HIP; }
+    }
+    size_t e = 0;   // events recorded
+    const BlockTrip trip{d, h, L.in_bytes, d + o_m, kn1 * 4, h + o_m, d + o_m, L.end - o_m};
+    const int rc = round_trip(scr, "create_new_map_points_kf", trip, elapsed_ms, [&](hipStream_t s) {
+        (void)hipMemsetAsync(d + o_nm, 0, L.end - o_nm, s);   // nmatches, x3D and status of the neighbours that launch nothing
+        if (stages) (void)hipEventRecord(ev[e++], s);
+        for (size_t k = 0; k < K; k++) {
+            const int cnt = item0[k + 1] - item0[k];
+            if (cnt == 0) continue;
+            int* match12 = (int*)(d + o_m) + k * (size_t)n1;
+            hipLaunchKernelGGL(triangulation_match_kernel, dim3((unsigned)cnt), dim3(64), w.lds(), s,
+                               (const BowItem*)(d + o_it) + item0[k], (const TriConst*)(d + o_c), st->d_desc, st->d_desc, d + o_fl, d + o_fl,
+                               st->d_xy, st->d_tr, st->d_feat, st->d_feat, call->coarse, match12);
+            if (stages) (void)hipEventRecord(ev[e++], s);
+            hipLaunchKernelGGL(pair_histogram_kernel, dim3(1), dim3(256), 0, s, (const PairPost*)(d + o_po) + k, st->d_angle, st->d_angle,
+                               call->check_orientation, (int*)(d + o_m), (int*)nullptr, (int*)(d + o_nm) + k);
+            if (stages) (void)hipEventRecord(ev[e++], s);
+            hipLaunchKernelGGL(new_points_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, (const NpSide*)(d + o_sd), (int)k + 1,
+                               (const float*)(d + o_lv), d + o_fl, (const float*)(d + o_ur), (const float*)(d + o_dp), st->d_xy, st->d_tr,
+                               match12, call->inertial, call->th_far, ratio_factor, d + o_st + k * (size_t)n1,
+                               (float*)(d + o_x) + 3 * k * (size_t)n1);
+            if (stages) (void)hipEventRecord(ev[e++], s);
+        }
+    });
+    if (stages && rc == MSORB_OK) {
+        g_np_stage_ms[0] = g_np_stage_ms[1] = g_np_stage_ms[2] = 0;
+        for (size_t i = 1; i < e; i++) {
+            float ms = 0;
+            if (hipEventElapsedTime(&ms, ev[i - 1], ev[i]) == hipSuccess) g_np_stage_ms[(i - 1) % 3] += ms;
+        }
+    }
+    if (stages)   // (a failed trip has released the scratch, the device is still current)
+        for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+    if (rc) return rc;
+    for (size_t k = 0; k < K; k++) {
+        msorb_new_points_neighbour& N = nb[k];
+        std::memcpy(N.match12, h + o_m + k * (size_t)n1 * 4, (size_t)n1 * 4);
+        std::memcpy(N.x3D, h + o_x + k * (size_t)n1 * 12, (size_t)n1 * 12);
+        std::memcpy(N.status, h + o_st + k * (size_t)n1, (size_t)n1);
+        N.nmatches = ((const int*)(h + o_nm))[k];
+        for (int i = 0; i < n1; i++) N.n_created += N.status[i] >= MSORB_NP_TRIANGULATED && N.status[i] <= MSORB_NP_STEREO2;
+    }
     return MSORB_OK;
 }

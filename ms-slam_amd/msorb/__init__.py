@@ -1967,3 +1967,89 @@ def local_ba_stage_ms():
     ms = np.zeros(4, np.float32)
     _check(_ba_lib().msorb_local_ba_stage_ms(_np_ptr(ms)), "msorb_local_ba_stage_ms")
     return dict(zip(("linearise", "schur", "solve", "trial"), (float(v) for v in ms)))
+
+
+EXPORTS = EXPORTS + ("msorb_create_new_map_points_kf", "msorb_create_new_map_points_stage_ms")
+
+NP_NONE, NP_TRIANGULATED, NP_STEREO1, NP_STEREO2, NP_LOW_PARALLAX, NP_NULL_W, NP_STEREO_DEPTH, NP_BEHIND1, NP_BEHIND2, NP_REPROJ1, \
+    NP_REPROJ2, NP_ZERO_DIST, NP_FAR, NP_SCALE_RATIO = range(14)   # MSORB_NP_* (status of a query of CreateNewMapPoints)
+
+
+class NewPointsGeometry(C.Structure):   # msorb_new_points_geometry
+    _fields_ = [("Tcw", C.c_float * 12), ("Ow", C.c_float * 3)] + \
+               [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf")] + \
+               [("u_right", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class NewPointsCall(C.Structure):       # msorb_new_points_call
+    _fields_ = [("kf1", C.c_int), ("valid1", C.c_void_p), ("g1", NewPointsGeometry), ("coarse", C.c_int),
+                ("check_orientation", C.c_int), ("inertial", C.c_int), ("th_far", C.c_float)]
+
+
+class NewPointsNeighbour(C.Structure):  # msorb_new_points_neighbour
+    _fields_ = [("kf2", C.c_int), ("avail2", C.c_void_p), ("g2", NewPointsGeometry), ("F12", C.c_float * 9), ("ep", C.c_float * 2),
+                ("match12", C.c_void_p), ("status", C.c_void_p), ("x3D", C.c_void_p), ("nmatches", C.c_int), ("n_created", C.c_int)]
+
+
+def _np_geometry(g, src, keep):
+    """src: dict Tcw [3, 4], Ow [3], fx fy cx cy invfx invfy mb mbf, u_right [n], depth [n] (None: a null pointer)"""
+    g.Tcw[:] = [float(x) for x in np.asarray(src["Tcw"], np.float32).reshape(12)]
+    g.Ow[:] = [float(x) for x in np.asarray(src["Ow"], np.float32).reshape(3)]
+    for k in ("fx", "fy", "cx", "cy", "invfx", "invfy", "mb", "mbf"):
+        setattr(g, k, float(np.float32(src[k])))
+    for k in ("u_right", "depth"):
+        a = None if src.get(k) is None else _c(src[k], np.float32)
+        keep.append(a)
+        setattr(g, k, None if a is None else _np_ptr(a))
+
+
+def _create_new_map_points(self, call, neighbours, timing=False):
+    """msorb_create_new_map_points_kf: the neighbour loop of LocalMapping::CreateNewMapPoints for resident KeyFrames.
+    call: dict kf1, valid1, geometry (see _np_geometry), coarse, check_orientation, inertial, th_far (<= 0: off).
+    neighbours: dicts kf2, avail2, geometry, F12, ep, in the reference's order.
+    -> list of dict(match12 int32 [n1], status uint8 [n1], x3D float32 [n1, 3], nmatches, n_created) and, with timing, the device ms"""
+    n1 = self.n.get(call["kf1"], 0)
+    keep = []
+    c = NewPointsCall()
+    c.kf1 = call["kf1"]
+    v1 = None if call.get("valid1") is None else _c(call["valid1"], np.uint8)
+    c.valid1 = None if v1 is None else _np_ptr(v1)
+    _np_geometry(c.g1, call["geometry"], keep)
+    c.coarse, c.check_orientation = int(bool(call.get("coarse", False))), int(bool(call.get("check_orientation", True)))
+    c.inertial, c.th_far = int(bool(call.get("inertial", False))), float(call.get("th_far", 0.0))
+    arr = (NewPointsNeighbour * max(len(neighbours), 1))()
+    outs = []
+    for k, p in enumerate(neighbours):
+        q = arr[k]
+        q.kf2 = p["kf2"]
+        a2 = None if p.get("avail2") is None else _c(p["avail2"], np.uint8)
+        keep.append(a2)
+        q.avail2 = None if a2 is None else _np_ptr(a2)
+        _np_geometry(q.g2, p["geometry"], keep)
+        q.F12[:] = [float(x) for x in np.asarray(p["F12"], np.float32).reshape(9)]
+        q.ep[:] = [float(x) for x in np.asarray(p["ep"], np.float32).reshape(2)]
+        o = (np.zeros(max(n1, 1), np.int32), np.zeros(max(n1, 1), np.uint8), np.zeros((max(n1, 1), 3), np.float32))
+        outs.append(o)
+        q.match12, q.status, q.x3D = (_np_ptr(a) for a in o)
+    ms = C.c_float()
+    vp = C.c_void_p
+    self.L.msorb_create_new_map_points_kf.argtypes = [vp, vp, vp, C.c_int, vp]
+    _check(self.L.msorb_create_new_map_points_kf(self.h, C.addressof(c), C.addressof(arr), len(neighbours), C.addressof(ms)),
+           "msorb_create_new_map_points_kf")
+    res = [dict(match12=o[0][:n1], status=o[1][:n1], x3D=o[2][:n1], nmatches=arr[k].nmatches, n_created=arr[k].n_created)
+           for k, o in enumerate(outs)]
+    return (res, ms.value) if timing else res
+
+
+def new_map_points_stage_ms():
+    """msorb_create_new_map_points_stage_ms: dict(match, histogram, new_points) in device ms of this thread's last timed
+    create_new_map_points call; needs MSORB_NEW_POINTS_STAGES=1 in the environment before the library is loaded"""
+    ms = np.zeros(3, np.float32)
+    L = lib()
+    L.msorb_create_new_map_points_stage_ms.argtypes = [C.c_void_p]
+    _check(L.msorb_create_new_map_points_stage_ms(_np_ptr(ms)), "msorb_create_new_map_points_stage_ms")
+    return dict(zip(("match", "histogram", "new_points"), (float(v) for v in ms)))
+
+
+KeyFrameStore.create_new_map_points = _create_new_map_points
+KfStore = KeyFrameStore
