@@ -867,6 +867,45 @@ int msorb_local_ba(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_poi
  * errors, cost).  Without the variable: MSORB_E_ARG, zeros. */
 int msorb_local_ba_stage_ms(float ms[4]);
 
+/* Sim3Solver's RANSAC (src/Sim3Solver.cc:228-373) for two pinhole cameras on the device, every hypothesis at once.  Appended to ABI
+ * 6002 as the local bundle adjustment was: MSORB_ABI_VERSION stays 6002.  The draws of :254-265 do not depend on the data, so the
+ * caller draws the minimal sets of all iterations beforehand (DUtils::Random::RandomInt with the swap-with-back rule of :256-264)
+ * and hands them in as index triples; ComputeSim3 (:390-491) and CheckInliers (:494-518) then run for all of them in one launch, and
+ * a second launch applies the loop's sequential rule (:344-366) to the counts in hypothesis order: starting from best_inliers_in
+ * (mnBestInliers), a hypothesis replaces the running best when count >= best, and the scan stops at the first one where that holds
+ * and count > min_inliers (mRansacMinInliers).
+ *   problem   n correspondences, n_hyp triples, fix_scale = mbFixScale, cam1 / cam2 = fx, fy, cx, cy of pCamera1 / pCamera2
+ *             (Pinhole only)
+ *   result    winner: the hypothesis the loop ends on or, not converged, the last one that replaced the best (-1: none reached
+ *             best_inliers_in; the record is then all zero); converged: the stop above happened (bConverge); consumed: the
+ *             iterations the loop went through (mnIterations advances by it: winner + 1 when converged, n_hyp otherwise);
+ *             n_inliers = mnInliersi, s = ms12i, R = mR12i (row major), t = mt12i, T12 = mT12i (row major) of the winner
+ * Problem i owns the correspondences [corr_offset[i], corr_offset[i+1]) of X1 / X2 (3 floats each: mvX3Dc1 / mvX3Dc2) and max_err1 /
+ * max_err2 (mvnMaxError1 / mvnMaxError2, which the reference holds as integers, Sim3Solver.h:85-86: the caller passes the truncated
+ * values as floats) and the hypotheses [hyp_offset[i], hyp_offset[i+1]) of triples (3 indices into the problem's own
+ * correspondences); both offset arrays start at 0 and advance by n / n_hyp.  inlier_out [per correspondence] = the winner's
+ * mvbInliersi (0 without a winner); counts_out [per hypothesis] (may be NULL) = every hypothesis' mnInliersi, also of those behind a
+ * converged winner.  The arithmetic is float, one rounded operation per reference operator (csrc/sim3_device.h); the eigenvector
+ * of :432-441 comes from a cyclic Jacobi iteration and the rotation of :441-447 from that quaternion in algebraic form, so bit
+ * parity with a compiled Eigen / libm is not pinned.  Non-finite results are results: a degenerate triple
+ * gives a NaN transform with no inliers and takes part in the >= rule as in the reference.
+ * MSORB_E_INVALID, before anything is launched and with every output untouched: n < 3, n_hyp < 1, offsets that do not match, an
+ * index of a triple that is negative, >= n or repeated, a null required array.  n_problems == 0 is MSORB_OK.  Flat host arrays,
+ * one upload, two launches, one read-back.  Two calls on the same input return the same bits, and a batch returns the bits of
+ * the single calls.  Re-entrant: every calling thread has its own stream and staging.  *elapsed_ms (may be NULL) = device time
+ * of the two launches. */
+typedef struct msorb_sim3_problem {
+    int n, n_hyp, fix_scale, min_inliers, best_inliers_in;
+    float cam1[4], cam2[4];
+} msorb_sim3_problem;
+typedef struct msorb_sim3_result {
+    int winner, converged, consumed, n_inliers;
+    float s, R[9], t[3], T12[16];
+} msorb_sim3_result;
+int msorb_sim3_ransac_batch(int device, int n_problems, const msorb_sim3_problem* problems, const int* corr_offset,
+                            const int* hyp_offset, const float* X1, const float* X2, const float* max_err1, const float* max_err2,
+                            const int* triples, uint8_t* inlier_out, int* counts_out, msorb_sim3_result* results, float* elapsed_ms);
+
 /* Frame::ComputeStereoMatches (Frame.cc:743-913, median rejection :899-912 included) for every stereo pair of the last
  * msorb_extract_batch() call of `h`, all on the device: pair p = images 2p (left) and 2p+1 (right) of that batch.
  * d_keypoints / d_descriptors / capacity are the arrays that call filled, d_counts[2*n_pairs] the keypoint counts as a

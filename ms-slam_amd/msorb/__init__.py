@@ -2053,3 +2053,52 @@ def new_map_points_stage_ms():
 
 KeyFrameStore.create_new_map_points = _create_new_map_points
 KfStore = KeyFrameStore
+
+
+# ---- Sim3Solver's RANSAC on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_sim3_ransac_batch",)
+
+SIM3_PROBLEM_DTYPE = np.dtype([("n", "<i4"), ("n_hyp", "<i4"), ("fix_scale", "<i4"), ("min_inliers", "<i4"), ("best_inliers_in", "<i4"),
+                               ("cam1", "<f4", 4), ("cam2", "<f4", 4)])                                     # msorb_sim3_problem
+SIM3_RESULT_DTYPE = np.dtype([("winner", "<i4"), ("converged", "<i4"), ("consumed", "<i4"), ("n_inliers", "<i4"), ("s", "<f4"),
+                              ("R", "<f4", (3, 3)), ("t", "<f4", 3), ("T12", "<f4", (4, 4))])                # msorb_sim3_result
+assert SIM3_PROBLEM_DTYPE.itemsize == 52 and SIM3_RESULT_DTYPE.itemsize == 132
+
+
+def sim3_ransac_batch(problems, device=0, timing=False):
+    """msorb_sim3_ransac_batch: Sim3Solver's RANSAC of every problem, all hypotheses in one launch.
+    problems: dicts X1, X2 [n, 3] (mvX3Dc1 / mvX3Dc2), max_err1, max_err2 [n], triples [n_hyp, 3], cam1, cam2 (fx, fy, cx, cy),
+    fix_scale, min_inliers, best_inliers_in (default 0).
+    -> list of dict(result: SIM3_RESULT_DTYPE record, inliers: bool [n] (the winner's), counts: int32 [n_hyp]) and, with timing, the
+    device time of the two launches in ms."""
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_sim3_ransac_batch.argtypes = [ci, ci] + [vp] * 12
+    pr = np.zeros(len(problems), SIM3_PROBLEM_DTYPE)
+    flat = {k: [] for k in ("X1", "X2", "max_err1", "max_err2", "triples")}
+    for r, p in zip(pr, problems):
+        tr = _c(p["triples"], np.int32).reshape(-1, 3)
+        x1 = _c(p["X1"], np.float32).reshape(-1, 3)
+        arrs = dict(X1=x1, X2=_c(p["X2"], np.float32).reshape(-1, 3), max_err1=_c(p["max_err1"], np.float32).reshape(-1),
+                    max_err2=_c(p["max_err2"], np.float32).reshape(-1), triples=tr)
+        if not len(x1) == len(arrs["X2"]) == len(arrs["max_err1"]) == len(arrs["max_err2"]):
+            raise ValueError("X1, X2, max_err1 and max_err2 of a problem differ in length")
+        r["n"], r["n_hyp"] = len(x1), len(tr)
+        r["fix_scale"], r["min_inliers"], r["best_inliers_in"] = int(bool(p["fix_scale"])), p["min_inliers"], p.get("best_inliers_in", 0)
+        r["cam1"], r["cam2"] = np.asarray(p["cam1"], np.float32), np.asarray(p["cam2"], np.float32)
+        for k, a in arrs.items():
+            flat[k].append(a.reshape(-1))
+    cat = {k: np.ascontiguousarray(np.concatenate(v)) if v else np.zeros(0, np.float32) for k, v in flat.items()}
+    corr = np.zeros(len(pr) + 1, np.int32)
+    hyp = np.zeros(len(pr) + 1, np.int32)
+    corr[1:], hyp[1:] = np.cumsum(pr["n"]), np.cumsum(pr["n_hyp"])
+    inl = np.zeros(max(int(corr[-1]), 1), np.uint8)
+    counts = np.zeros(max(int(hyp[-1]), 1), np.int32)
+    res = np.zeros(max(len(pr), 1), SIM3_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_sim3_ransac_batch(device, len(pr), _np_ptr(pr), _np_ptr(corr), _np_ptr(hyp), _np_ptr(cat["X1"]), _np_ptr(cat["X2"]),
+                                     _np_ptr(cat["max_err1"]), _np_ptr(cat["max_err2"]), _np_ptr(cat["triples"]), _np_ptr(inl),
+                                     _np_ptr(counts), _np_ptr(res), C.addressof(ms)), "msorb_sim3_ransac_batch")
+    out = [dict(result=res[i].copy(), inliers=inl[corr[i]:corr[i + 1]].astype(bool), counts=counts[hyp[i]:hyp[i + 1]].copy())
+           for i in range(len(pr))]
+    return (out, ms.value) if timing else out
