@@ -906,6 +906,51 @@ int msorb_sim3_ransac_batch(int device, int n_problems, const msorb_sim3_problem
                             const int* hyp_offset, const float* X1, const float* X2, const float* max_err1, const float* max_err2,
                             const int* triples, uint8_t* inlier_out, int* counts_out, msorb_sim3_result* results, float* elapsed_ms);
 
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:1986-2242 and :2244-2429) for two pinhole cameras on the device, after the gathering
+ * loops: the 7-DoF Sim3 vertex over the EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ pair of every correspondence, g2o's
+ * Levenberg loop and both classifications in ONE launch, in double.  Appended to ABI 6002 as the Sim3 RANSAC was:
+ * MSORB_ABI_VERSION stays 6002.  This fork comments linearizeOplus out on both edges (OptimizableTypes.h:192,213), so g2o
+ * differentiates numerically (core/base_binary_edge.hpp:131-205, central differences, delta = 1e-9, through oplus); the device
+ * does the same.  The routine: optimize(its[0]) with Huber (delta = (float)sqrt(th2)) over all pairs, run whenever n >= 1; the
+ * first classification reads the chi2 the last trial left and drops a pair when either chi2 > th2 (n_bad of them), the others
+ * lose the kernel; with n - n_bad < min_pairs the reference returns 0 before it writes g2oS12: status 1, n_in 0, the estimate
+ * repeats the input, the flags are those of the first classification; otherwise optimize(n_bad > 0 ? its[1] : its[2]) (a fresh
+ * run), computeError of the survivors at the final estimate and the final classification: status 0, n_in = the survivors that
+ * pass, the estimate in double.  The reference passes its = {5, 10, 5} and min_pairs = 10 (:2211) or 5 (:2397).
+ * Nothing normalises the quaternion (g2o::Sim3 does not).  Non-finite results are results: a point with z <= 0 after a map
+ * gives an infinite or negative projection and takes part as in the reference. */
+typedef struct msorb_sim3_opt_problem {
+    double q[4], t[3], s;               /* g2oS12: rotation x, y, z, w, translation, scale */
+    float cam1[4], cam2[4];             /* fx, fy, cx, cy of pKF1->mpCamera / pKF2->mpCamera (Pinhole only) */
+    float th2;
+    int fix_scale;                      /* bFixScale */
+    int min_pairs;
+    int its[3];                         /* each >= 1 */
+    int n;                              /* pairs */
+    int reserved;                       /* 0 */
+} msorb_sim3_opt_problem;
+typedef struct msorb_sim3_opt_result {
+    double q[4], t[3], s;               /* the estimate; the input again with status 1 */
+    int status;                         /* 0 optimised; 1 fewer than min_pairs pairs left after the first classification */
+    int n_pairs, n_bad, n_in;           /* nCorrespondences, nBad, the return value */
+    int iterations[2], rejected_trials[2];   /* per optimize() call: solve() calls made, trials popped; -1 = not run */
+} msorb_sim3_opt_result;
+/* Pairs up to which a problem is held in registers; a larger one walks global memory (same additions, same result). */
+int msorb_sim3_optimization_capacity(void);
+/* n_problems independent calls as flat host arrays: one upload, one launch, one read-back.  Problem i owns the pairs
+ * [pair_offset[i], pair_offset[i+1]) (pair_offset[0] = 0, the difference = problems[i].n) of P1c / P2c (3 floats per pair: the
+ * floats R1w*P3D1w + t1w and R2w*P3D2w + t2w that the reference casts to double), obs1 / obs2 (2 floats per pair) and
+ * inv_sigma2_1 / inv_sigma2_2.  bad_out [per pair]: 0 kept, 1 bad at the first classification, 2 bad at the final one;
+ * chi2_out [2 doubles per pair: e12, e21] (may be NULL) = what the last classification a pair took part in read.
+ * MSORB_E_INVALID, before anything is launched and with every output untouched: a null required array, offsets that do not match,
+ * n < 0, an entry of its below 1.  n_problems == 0 is MSORB_OK.  Two calls on the same input return the same bits, and a batch
+ * returns the bits of the single calls.  Re-entrant: every calling thread has its own stream and staging.  *elapsed_ms (may be
+ * NULL) = device time of the kernel. */
+int msorb_sim3_optimization_batch(int device, int n_problems, const msorb_sim3_opt_problem* problems, const int* pair_offset,
+                                  const float* P1c, const float* P2c, const float* obs1, const float* obs2,
+                                  const float* inv_sigma2_1, const float* inv_sigma2_2, uint8_t* bad_out, double* chi2_out,
+                                  msorb_sim3_opt_result* results, float* elapsed_ms);
+
 /* Frame::ComputeStereoMatches (Frame.cc:743-913, median rejection :899-912 included) for every stereo pair of the last
  * msorb_extract_batch() call of `h`, all on the device: pair p = images 2p (left) and 2p+1 (right) of that batch.
  * d_keypoints / d_descriptors / capacity are the arrays that call filled, d_counts[2*n_pairs] the keypoint counts as a

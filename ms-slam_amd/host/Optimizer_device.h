@@ -1,4 +1,5 @@
-// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037) on the device entry of libmsorb (msorb_pose_optimization_batch /
+// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037), LocalBundleAdjustment and the two OptimizeSim3 (further down), each on
+// its device entry of libmsorb.  First PoseOptimization (msorb_pose_optimization_batch /
 // msorb_frame_pose_optimization), written against the reference's own types by name (a template: this header compiles inside
 // MS-SLAM, where Frame / MapPoint are the real classes, and in tests/dropin_poseopt_main.cc, where they are minimal stand-ins
 // with the same member names).
@@ -315,6 +316,188 @@ bool LocalBundleAdjustment(KFPtr pKF, bool* pbStopFlag, MapT* pMap, int& num_fix
     }
     pMap->IncreaseChangeIndex();                                                                         // :1406
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::OptimizeSim3 (src/Optimizer.cc:1986-2242 and :2244-2429) on msorb_sim3_optimization_batch.
+//
+//   int ORB_SLAM3::msorb_host::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints)
+//   int ORB_SLAM3::msorb_host::OptimizeSim3(pKF1, pKF2, vpMatches1, vpMatches2, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints)
+//
+// the reference's two parameter lists, and its effects: vpMatches1[idx] (and vpMatches2[idx] in the second form) reset for the
+// pairs that either classification drops, g2oS12 written only when the second optimisation was made, mAcumHessian set to zero
+// there and nothing more (the reference never fills it), the return value nIn (0 after the early return of :2211-2212 /
+// :2397-2398, which leaves g2oS12 and mAcumHessian as they were).
+//
+// -1 = NOT handled, nothing touched, the caller keeps Optimizer::OptimizeSim3: a camera that is not Pinhole, a KeyFrame with
+// mpCamera2, a gathered keypoint with octave > 10 (for which :2110 and :2134 leave a half-added edge in the reference's graph).
+//
+// What runs where.  The gathering loops (:2039-2170, :2295-2361) stay host code: they read the map points.  Both optimisations
+// and both classifications are one device launch.
+struct Sim3OptPairs {
+    std::vector<float> P1c, P2c, obs1, obs2, w1, w2;
+    std::vector<size_t> vnIndexEdge;
+    int nCorrespondences = 0;
+    bool handled = true;
+    void add(size_t i, const float* p1, const float* p2, float u1, float v1, float u2, float v2, float s1, float s2) {
+        P1c.insert(P1c.end(), p1, p1 + 3); P2c.insert(P2c.end(), p2, p2 + 3);
+        obs1.push_back(u1); obs1.push_back(v1); obs2.push_back(u2); obs2.push_back(v2);
+        w1.push_back(s1); w2.push_back(s2);
+        vnIndexEdge.push_back(i);
+    }
+};
+
+template <class KFPtr>
+bool Sim3OptPinholePair(const KFPtr& pKF1, const KFPtr& pKF2) {
+    if (pKF1->mpCamera2 || pKF2->mpCamera2) return false;
+    return pKF1->mpCamera->GetType() == pKF1->mpCamera->CAM_PINHOLE && pKF2->mpCamera->GetType() == pKF2->mpCamera->CAM_PINHOLE;
+}
+
+// :2039-2170
+template <class KFPtr, class MPPtr>
+Sim3OptPairs GatherSim3Pairs(KFPtr pKF1, KFPtr pKF2, const std::vector<MPPtr>& vpMatches1, const bool bAllPoints) {
+    Sim3OptPairs G;
+    if (!Sim3OptPinholePair(pKF1, pKF2)) { G.handled = false; return G; }
+    const auto R1w = pKF1->GetRotation();
+    const auto t1w = pKF1->GetTranslation();
+    const auto R2w = pKF2->GetRotation();
+    const auto t2w = pKF2->GetTranslation();
+    const int N = vpMatches1.size();
+    const std::vector<MPPtr> vpMapPoints1 = pKF1->GetMapPointMatches();
+    for (int i = 0; i < N; i++) {
+        if (!vpMatches1[i]) continue;                                                                    // :2040
+        MPPtr pMP1 = vpMapPoints1[i];
+        MPPtr pMP2 = vpMatches1[i];
+        const int i2 = std::get<0>(pMP2->GetIndexInKeyFrame(pKF2));                                      // :2049
+        if (!(pMP1 && pMP2)) continue;                        // :2075-2091: at most a fixed vertex that no edge uses
+        if (pMP1->isBad() || pMP2->isBad()) continue;                                                    // :2055, :2071-2074
+        const auto P3D1w = pMP1->GetWorldPos();
+        const auto P3D1c = (R1w * P3D1w + t1w).eval();                                                           // :2058
+        const auto P3D2w = pMP2->GetWorldPos();
+        const auto P3D2c = (R2w * P3D2w + t2w).eval();                                                           // :2066
+        if (i2 < 0 && !bAllPoints) continue;                                                             // :2093
+        if (P3D2c(2) < 0) continue;                                                                      // :2100
+        G.nCorrespondences++;                                                                            // :2105
+        const auto kpUn1 = pKF1->GetKeyUn(i);
+        if (kpUn1.octave > 10) { G.handled = false; return G; }                                          // :2110
+        const float invSigmaSquare1 = pKF1->mvInvLevelSigma2[kpUn1.octave];                              // :2120
+        float x2, y2;
+        int octave2;
+        if (i2 >= 0) {                                                                                   // :2132-2139
+            const auto kpUn2 = pKF2->GetKeyUn(i2);
+            if (kpUn2.octave > 10) { G.handled = false; return G; }
+            x2 = kpUn2.pt.x; y2 = kpUn2.pt.y;
+            octave2 = kpUn2.octave;
+        } else {                                                                                         // :2140-2150
+            float invz = 1 / P3D2c(2);
+            x2 = P3D2c(0) * invz;
+            y2 = P3D2c(1) * invz;
+            octave2 = pMP2->mnTrackScaleLevel;
+        }
+        const float invSigmaSquare2 = pKF2->mvInvLevelSigma2[octave2];                                   // :2157
+        const float p1[3] = {P3D1c(0), P3D1c(1), P3D1c(2)}, p2[3] = {P3D2c(0), P3D2c(1), P3D2c(2)};
+        G.add((size_t)i, p1, p2, kpUn1.pt.x, kpUn1.pt.y, x2, y2, invSigmaSquare1, invSigmaSquare2);
+    }
+    return G;
+}
+
+// :2295-2361
+template <class KFPtr, class MPPtr>
+Sim3OptPairs GatherSim3Pairs(KFPtr pKF1, KFPtr pKF2, const std::vector<MPPtr>& vpMatches1, const std::vector<MPPtr>& vpMatches2) {
+    Sim3OptPairs G;
+    if (!Sim3OptPinholePair(pKF1, pKF2)) { G.handled = false; return G; }
+    const auto R1w = pKF1->GetRotation();
+    const auto t1w = pKF1->GetTranslation();
+    const auto R2w = pKF2->GetRotation();
+    const auto t2w = pKF2->GetTranslation();
+    const auto O1w = pKF1->GetCameraCenter();
+    const auto O2w = pKF2->GetCameraCenter();
+    auto* pCamera1 = pKF1->mpCamera;
+    auto* pCamera2 = pKF2->mpCamera;
+    const int N = vpMatches1.size();
+    for (int i = 0; i < N; i++) {
+        MPPtr pMP1 = vpMatches1[i];
+        MPPtr pMP2 = vpMatches2[i];
+        if (!pMP1 || !pMP2 || pMP1->isBad() || pMP2->isBad()) continue;                                  // :2298
+        const auto P3D1w = pMP1->GetWorldPos();
+        const auto P3D1c = (R1w * P3D1w + t1w).eval();                                                           // :2306
+        const auto P3D2w = pMP2->GetWorldPos();
+        const auto P3D2c = (R2w * P3D2w + t2w).eval();                                                           // :2314
+        G.nCorrespondences++;
+        const auto obs1 = pCamera1->project(P3D1c);                                                      // :2323, in float
+        const auto PO1 = P3D1w - O1w;
+        const float dist1 = PO1.norm();
+        const int nPredictedLevel1 = pMP1->PredictScale(dist1, pKF1);                                    // :2331
+        const float invSigmaSquare1 = pKF1->mvInvLevelSigma2[nPredictedLevel1];
+        const auto obs2 = pCamera2->project(P3D2c);                                                      // :2341
+        const auto PO2 = P3D2w - O2w;
+        const float dist2 = PO2.norm();
+        const int nPredictedLevel2 = pMP2->PredictScale(dist2, pKF2);                                    // :2349
+        const float invSigmaSquare2 = pKF2->mvInvLevelSigma2[nPredictedLevel2];
+        const float p1[3] = {P3D1c(0), P3D1c(1), P3D1c(2)}, p2[3] = {P3D2c(0), P3D2c(1), P3D2c(2)};
+        G.add((size_t)i, p1, p2, obs1(0), obs1(1), obs2(0), obs2(1), invSigmaSquare1, invSigmaSquare2);
+    }
+    return G;
+}
+
+// :2172-2241 / :2363-2428 on the gathered pairs.  bad_out [G.vnIndexEdge.size()] receives the flags.
+template <class KFPtr, class Sim3T, class HessianT>
+int RunSim3Optimization(const Sim3OptPairs& G, KFPtr pKF1, KFPtr pKF2, Sim3T& g2oS12, const float th2, const bool bFixScale,
+                        HessianT& mAcumHessian, int min_pairs, std::vector<uint8_t>& bad, int device) {
+    const int n = (int)G.vnIndexEdge.size();
+    bad.assign((size_t)n, 0);
+    if (n == 0) return 0;                                     // optimize() on an empty graph, then the early return
+    msorb_sim3_opt_problem p{};
+    const auto& r = g2oS12.rotation();
+    const auto& t = g2oS12.translation();
+    p.q[0] = r.x(); p.q[1] = r.y(); p.q[2] = r.z(); p.q[3] = r.w();
+    p.t[0] = t[0]; p.t[1] = t[1]; p.t[2] = t[2];
+    p.s = g2oS12.scale();
+    for (int k = 0; k < 4; k++) { p.cam1[k] = pKF1->mpCamera->getParameter(k); p.cam2[k] = pKF2->mpCamera->getParameter(k); }
+    p.th2 = th2;
+    p.fix_scale = bFixScale ? 1 : 0;
+    p.min_pairs = min_pairs;
+    p.its[0] = 5; p.its[1] = 10; p.its[2] = 5;                                                           // :2174, :2205-2209
+    p.n = n;
+    const int off[2] = {0, n};
+    msorb_sim3_opt_result res;
+    if (msorb_sim3_optimization_batch(device, 1, &p, off, G.P1c.data(), G.P2c.data(), G.obs1.data(), G.obs2.data(), G.w1.data(),
+                                      G.w2.data(), bad.data(), nullptr, &res, nullptr) != MSORB_OK)
+        fail_call("msorb_sim3_optimization_batch");
+    if (res.status != 0) return 0;                                                                       // :2211-2212, :2397-2398
+    mAcumHessian.setZero();                                                                              // :2219, :2405
+    typedef typename std::decay<decltype(g2oS12.rotation())>::type QuatT;
+    typedef typename std::decay<decltype(g2oS12.translation())>::type VecT;
+    g2oS12 = Sim3T(QuatT(res.q[3], res.q[0], res.q[1], res.q[2]), VecT(res.t[0], res.t[1], res.t[2]), res.s);   // :2239, :2426
+    return res.n_in;
+}
+
+template <class KFPtr, class MPPtr, class Sim3T, class HessianT>
+int OptimizeSim3(KFPtr pKF1, KFPtr pKF2, std::vector<MPPtr>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale,
+                 HessianT& mAcumHessian, const bool bAllPoints = false, int device = 0) {
+    const Sim3OptPairs G = GatherSim3Pairs(pKF1, pKF2, vpMatches1, bAllPoints);
+    if (!G.handled) return -1;
+    std::vector<uint8_t> bad;
+    const int nIn = RunSim3Optimization(G, pKF1, pKF2, g2oS12, th2, bFixScale, mAcumHessian, 10, bad, device);
+    for (size_t k = 0; k < bad.size(); k++)
+        if (bad[k]) vpMatches1[G.vnIndexEdge[k]].reset();                                                // :2187, :2231
+    return nIn;
+}
+
+template <class KFPtr, class MPPtr, class Sim3T, class HessianT>
+int OptimizeSim3(KFPtr pKF1, KFPtr pKF2, std::vector<MPPtr>& vpMatches1, std::vector<MPPtr>& vpMatches2, Sim3T& g2oS12, const float th2,
+                 const bool bFixScale, HessianT& mAcumHessian, const bool bAllPoints = false, int device = 0) {
+    (void)bAllPoints;                                         // the reference's second form does not read it either
+    const Sim3OptPairs G = GatherSim3Pairs(pKF1, pKF2, vpMatches1, vpMatches2);
+    if (!G.handled) return -1;
+    std::vector<uint8_t> bad;
+    const int nIn = RunSim3Optimization(G, pKF1, pKF2, g2oS12, th2, bFixScale, mAcumHessian, 5, bad, device);
+    for (size_t k = 0; k < bad.size(); k++)
+        if (bad[k]) {
+            vpMatches1[G.vnIndexEdge[k]].reset();                                                        // :2377-2378, :2417-2418
+            vpMatches2[G.vnIndexEdge[k]].reset();
+        }
+    return nIn;
 }
 
 }  // namespace msorb_host

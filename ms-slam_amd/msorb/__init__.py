@@ -2102,3 +2102,59 @@ def sim3_ransac_batch(problems, device=0, timing=False):
     out = [dict(result=res[i].copy(), inliers=inl[corr[i]:corr[i + 1]].astype(bool), counts=counts[hyp[i]:hyp[i + 1]].copy())
            for i in range(len(pr))]
     return (out, ms.value) if timing else out
+
+
+# ---- Optimizer::OptimizeSim3 on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_sim3_optimization_capacity", "msorb_sim3_optimization_batch")
+
+SIM3_OPT_PROBLEM_DTYPE = np.dtype([("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8"), ("cam1", "<f4", 4), ("cam2", "<f4", 4), ("th2", "<f4"),
+                                   ("fix_scale", "<i4"), ("min_pairs", "<i4"), ("its", "<i4", 3), ("n", "<i4"),
+                                   ("reserved", "<i4")])                                                    # msorb_sim3_opt_problem
+SIM3_OPT_RESULT_DTYPE = np.dtype([("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8"), ("status", "<i4"), ("n_pairs", "<i4"), ("n_bad", "<i4"),
+                                  ("n_in", "<i4"), ("iterations", "<i4", 2), ("rejected_trials", "<i4", 2)])   # msorb_sim3_opt_result
+assert SIM3_OPT_PROBLEM_DTYPE.itemsize == 128 and SIM3_OPT_RESULT_DTYPE.itemsize == 96
+
+
+def _sim3_opt_lib():
+    L = lib()
+    L.msorb_sim3_optimization_capacity.argtypes = []
+    L.msorb_sim3_optimization_batch.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 12
+    return L
+
+
+def sim3_optimization_capacity():
+    """pairs up to which the kernel keeps a problem in registers"""
+    return _sim3_opt_lib().msorb_sim3_optimization_capacity()
+
+
+def sim3_opt_problem(q, t, s, cam1, cam2, th2, fix_scale, min_pairs, n=0, its=(5, 10, 5)):
+    """one msorb_sim3_opt_problem record; q = x, y, z, w of g2oS12's rotation; cam = (fx, fy, cx, cy)"""
+    p = np.zeros(1, SIM3_OPT_PROBLEM_DTYPE)
+    p["q"], p["t"], p["s"] = np.asarray(q, np.float64), np.asarray(t, np.float64), s
+    p["cam1"], p["cam2"], p["th2"] = np.asarray(cam1, np.float32), np.asarray(cam2, np.float32), th2
+    p["fix_scale"], p["min_pairs"], p["its"], p["n"] = int(bool(fix_scale)), min_pairs, its, n
+    return p
+
+
+def sim3_optimization_batch(problems, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, device=0, timing=False, chi2=True):
+    """msorb_sim3_optimization_batch: Optimizer::OptimizeSim3 of every problem in one launch.  problems: SIM3_OPT_PROBLEM_DTYPE
+    records whose n partition the flat arrays P1c, P2c [M, 3], obs1, obs2 [M, 2], inv_sigma2_1, inv_sigma2_2 [M] in order.
+    -> (results: SIM3_OPT_RESULT_DTYPE [n_problems], bad: uint8 [M] (0 kept, 1 / 2 bad at the first / final classification),
+    chi2: float64 [M, 2] or None) and, with timing, the kernel's device time in ms."""
+    L = _sim3_opt_lib()
+    pr = _c(problems, SIM3_OPT_PROBLEM_DTYPE).reshape(-1)
+    off = np.zeros(len(pr) + 1, np.int32)
+    off[1:] = np.cumsum(pr["n"])
+    m = int(off[-1])
+    arrs = [_c(a, np.float32).reshape(-1) for a in (P1c, P2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2)]
+    if [len(a) for a in arrs] != [3 * m, 3 * m, 2 * m, 2 * m, m, m]:
+        raise ValueError("the flat arrays do not hold sum(problems.n) pairs")
+    res = np.zeros(max(len(pr), 1), SIM3_OPT_RESULT_DTYPE)
+    bad = np.zeros(max(m, 1), np.uint8)
+    c2 = np.zeros((max(m, 1), 2), np.float64) if chi2 else None
+    ms = C.c_float()
+    _check(L.msorb_sim3_optimization_batch(device, len(pr), _np_ptr(pr), _np_ptr(off), *[_np_ptr(a) for a in arrs], _np_ptr(bad),
+                                           _np_ptr(c2) if chi2 else None, _np_ptr(res), C.addressof(ms)),
+           "msorb_sim3_optimization_batch")
+    out = (res[:len(pr)], bad[:m], c2[:m] if chi2 else None)
+    return out + (ms.value,) if timing else out
