@@ -1197,6 +1197,49 @@ int msorb_track_batch(int device, int n_frames, const msorb_keypoint* d_keypoint
                       float th_far_points, int* d_topk, uint8_t* d_track_in_view, int* d_cell_begin, int* d_cell_idx,
                       float* elapsed_ms, unsigned long long* n_pairs);
 
+/* MLPnPsolver's RANSAC (src/MLPnPsolver.cpp:143-266) for a pinhole camera on the device, every hypothesis at once.  Appended to ABI
+ * 6002 as the Sim3 RANSAC was: MSORB_ABI_VERSION stays 6002.  The draws of :163-183 do not depend on the data, so the caller draws
+ * the minimal sets of all iterations beforehand (DUtils::Random::RandomInt with the swap-with-back rule of :173-182) and hands them
+ * in as sets of six indices; computePose (:399-701) and CheckInliers (:305-336) then run for all of them in one launch, and a
+ * second launch applies the loop's sequential rule (:212-263) to the counts in hypothesis order: starting from best_inliers_in
+ * (mnBestInliers), a hypothesis with count >= min_inliers (mRansacMinInliers) raises the best when count > best, and the scan
+ * stops at the first hypothesis with count > min_inliers, which is handed out whether or not it is the best (Refine(), :338-396,
+ * computes into a local nothing reads and counts the current hypothesis again).
+ *   problem   n correspondences, n_hyp sets, cam = fx, fy, cx, cy of mpCamera (Pinhole only)
+ *   result    winner: converged, the hypothesis the loop returned at; otherwise the last one that raised the best (-1: none did;
+ *             the record is then all zero); converged: Refine() returned true there; consumed: the iterations the loop went
+ *             through (mnIterations advances by it: winner + 1 when converged, n_hyp otherwise); n_inliers = mnInliersi of the
+ *             winner, R (row major) / t = its mRi / mti, Tcw = mRefinedTcw / mBestTcw (row major): R and t narrowed to float
+ * Problem i owns the correspondences [corr_offset[i], corr_offset[i+1]) of p2d (2 floats each: mvP2D, from which the bearings are
+ * taken as Pinhole::unproject followed by / z, :78-80), p3d_w (3 floats each: mvP3Dw) and max_err (mvMaxError) and the hypotheses
+ * [hyp_offset[i], hyp_offset[i+1]) of sets (6 indices into the problem's own correspondences); both offset arrays start at 0 and
+ * advance by n / n_hyp.  inlier_out [per correspondence] = the winner's mvbInliersi (0 without a winner); counts_out [per
+ * hypothesis] (may be NULL) = every hypothesis' mnInliersi, also of those behind a converged winner; hyp_pose_out (may be NULL)
+ * [per hypothesis] = R (9, row major) then t (3); hyp_flags_out (may be NULL) [per hypothesis]: bit 0 the planar branch was taken,
+ * bits 1-3 the Gauss-Newton updates applied (0-5), bit 4 the loop was left by the break of :787.  computePose is double, one
+ * rounded operation per reference operator (csrc/mlpnp_device.h), with the choices the reference leaves to Eigen fixed there, so
+ * bit parity with a compiled Eigen / libm is not pinned; CheckInliers narrows to float where the reference
+ * does.  The N-point computePose of Refine() is dead work and is not done.  Non-finite poses are results: they count no inlier
+ * and take part in the rule.
+ * MSORB_E_INVALID, before anything is launched and with every output untouched: n < 6, n_hyp < 1, offsets that do not match, an
+ * index of a set that is negative, >= n or repeated within its set, a null required array.  n_problems == 0 is MSORB_OK.  Flat host
+ * arrays, one upload, two launches, one read-back.  Two calls on the same input return the same bits, and a batch returns the
+ * bits of the single calls.  Re-entrant: every calling thread has its own stream and staging.  *elapsed_ms (may be NULL) = device
+ * time of the two launches. */
+typedef struct msorb_mlpnp_problem {
+    int n, n_hyp, min_inliers, best_inliers_in;
+    float cam[4];
+} msorb_mlpnp_problem;
+typedef struct msorb_mlpnp_result {
+    int winner, converged, consumed, n_inliers;
+    float Tcw[16];
+    double R[9], t[3];
+} msorb_mlpnp_result;
+int msorb_mlpnp_ransac_batch(int device, int n_problems, const msorb_mlpnp_problem* problems, const int* corr_offset,
+                             const int* hyp_offset, const float* p2d, const float* p3d_w, const float* max_err, const int* sets,
+                             uint8_t* inlier_out, int* counts_out, double* hyp_pose_out, uint8_t* hyp_flags_out,
+                             msorb_mlpnp_result* results, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2158,3 +2158,55 @@ def sim3_optimization_batch(problems, P1c, P2c, obs1, obs2, inv_sigma2_1, inv_si
            "msorb_sim3_optimization_batch")
     out = (res[:len(pr)], bad[:m], c2[:m] if chi2 else None)
     return out + (ms.value,) if timing else out
+
+
+# ---- MLPnPsolver's RANSAC on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_mlpnp_ransac_batch",)
+
+MLPNP_PROBLEM_DTYPE = np.dtype([("n", "<i4"), ("n_hyp", "<i4"), ("min_inliers", "<i4"), ("best_inliers_in", "<i4"),
+                                ("cam", "<f4", 4)])                                                          # msorb_mlpnp_problem
+MLPNP_RESULT_DTYPE = np.dtype([("winner", "<i4"), ("converged", "<i4"), ("consumed", "<i4"), ("n_inliers", "<i4"),
+                               ("Tcw", "<f4", (4, 4)), ("R", "<f8", (3, 3)), ("t", "<f8", 3)])                 # msorb_mlpnp_result
+assert MLPNP_PROBLEM_DTYPE.itemsize == 32 and MLPNP_RESULT_DTYPE.itemsize == 176
+MLPNP_PLANAR, MLPNP_BROKE = 1, 16      # hyp_flags_out: bit 0, bit 4; (flags >> 1) & 7 = the Gauss-Newton updates applied
+
+
+def mlpnp_ransac_batch(problems, device=0, timing=False):
+    """msorb_mlpnp_ransac_batch: MLPnPsolver's RANSAC of every problem, all hypotheses in one launch.
+    problems: dicts p2d [n, 2] (mvP2D), p3d [n, 3] (mvP3Dw), max_err [n] (mvMaxError), sets [n_hyp, 6], cam (fx, fy, cx, cy),
+    min_inliers, best_inliers_in (default 0).
+    -> list of dict(result: MLPNP_RESULT_DTYPE record, inliers: bool [n] (the winner's), counts: int32 [n_hyp], poses: float64
+    [n_hyp, 12] (R row major, t), flags: uint8 [n_hyp]) and, with timing, the device time of the two launches in ms."""
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_mlpnp_ransac_batch.argtypes = [ci, ci] + [vp] * 13
+    pr = np.zeros(len(problems), MLPNP_PROBLEM_DTYPE)
+    flat = {k: [] for k in ("p2d", "p3d", "max_err", "sets")}
+    for r, p in zip(pr, problems):
+        sets = _c(p["sets"], np.int32).reshape(-1, 6)
+        p2d = _c(p["p2d"], np.float32).reshape(-1, 2)
+        arrs = dict(p2d=p2d, p3d=_c(p["p3d"], np.float32).reshape(-1, 3), max_err=_c(p["max_err"], np.float32).reshape(-1), sets=sets)
+        if not len(p2d) == len(arrs["p3d"]) == len(arrs["max_err"]):
+            raise ValueError("p2d, p3d and max_err of a problem differ in length")
+        r["n"], r["n_hyp"] = len(p2d), len(sets)
+        r["min_inliers"], r["best_inliers_in"] = p["min_inliers"], p.get("best_inliers_in", 0)
+        r["cam"] = np.asarray(p["cam"], np.float32)
+        for k, a in arrs.items():
+            flat[k].append(a.reshape(-1))
+    cat = {k: np.ascontiguousarray(np.concatenate(v)) if v else np.zeros(0, np.float32) for k, v in flat.items()}
+    corr = np.zeros(len(pr) + 1, np.int32)
+    hyp = np.zeros(len(pr) + 1, np.int32)
+    corr[1:], hyp[1:] = np.cumsum(pr["n"]), np.cumsum(pr["n_hyp"])
+    nh = max(int(hyp[-1]), 1)
+    inl = np.zeros(max(int(corr[-1]), 1), np.uint8)
+    counts = np.zeros(nh, np.int32)
+    poses = np.zeros((nh, 12), np.float64)
+    flags = np.zeros(nh, np.uint8)
+    res = np.zeros(max(len(pr), 1), MLPNP_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_mlpnp_ransac_batch(device, len(pr), _np_ptr(pr), _np_ptr(corr), _np_ptr(hyp), _np_ptr(cat["p2d"]), _np_ptr(cat["p3d"]),
+                                      _np_ptr(cat["max_err"]), _np_ptr(cat["sets"]), _np_ptr(inl), _np_ptr(counts), _np_ptr(poses),
+                                      _np_ptr(flags), _np_ptr(res), C.addressof(ms)), "msorb_mlpnp_ransac_batch")
+    out = [dict(result=res[i].copy(), inliers=inl[corr[i]:corr[i + 1]].astype(bool), counts=counts[hyp[i]:hyp[i + 1]].copy(),
+                poses=poses[hyp[i]:hyp[i + 1]].copy(), flags=flags[hyp[i]:hyp[i + 1]].copy()) for i in range(len(pr))]
+    return (out, ms.value) if timing else out
