@@ -1240,6 +1240,52 @@ int msorb_mlpnp_ransac_batch(int device, int n_problems, const msorb_mlpnp_probl
                              uint8_t* inlier_out, int* counts_out, double* hyp_pose_out, uint8_t* hyp_flags_out,
                              msorb_mlpnp_result* results, float* elapsed_ms);
 
+/* TwoViewReconstruction::Reconstruct (src/TwoViewReconstruction.cc:41-129) for a pinhole camera on the device: the monocular
+ * initialisation between msorb_search_for_initialization and CreateInitialMapMonocular.  Appended to ABI 6002 as the MLPnP RANSAC
+ * was: MSORB_ABI_VERSION stays 6002.  One problem per call: no caller has more.  The reference draws all minimal sets before its loops
+ * (:79-98) and has no early exit, so the caller draws them (DUtils::Random::SeedRandOnce(0), RandomInt, the swap-with-back rule of
+ * :83-98) and hands them in; all n_hyp homographies and all n_hyp fundamental matrices are then computed and scored over every match
+ * in one launch, a second launch folds the scores (:172-177, :223-228), takes Reconstruct's branch and forms the 8 (ReconstructH,
+ * :582-690) or 4 (ReconstructF / DecomposeE) motion hypotheses, a third runs CheckRT (:786-901) for each of them; the host part of
+ * the entry takes acos with the host's libm and applies the closing rule (:505-568, :693-733).
+ *   keys1 [n1 x 2], keys2 [n2 x 2]   the pt of mvKeysUn of the reference / current frame; Normalize (:737-784) runs over ALL of them
+ *   matches12 [n1]                   index into keys2 or -1; the match list is its entries >= 0 in ascending order of i (:55-64)
+ *   sets [n_hyp x 8]                 indices into the match list (mvSets)
+ *   fx, fy, cx, cy, sigma            K as Pinhole::toK_ gives it (no skew), mSigma
+ *   h_ratio                          the constant of :119: the reference has 0.50 (its comment names the older 0.40-0.45)
+ *   min_parallax, min_triangulated   the reference passes 1.0 and 50
+ * result: ok = Reconstruct's return value; branch 0 no model (SH + SF == 0), 1 homography, 2 fundamental; winner_h / winner_f the
+ * hypotheses the two folds kept (-1: no score exceeded 0); model = the branch's H21 / F21 (row major); n_motion 8, 4 or 0 (the
+ * return of :597-600); motion_R / motion_t every motion hypothesis in the reference's order; n_good / cosine / parallax per motion
+ * hypothesis: CheckRT's return value, the accepted cosParallax at sorted index min(50, nGood - 1), and acos of it in degrees;
+ * chosen = the hypothesis handed out (-1: none), R / t = T21 (zero when !ok); n_inliers = the N of :478-481 / :574-577.
+ * triangulated [n1] / p3d [n1 x 3] = vbTriangulated and the chosen hypothesis' vP3D, indexed by the keypoint of frame 1 (all zero
+ * when !ok; ReconstructH hands vbTriangulated out and leaves vP3D unassigned, :725-731: p3d here holds the points it dropped).
+ * inlier_out [per match] = the branch winner's vbMatchesInliers.  hyp_score_out / hyp_count_out [2 n_hyp] and hyp_mask_out
+ * [2 n_hyp x matches] (each may be NULL): every hypothesis' score, inlier count and mask, the homographies first.
+ * Float, one rounded operation per reference operator (csrc/two_view_device.h), with what the reference leaves to Eigen fixed there
+ * (DESIGN.md section 15), so bit parity with a compiled Eigen is not pinned.  A match whose triangulation has x3Dh(3) == 0 counts
+ * as not finite (the reference reads an unassigned vector there).
+ * MSORB_E_INVALID, before anything is launched and with every output untouched: fewer than 8 matches, n_hyp < 1, a set index that
+ * is negative, beyond the match count or repeated within its set, a match index >= n2, a null required array (the three hyp_*
+ * outputs and elapsed_ms are optional).  More than 32768 matches: MSORB_E_CAPACITY.  One upload, three launches, one read-back; two
+ * calls on the same input return the same bits.  Re-entrant: every calling thread has its own stream and staging.  *elapsed_ms
+ * (may be NULL) = device time of the three launches. */
+typedef struct msorb_two_view_result {
+    int ok, branch, winner_h, winner_f, n_motion, chosen, n_inliers;
+    float SH, SF, RH;
+    float R[9], t[3];
+    float model[9];
+    int n_good[8];
+    float parallax[8], cosine[8];
+    float motion_R[72], motion_t[24];
+} msorb_two_view_result;
+int msorb_two_view_reconstruct(int device, int n1, const float* keys1, int n2, const float* keys2, const int* matches12,
+                               int n_hyp, const int* sets, float fx, float fy, float cx, float cy, float sigma, double h_ratio,
+                               float min_parallax, int min_triangulated, msorb_two_view_result* result, uint8_t* triangulated,
+                               float* p3d, uint8_t* inlier_out, float* hyp_score_out, int* hyp_count_out, uint8_t* hyp_mask_out,
+                               float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

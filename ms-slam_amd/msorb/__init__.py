@@ -2210,3 +2210,56 @@ def mlpnp_ransac_batch(problems, device=0, timing=False):
     out = [dict(result=res[i].copy(), inliers=inl[corr[i]:corr[i + 1]].astype(bool), counts=counts[hyp[i]:hyp[i + 1]].copy(),
                 poses=poses[hyp[i]:hyp[i + 1]].copy(), flags=flags[hyp[i]:hyp[i + 1]].copy()) for i in range(len(pr))]
     return (out, ms.value) if timing else out
+
+
+# ---- TwoViewReconstruction on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_two_view_reconstruct",)
+
+TWO_VIEW_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("branch", "<i4"), ("winner_h", "<i4"), ("winner_f", "<i4"), ("n_motion", "<i4"),
+                                  ("chosen", "<i4"), ("n_inliers", "<i4"), ("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"),
+                                  ("R", "<f4", (3, 3)), ("t", "<f4", 3), ("model", "<f4", (3, 3)), ("n_good", "<i4", 8),
+                                  ("parallax", "<f4", 8), ("cosine", "<f4", 8), ("motion_R", "<f4", (8, 3, 3)),
+                                  ("motion_t", "<f4", (8, 3))])                                               # msorb_two_view_result
+assert TWO_VIEW_RESULT_DTYPE.itemsize == 604
+TWO_VIEW_NO_MODEL, TWO_VIEW_HOMOGRAPHY, TWO_VIEW_FUNDAMENTAL = 0, 1, 2
+
+
+def _two_view_argtypes(L):
+    vp, ci, cf = C.c_void_p, C.c_int, C.c_float
+    L.msorb_two_view_reconstruct.argtypes = [ci, ci, vp, ci, vp, vp, ci, vp, cf, cf, cf, cf, cf, C.c_double, cf, ci] + [vp] * 8
+    L.msorb_two_view_reconstruct.restype = ci
+
+
+def two_view_reconstruct(keys1, keys2, matches12, sets, cam, sigma=1.0, h_ratio=0.5, min_parallax=1.0, min_triangulated=50, device=0,
+                         timing=False, hypotheses=True):
+    """msorb_two_view_reconstruct: TwoViewReconstruction::Reconstruct with every hypothesis of both models in one launch.
+    keys1 [n1, 2], keys2 [n2, 2] (the pt of mvKeysUn), matches12 [n1] (-1: none), sets [n_hyp, 8] indices into the match list,
+    cam = fx, fy, cx, cy.
+    -> dict(result: TWO_VIEW_RESULT_DTYPE record, triangulated: bool [n1], p3d: float32 [n1, 3], inliers: bool [matches] (the branch
+    winner's) and, with hypotheses, scores: float32 [2, n_hyp], counts: int32 [2, n_hyp], masks: bool [2, n_hyp, matches], the
+    homographies first) and, with timing, the device time of the three launches in ms."""
+    L = lib()
+    _two_view_argtypes(L)
+    k1, k2 = _c(keys1, np.float32).reshape(-1, 2), _c(keys2, np.float32).reshape(-1, 2)
+    m12 = _c(matches12, np.int32).reshape(-1)
+    st = _c(sets, np.int32).reshape(-1, 8)
+    if len(m12) != len(k1):
+        raise ValueError("matches12 must have one entry per keypoint of frame 1")
+    n, H = int((m12 >= 0).sum()), len(st)
+    res = np.zeros(1, TWO_VIEW_RESULT_DTYPE)
+    tri = np.zeros(max(len(k1), 1), np.uint8)
+    p3d = np.zeros((max(len(k1), 1), 3), np.float32)
+    inl = np.zeros(max(n, 1), np.uint8)
+    scores = np.zeros((2, max(H, 1)), np.float32) if hypotheses else None
+    counts = np.zeros((2, max(H, 1)), np.int32) if hypotheses else None
+    masks = np.zeros((2, max(H, 1), max(n, 1)), np.uint8) if hypotheses else None
+    ms = C.c_float()
+    _check(L.msorb_two_view_reconstruct(device, len(k1), _np_ptr(k1), len(k2), _np_ptr(k2), _np_ptr(m12), H, _np_ptr(st), cam[0], cam[1],
+                                        cam[2], cam[3], sigma, h_ratio, min_parallax, min_triangulated, _np_ptr(res), _np_ptr(tri),
+                                        _np_ptr(p3d), _np_ptr(inl), _np_ptr(scores) if hypotheses else None,
+                                        _np_ptr(counts) if hypotheses else None, _np_ptr(masks) if hypotheses else None,
+                                        C.addressof(ms)), "msorb_two_view_reconstruct")
+    out = dict(result=res[0].copy(), triangulated=tri[:len(k1)].astype(bool), p3d=p3d[:len(k1)], inliers=inl[:n].astype(bool))
+    if hypotheses:
+        out.update(scores=scores[:, :H], counts=counts[:, :H], masks=masks[:, :H, :n].astype(bool))
+    return (out, ms.value) if timing else out
