@@ -867,6 +867,33 @@ int msorb_local_ba(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_poi
  * errors, cost).  Without the variable: MSORB_E_ARG, zeros. */
 int msorb_local_ba_stage_ms(float ms[4]);
 
+/* Optimizer::BundleAdjustment (src/Optimizer.cc:60-364, the body of GlobalBundleAdjustemnt) for pinhole KeyFrames without a second
+ * camera on the device: the global bundle adjustment of the monocular initialisation (Tracking.cc:2561) and of loop closing
+ * (LoopClosing.cc:2228).  Appended to ABI 6002 as the local bundle adjustment was: MSORB_ABI_VERSION stays 6002.  The arrays and
+ * the point-major edge order are msorb_local_ba's; what differs restates the reference: fixed marks mnId == GetInitKFid() (:122);
+ * no fixed KeyFrame is nothing special (no status 1); robust == 0 leaves the Huber kernel off (:174, :206); optimize(n_iterations)
+ * runs once and nothing is classified (n_outliers is 0); a stop flag that is already set yields zero iterations (no status 2);
+ * a point without an edge is no vertex (:261-263): point_included [per point] is 0 and its pos_out repeats the input.  The
+ * reduced system is solved by a blocked, multi-workgroup L D L^T (below).  More free KeyFrames than the capacity, or no room on
+ * the device for the reduced system: MSORB_E_CAPACITY, nothing launched, no output written.  Two calls on the same input return
+ * the same bits.  Re-entrant like msorb_local_ba. */
+int msorb_bundle_adjustment_capacity(void);            /* free KeyFrames: 1024 (the reduced system is 6144^2 doubles = 302 MB) */
+int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_points, const float* pos_w,
+                            int n_edges, const int* edge_kf, const int* edge_point, const float* xy, const float* u_right,
+                            const float* inv_sigma2, int n_iterations, int robust, const volatile int* stop_flag,
+                            float* kf_qt_out, double* kf_qt_d, float* pos_out, double* pos_d, uint8_t* point_included,
+                            msorb_ba_result* r, float* elapsed_ms);
+/* msorb_local_ba_stage_ms for the calling thread's last msorb_bundle_adjustment call (the same environment variable). */
+int msorb_bundle_adjustment_stage_ms(float ms[4]);
+/* The dense solver of msorb_bundle_adjustment alone: S x = b for a symmetric S by L D L^T without pivoting and without a square
+ * root, right-looking and blocked: a panel of *panel columns is factored by one workgroup in LDS, the rows below it and the
+ * trailing lower triangle (in tiles of *tile) by as many workgroups as there are rows and tiles.  Every entry goes through the
+ * subtractions of the column-by-column factorisation in the same order, so two runs, and any panel width, return the same bits. */
+int msorb_ldlt_block_sizes(int* panel, int* tile);
+/* S: n x n doubles, row-major, the lower triangle is read; b, x: n; any n >= 1.  Host arrays: upload, solve, read-back.
+ * *ok = 0: a pivot was not positive ("solver failed"), x untouched.  *elapsed_ms (may be NULL): device time of the solve. */
+int msorb_ldlt_solve(int device, int n, const double* S, const double* b, double* x, int* ok, float* elapsed_ms);
+
 /* Sim3Solver's RANSAC (src/Sim3Solver.cc:228-373) for two pinhole cameras on the device, every hypothesis at once.  Appended to ABI
  * 6002 as the local bundle adjustment was: MSORB_ABI_VERSION stays 6002.  The draws of :254-265 do not depend on the data, so the
  * caller draws the minimal sets of all iterations beforehand (DUtils::Random::RandomInt with the swap-with-back rule of :256-264)

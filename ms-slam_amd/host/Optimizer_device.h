@@ -1,4 +1,4 @@
-// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037), LocalBundleAdjustment and the two OptimizeSim3 (further down), each on
+// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037), LocalBundleAdjustment, BundleAdjustment / GlobalBundleAdjustemnt and the two OptimizeSim3 (further down), each on
 // its device entry of libmsorb.  First PoseOptimization (msorb_pose_optimization_batch /
 // msorb_frame_pose_optimization), written against the reference's own types by name (a template: this header compiles inside
 // MS-SLAM, where Frame / MapPoint are the real classes, and in tests/dropin_poseopt_main.cc, where they are minimal stand-ins
@@ -316,6 +316,141 @@ bool LocalBundleAdjustment(KFPtr pKF, bool* pbStopFlag, MapT* pMap, int& num_fix
     }
     pMap->IncreaseChangeIndex();                                                                         // :1406
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::BundleAdjustment and GlobalBundleAdjustemnt (src/Optimizer.cc:51-364) on msorb_bundle_adjustment: the global bundle
+// adjustment of the monocular initialisation (Tracking.cc:2561) and of loop closing (LoopClosing.cc:2228).
+//
+//   bool ORB_SLAM3::msorb_host::BundleAdjustment(vpKFs, vpMP, nIterations = 5, pbStopFlag = NULL, nLoopKF = 0, bRobust = true)
+//   bool ORB_SLAM3::msorb_host::GlobalBundleAdjustemnt(pMap, nIterations = 5, pbStopFlag = NULL, nLoopKF = 0, bRobust = true)
+//
+// the reference's parameter lists and defaults, and its effects: with nLoopKF == pMap->GetOriginKF()->mnId SetPose / SetWorldPos /
+// UpdateNormalAndDepth, otherwise mTcwGBA / mPosGBA / mnBAGlobalForKF (:284-288, :356-362), for every KeyFrame that is not bad and
+// every point that is not bad and has an observation the reference counts (:154, :261-263).  The counting block of :289-340 has
+// no effect and is not restated.  true = done.
+//
+// false = NOT handled, nothing touched, the caller runs Optimizer::BundleAdjustment: a KeyFrame with a second camera (the
+// EdgeSE3ProjectXYZToBody arm, :225-257), or more free KeyFrames than msorb_bundle_adjustment_capacity() (or no room on the device
+// for their reduced system).
+//
+// What runs where.  The gathering (:114-267) stays host code, as the reference's; the optimisation is the device's.  *pbStopFlag is
+// a bool another thread may set (LoopClosing's mbStopGBA); a watcher thread mirrors it into the int the C ABI reads, as above.
+template <class KFPtr, class MPPtr>
+bool BundleAdjustment(const std::vector<KFPtr>& vpKFs, const std::vector<MPPtr>& vpMP, int nIterations = 5, bool* pbStopFlag = nullptr,
+                      const unsigned long nLoopKF = 0, const bool bRobust = true, int device = 0) {
+    if (vpKFs.empty()) return false;
+    auto* pMap = vpKFs[0]->GetMap();                                                                     // :66
+    std::map<unsigned long, int> index;                                                                  // optimizer.vertex(mnId)
+    std::vector<msorb_ba_keyframe> kfs;
+    std::vector<KFPtr> kf_of_index;
+    unsigned long maxKFid = 0;
+    int n_free = 0;
+    for (const KFPtr& pKF : vpKFs) {                                                                     // :114-126
+        if (pKF->isBad()) continue;
+        if (pKF->mpCamera2) return false;
+        const auto Tcw = pKF->GetPose();
+        const auto& q = Tcw.unit_quaternion();
+        const auto& t = Tcw.translation();
+        msorb_ba_keyframe r;
+        r.q[0] = q.x(); r.q[1] = q.y(); r.q[2] = q.z(); r.q[3] = q.w();
+        r.t[0] = t(0); r.t[1] = t(1); r.t[2] = t(2);
+        r.fx = pKF->fx; r.fy = pKF->fy; r.cx = pKF->cx; r.cy = pKF->cy; r.mbf = pKF->mbf;                // :212-216
+        r.fixed = pKF->mnId == pMap->GetInitKFid() ? 1 : 0;                                              // :122
+        n_free += r.fixed ? 0 : 1;
+        index[pKF->mnId] = (int)kfs.size();
+        kfs.push_back(r);
+        kf_of_index.push_back(pKF);
+        if (pKF->mnId > maxKFid) maxKFid = pKF->mnId;
+    }
+    if (n_free > msorb_bundle_adjustment_capacity()) return false;
+    std::vector<float> pos_w, xy, u_right, inv_sigma2;
+    std::vector<int> edge_kf, edge_point;
+    std::vector<MPPtr> mp_of_index;
+    std::vector<uint8_t> counted;                                                                        // !vbNotIncludedMP
+    for (const MPPtr& pMP : vpMP) {                                                                      // :132-267
+        if (pMP->isBad()) continue;
+        const auto Xw = pMP->GetWorldPos();
+        const int nPoint = (int)mp_of_index.size();
+        int nEdges = 0;
+        const auto observations = pMP->GetObservations();
+        for (const auto& ob : observations) {
+            const auto& pKF = ob.first;
+            if (pKF->isBad() || pKF->mnId > maxKFid) continue;                                           // :150
+            const auto at = index.find(pKF->mnId);
+            if (at == index.end()) continue;                                                             // :152
+            nEdges++;                                                                                    // :154
+            const int leftIndex = std::get<0>(ob.second);
+            if (leftIndex == -1) continue;
+            const float kp_ur = pKF->GetuRight(leftIndex);
+            const auto& kpUn = pKF->GetKeyUn(leftIndex);
+            if (kpUn.octave > 10) continue;                                                              // :160, :190
+            edge_kf.push_back(at->second);
+            edge_point.push_back(nPoint);
+            xy.push_back(kpUn.pt.x); xy.push_back(kpUn.pt.y);
+            u_right.push_back(kp_ur < 0 ? -1.0f : kp_ur);                                                // :158 / :187
+            inv_sigma2.push_back(pKF->mvInvLevelSigma2[kpUn.octave]);
+        }
+        pos_w.push_back(Xw(0)); pos_w.push_back(Xw(1)); pos_w.push_back(Xw(2));
+        mp_of_index.push_back(pMP);
+        counted.push_back(nEdges ? 1 : 0);                                                               // :261-266
+    }
+    const int K = (int)kfs.size(), P = (int)mp_of_index.size(), E = (int)edge_kf.size();
+    std::vector<float> kf_out(7 * (size_t)K), pos_out(3 * (size_t)P);
+    std::vector<uint8_t> included((size_t)P);
+    msorb_ba_result r;
+    volatile int stop = pbStopFlag && *pbStopFlag ? 1 : 0;
+    std::atomic<bool> done(false);
+    std::thread watcher;
+    if (pbStopFlag && !stop)
+        watcher = std::thread([&] {
+            while (!done.load(std::memory_order_acquire)) {
+                if (*static_cast<volatile bool*>(pbStopFlag)) { stop = 1; return; }
+                std::this_thread::sleep_for(std::chrono::microseconds(50));
+            }
+        });
+    const int rc = msorb_bundle_adjustment(device, K, kfs.data(), P, pos_w.data(), E, edge_kf.data(), edge_point.data(), xy.data(),
+                                           u_right.data(), inv_sigma2.data(), nIterations, bRobust ? 1 : 0, pbStopFlag ? &stop : nullptr,
+                                           kf_out.data(), nullptr, pos_out.data(), nullptr, included.data(), &r, nullptr);
+    done.store(true, std::memory_order_release);
+    if (watcher.joinable()) watcher.join();
+    if (rc == MSORB_E_CAPACITY) return false;
+    if (rc != MSORB_OK) fail_call("msorb_bundle_adjustment");
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose().unit_quaternion())>::type QuatT;
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose().translation())>::type VecT;
+    const bool bApply = nLoopKF == pMap->GetOriginKF()->mnId;
+    for (int k = 0; k < K; k++) {                                                                        // :277-342
+        const float* o = kf_out.data() + 7 * (size_t)k;
+        const SE3T T(QuatT(o[3], o[0], o[1], o[2]), VecT(o[4], o[5], o[6]));
+        if (bApply) {
+            kf_of_index[k]->SetPose(T);
+        } else {
+            kf_of_index[k]->mTcwGBA = T;
+            kf_of_index[k]->mnBAGlobalForKF = nLoopKF;
+        }
+    }
+    for (int p = 0; p < P; p++) {                                                                        // :345-363
+        if (!counted[p]) continue;   // (a counted point whose observations gave no edge keeps its position: pos_out repeats it)
+        typedef typename std::decay<decltype(mp_of_index[p]->GetWorldPos())>::type PosT;
+        const float* o = pos_out.data() + 3 * (size_t)p;
+        if (bApply) {
+            mp_of_index[p]->SetWorldPos(PosT(o[0], o[1], o[2]));
+            mp_of_index[p]->UpdateNormalAndDepth();
+        } else {
+            mp_of_index[p]->mPosGBA = PosT(o[0], o[1], o[2]);
+            mp_of_index[p]->mnBAGlobalForKF = nLoopKF;
+        }
+    }
+    return true;
+}
+
+template <class MapT>
+bool GlobalBundleAdjustemnt(MapT* pMap, int nIterations = 5, bool* pbStopFlag = nullptr, const unsigned long nLoopKF = 0,
+                            const bool bRobust = true, int device = 0) {
+    const auto vpKFs = pMap->GetAllKeyFrames();                                                          // :53-56
+    const auto vpMP = pMap->GetAllMapPoints();
+    return BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust, device);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -1969,6 +1969,85 @@ def local_ba_stage_ms():
     return dict(zip(("linearise", "schur", "solve", "trial"), (float(v) for v in ms)))
 
 
+# ---- Optimizer::BundleAdjustment (global BA) and its blocked dense solver on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_bundle_adjustment_capacity", "msorb_bundle_adjustment", "msorb_bundle_adjustment_stage_ms",
+                     "msorb_ldlt_block_sizes", "msorb_ldlt_solve")
+
+
+def _gba_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_bundle_adjustment_capacity.argtypes = []
+    L.msorb_bundle_adjustment.argtypes = [ci, ci, vp, ci, vp, ci] + [vp] * 5 + [ci, ci] + [vp] * 8
+    L.msorb_bundle_adjustment_stage_ms.argtypes = [vp]
+    L.msorb_ldlt_block_sizes.argtypes = [vp, vp]
+    L.msorb_ldlt_solve.argtypes = [ci, ci] + [vp] * 5
+    return L
+
+
+def bundle_adjustment_capacity():
+    """the largest number of free KeyFrames msorb_bundle_adjustment accepts"""
+    return _gba_lib().msorb_bundle_adjustment_capacity()
+
+
+def ldlt_block_sizes():
+    """(panel width, trailing tile edge) of the blocked L D L^T"""
+    nb, tile = C.c_int(), C.c_int()
+    _check(_gba_lib().msorb_ldlt_block_sizes(C.addressof(nb), C.addressof(tile)), "msorb_ldlt_block_sizes")
+    return nb.value, tile.value
+
+
+def ldlt_solve(S, b, x=None, device=0, timing=False):
+    """msorb_ldlt_solve: S [n, n] float64 (lower triangle read), b [n] -> (x, ok); x (given or zeros) is left as it is when a
+    pivot is not positive.  With timing: (x, ok, elapsed_ms)."""
+    S, b = _c(S, np.float64), _c(b, np.float64).reshape(-1)
+    n = len(b)
+    if S.shape != (n, n):
+        raise ValueError("S is not n x n")
+    x = np.zeros(n, np.float64) if x is None else x
+    assert x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous
+    ok, ms = C.c_int(), C.c_float()
+    _check(_gba_lib().msorb_ldlt_solve(device, n, _np_ptr(S), _np_ptr(b), _np_ptr(x), C.addressof(ok), C.addressof(ms)), "msorb_ldlt_solve")
+    return (x, bool(ok.value), ms.value) if timing else (x, bool(ok.value))
+
+
+def bundle_adjustment(keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, n_iterations=5, robust=True, stop_flag=None,
+                      device=0, timing=False):
+    """msorb_bundle_adjustment: Optimizer::BundleAdjustment on the device.  The arrays are local_ba's; fixed marks the InitKFid
+    KeyFrame.  -> dict(result: BA_RESULT_DTYPE record, kf_qt, kf_qt_d [K, 7], pos, pos_d [P, 3], point_included bool [P]) and, with
+    timing, elapsed_ms (device time)."""
+    L = _gba_lib()
+    kf = _c(keyframes, BA_KEYFRAME_DTYPE).reshape(-1)
+    pw = _c(pos_w, np.float32).reshape(-1, 3)
+    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
+    ob, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
+    K, P, E = len(kf), len(pw), len(ek)
+    if [len(ep), len(ob), len(ur), len(inv)] != [E, 2 * E, E, E]:
+        raise ValueError("the edge arrays do not have one entry per edge")
+    if stop_flag is not None:
+        assert stop_flag.dtype == np.int32 and stop_flag.size == 1
+    qt, qtd = np.zeros((max(K, 1), 7), np.float32), np.zeros((max(K, 1), 7), np.float64)
+    po, pod = np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64)
+    inc = np.zeros(max(P, 1), np.uint8)
+    res = np.zeros(1, BA_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_bundle_adjustment(device, K, _np_ptr(kf), P, _np_ptr(pw), E, _np_ptr(ek), _np_ptr(ep), _np_ptr(ob), _np_ptr(ur),
+                                     _np_ptr(inv), int(n_iterations), int(bool(robust)),
+                                     None if stop_flag is None else _np_ptr(stop_flag), _np_ptr(qt), _np_ptr(qtd), _np_ptr(po),
+                                     _np_ptr(pod), _np_ptr(inc), _np_ptr(res), C.addressof(ms)), "msorb_bundle_adjustment")
+    r = dict(result=res[0], kf_qt=qt[:K], kf_qt_d=qtd[:K], pos=po[:P], pos_d=pod[:P], point_included=inc[:P].astype(bool))
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r
+
+
+def bundle_adjustment_stage_ms():
+    """local_ba_stage_ms for this thread's last bundle_adjustment call (MSORB_LOCAL_BA_STAGES=1)"""
+    ms = np.zeros(4, np.float32)
+    _check(_gba_lib().msorb_bundle_adjustment_stage_ms(_np_ptr(ms)), "msorb_bundle_adjustment_stage_ms")
+    return dict(zip(("linearise", "schur", "solve", "trial"), (float(v) for v in ms)))
+
+
 EXPORTS = EXPORTS + ("msorb_create_new_map_points_kf", "msorb_create_new_map_points_stage_ms")
 
 NP_NONE, NP_TRIANGULATED, NP_STEREO1, NP_STEREO2, NP_LOW_PARALLAX, NP_NULL_W, NP_STEREO_DEPTH, NP_BEHIND1, NP_BEHIND2, NP_REPROJ1, \
