@@ -1,7 +1,7 @@
-// The kernels that msorb_local_ba (local_ba.hip) and msorb_bundle_adjustment (bundle_adjustment.hip) share: the edge
-// linearisation with the Huber switch, the per-vertex gathers, the point inverse, the Schur complement over the plan's index lists,
-// the update, the cost / scale reduction, and the stage timer.  local_ba.hip's header comment and DESIGN.md sections 10 and 16 say
-// what each does.  Every sum walks an index list of local_ba_plan.h in a fixed order: no floating-point atomics.
+// The kernels under the engine of msorb_local_ba and msorb_bundle_adjustment (bundle_adjustment.hip): the edge linearisation with
+// the Huber switch, the per-vertex gathers, the point inverse, the Schur complement over the plan's index lists, the update, the
+// cost / scale reduction, and the stage timer.  bundle_adjustment.hip's header comment and DESIGN.md sections 10 and 16 say what
+// each does.  Every sum walks an index list of local_ba_plan.h in a fixed order: no floating-point atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,13 +1,29 @@
-// Optimizer::BundleAdjustment (src/Optimizer.cc:60-364, reached through GlobalBundleAdjustemnt, :51-58) for pinhole KeyFrames
-// without a second camera: the kernels of ba_kernels_device.h under g2o's Levenberg loop, as local_ba.hip drives them, with the
-// reduced system solved by the blocked, multi-workgroup L D L^T of ldlt_blocked.h.  DESIGN.md section 16 has the whole story.
+// Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1040-1407) and Optimizer::BundleAdjustment (:60-364, reached through
+// GlobalBundleAdjustemnt, :51-58) for pinhole KeyFrames without a second camera: g2o's Levenberg-Marquardt over KeyFrame poses and
+// map points with the points eliminated by the Schur complement (core/block_solver.hpp:354-486), in double.  Both entries run ONE
+// engine, ba_engine below; what the reference does differently in the two is the Entry struct.  DESIGN.md sections 10 and 16 have
+// the whole story.
 //
-// What differs from msorb_local_ba restates the reference: bRobust is a switch (:174, :206), the iteration count is the caller's
-// (:269), there is no early return without a fixed KeyFrame and none for a stop flag that is already set (optimize() then makes zero
-// iterations), no classification follows, and a point without an edge is no vertex (:261-263).
+// The host drives the loop (optimization_algorithm_levenberg.cpp:61-170, sparse_optimizer.cpp:376-389) and reads 32 bytes back
+// per linearisation and per trial: the cost, computeScale and the solver's status.  That is where the stop flag is looked at,
+// exactly where g2o calls terminate().  Everything else stays on the device between the upload and the read-back of the result.
+//
+//   linearise   one thread per edge: error, Huber weight, both Jacobians, and the edge's terms of Hll / bl (point), Hpp / bp
+//               (KeyFrame) and W = Hpl (6x3), written edge-major as 54 planes of E doubles; the cost as one partial per workgroup
+//   gather      one thread per point adds its edges' Hll / bl terms (the edges are point-major: a contiguous run); one wavefront
+//               per free KeyFrame adds Hpp / bp over the by-KeyFrame list (lane l takes entries l, l + 64, ...; xor butterfly)
+//   trial       per lambda: D^-1 = adj(Hll + lambda I) / det and D^-1 bl per point; one wavefront per block pair (i, j) of the
+//               reduced system adds W_a D^-1 W_b^T over the pair's list and one per KeyFrame adds W D^-1 bl; the dense
+//               6 Kf x 6 Kf system is factored (L D L^T, no pivoting, no square root) and substituted, by ONE workgroup
+//               (ba_solve_kernel) under msorb_local_ba and by the blocked kernels of ldlt_blocked.h under msorb_bundle_adjustment:
+//               the same bits either way, see Entry::one_workgroup_solve; one thread per vertex applies the update to a second
+//               copy of the state (push / pop is which copy is current) and returns its share of computeScale; the errors at the
+//               trial state; a one-workgroup reduction of the cost and the scale.
 //
 // The square of the reduced system is zeroed before every trial's Schur launch: the Schur kernel writes the listed block pairs only
 // and the factorisation, which is in place, fills the rest in.  A rejected trial therefore rebuilds S from Hpp and the lists.
+//
+// No floating-point atomics: every sum walks an index list of local_ba_plan.h in a fixed order, two runs return the same bits.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -29,47 +45,146 @@ using namespace msorb::ba;
 namespace ldlt = msorb::ldlt;
 
 namespace {
-constexpr int kCapacity = 1024;   // free KeyFrames: S is 6144^2 doubles = 302 MB
+
+// Free KeyFrames.  Local: the reduced system is at most 768 x 768, four columns of which are ba_solve_kernel's LDS; the host
+// template hands a larger window back to the reference path.  Global: S is 6144^2 doubles = 302 MB.
+constexpr int kLocalCapacity = 128, kGlobalCapacity = 1024;
+constexpr int kMaxN = 6 * kLocalCapacity;
+constexpr int kSolveThreads = 1024;
+
+// What the reference does differently in LocalBundleAdjustment and in BundleAdjustment.
+struct Entry {
+    const char* name;          // "local_ba" / "bundle_adjustment": error strings
+    int capacity;
+    float d_mono;              // thHuber2D: (float)sqrt(5.991) at :1190, (float)sqrt(5.99) at :128
+    int robust;                // local: always (:1186-1191); global: bRobust (:174, :206)
+    int iterations;
+    bool one_workgroup_solve;  // ba_solve_kernel instead of ldlt::launch.  Both return the same bits (tests/test_ldlt_gpu.py, and the
+                               // 128-KeyFrame scene of tests/test_bundle_adjustment_gpu.py through both entries); the blocked solve is
+                               // 1.2 / 2.0 / 5.1 times faster for the whole call at 20 / 40 / 80 free KeyFrames but its four
+                               // launches cost a call of 2 free KeyFrames 0.05 ms (0.96 against 0.91 ms), so local keeps the one
+                               // launch until small systems take fewer
+    bool local;                // *r zeroed first; the early returns of :1098-1102 and :1323-1325; the classification of :1331-1373;
+                               // every point is a vertex (global: a point without an edge is none, :261-263)
+    uint8_t* edge_outlier;     // local's output, [E]
+    uint8_t* point_included;   // global's output, [P]
+};
+
+// The reduced system, dense: S = L D L^T without pivoting and without a square root (one reciprocal per pivot), right-looking over
+// the lower triangle, then the two substitutions.  One workgroup; S stays in global memory (L2), a column and its scaled copy in
+// LDS.  Column m's update of entry (i, k) is  - L[i][m] (L[k][m] D[m]),  applied for m ascending: the subtractions of the
+// left-looking form of DESIGN section 9 in the same order.  A pivot that is not positive: solver_ok = 0, x untouched.
+__global__ __launch_bounds__(kSolveThreads) void ba_solve_kernel(const BaDev A) {
+    __shared__ double v[kMaxN], l[kMaxN], y[kMaxN], rd[kMaxN];
+    const int n = A.n, t = threadIdx.x;
+    double* S = A.S;
+    for (int j = 0; j < n; j++) {
+        const double d = S[(size_t)j * n + j];   // (uniform: every thread reads the same word, written before the last barrier)
+        if (!(d > 0)) {
+            if (t == 0) A.res->solver_ok = 0;
+            return;
+        }
+        const double r = 1.0 / d;
+        if (t == 0) rd[j] = r;
+        for (int i = j + 1 + t; i < n; i += kSolveThreads) {
+            const double s = S[(size_t)i * n + j];
+            v[i] = s;
+            l[i] = s * r;
+            S[(size_t)i * n + j] = s * r;
+        }
+        __syncthreads();
+        // the trailing lower triangle: a wavefront takes rows, its lanes the columns of a row
+        for (int i = j + 1 + (t >> 6); i < n; i += kSolveThreads / 64) {
+            const double li = l[i];
+            double* row = S + (size_t)i * n;
+            for (int k = j + 1 + (t & 63); k <= i; k += 64) row[k] -= li * v[k];
+        }
+        __syncthreads();
+    }
+    // L y = b: column by column, so y[i] loses L[i][m] y[m] for m ascending
+    for (int i = t; i < n; i += kSolveThreads) y[i] = A.bs[i];
+    __syncthreads();
+    for (int m = 0; m < n; m++) {
+        const double ym = y[m];
+        __syncthreads();
+        for (int i = m + 1 + t; i < n; i += kSolveThreads) y[i] -= S[(size_t)i * n + m] * ym;
+        __syncthreads();
+    }
+    // D L^T x = y: x[i] = y[i] / D[i] - sum_m L[m][i] x[m], the columns taken from the last
+    for (int i = t; i < n; i += kSolveThreads) y[i] *= rd[i];
+    __syncthreads();
+    for (int m = n - 1; m >= 0; m--) {
+        const double xm = y[m];
+        __syncthreads();
+        for (int i = t; i < m; i += kSolveThreads) y[i] -= S[(size_t)m * n + i] * xm;
+        __syncthreads();
+    }
+    for (int i = t; i < n; i += kSolveThreads) A.x[i] = y[i];
+    if (t == 0) A.res->solver_ok = 1;
 }
 
-extern "C" int msorb_bundle_adjustment_capacity(void) { return kCapacity; }
+// :1331-1373: computeError at the final estimate, float fChi2 > 5.991 / 7.815 (double literals) or !isDepthPositive()
+__global__ __launch_bounds__(kEdgeThreads) void ba_classify_kernel(const BaDev A, int s) {
+    const int e = blockIdx.x * kEdgeThreads + threadIdx.x;
+    if (e >= A.E) return;
+    int k, p;
+    const EdgeGeom g = edge_geom(A, s, e, k, p);
+    const double c = (double)(float)g.chi2;
+    A.outlier[e] = (c > (g.stereo ? 7.815 : 5.991) || !(g.z > 0.0)) ? 1 : 0;
+}
 
-extern "C" int msorb_bundle_adjustment_stage_ms(float ms[4]) {
+int stage_ms(float ms[4]) {
     if (!ms) return MSORB_E_ARG;
     for (int i = 0; i < kStages; i++) ms[i] = g_stages.ms[i];
     return stages_on() ? MSORB_OK : MSORB_E_ARG;
 }
 
-extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_points, const float* pos_w,
-                                       int n_edges, const int* edge_kf, const int* edge_point, const float* xy, const float* u_right,
-                                       const float* inv_sigma2, int n_iterations, int robust, const volatile int* stop_flag,
-                                       float* kf_qt_out, double* kf_qt_d, float* pos_out, double* pos_d, uint8_t* point_included,
-                                       msorb_ba_result* r, float* elapsed_ms) {
+int ba_engine(const Entry& f, int device, int n_kf, const msorb_ba_keyframe* kfs, int n_points, const float* pos_w, int n_edges,
+              const int* edge_kf, const int* edge_point, const float* xy, const float* u_right, const float* inv_sigma2,
+              const volatile int* stop_flag, float* kf_qt_out, double* kf_qt_d, float* pos_out, double* pos_d, msorb_ba_result* r,
+              float* elapsed_ms) {
     if (elapsed_ms) *elapsed_ms = 0;
-    if (!r || n_kf < 0 || n_points < 0 || n_edges < 0 || n_iterations < 0) return MSORB_E_ARG;
-    if ((n_kf > 0 && (!kfs || !kf_qt_out)) || (n_points > 0 && (!pos_w || !pos_out || !point_included)) ||
-        (n_edges > 0 && (!edge_kf || !edge_point || !xy || !u_right || !inv_sigma2)))
+    if (!r || n_kf < 0 || n_points < 0 || n_edges < 0 || f.iterations < 0) return MSORB_E_ARG;
+    if ((n_kf > 0 && (!kfs || !kf_qt_out)) || (n_points > 0 && (!pos_w || !pos_out || (!f.local && !f.point_included))) ||
+        (n_edges > 0 && (!edge_kf || !edge_point || !xy || !u_right || !inv_sigma2 || (f.local && !f.edge_outlier))))
         return MSORB_E_ARG;
+    if (f.local) std::memset(r, 0, sizeof *r);   // (global leaves every output untouched until the capacity checks have passed)
     const int K = n_kf, P = n_points, E = n_edges;
+    const std::string name = std::string(f.name) + ": ";
     static thread_local std::vector<int> fixed;
     static thread_local msorb::LocalBaPlan plan;
     fixed.resize((size_t)K);
     for (int k = 0; k < K; k++) fixed[k] = kfs[k].fixed != 0;
     switch (msorb::build_local_ba_plan(K, fixed.data(), P, E, edge_kf, edge_point, plan)) {
-        case msorb::kPlanIndexOutOfRange: set_last_error("bundle_adjustment: an edge names a KeyFrame or a point out of range"); return MSORB_E_ARG;
-        case msorb::kPlanNotPointMajor: set_last_error("bundle_adjustment: the edges are not point-major"); return MSORB_E_ARG;
+        case msorb::kPlanIndexOutOfRange: set_last_error(name + "an edge names a KeyFrame or a point out of range"); return MSORB_E_ARG;
+        case msorb::kPlanNotPointMajor: set_last_error(name + "the edges are not point-major"); return MSORB_E_ARG;
         default: break;
     }
     const int Kf = plan.Kf, n = 6 * Kf;
-    if (Kf > kCapacity) {
-        set_last_error("bundle_adjustment: more free KeyFrames than msorb_bundle_adjustment_capacity()");
+    if (Kf > f.capacity) {
+        set_last_error(name + "more free KeyFrames than msorb_" + f.name + "_capacity()");
         return MSORB_E_CAPACITY;
+    }
+    if (f.local && (Kf == K || (stop_flag && *stop_flag))) {   // :1098-1102, :1323-1325: nothing touched, the outputs are the inputs
+        r->status = Kf == K ? 1 : 2;
+        for (int k = 0; k < K; k++)
+            for (int c = 0; c < 7; c++) {
+                const float v = c < 4 ? kfs[k].q[c] : kfs[k].t[c - 4];
+                kf_qt_out[7 * (size_t)k + c] = v;
+                if (kf_qt_d) kf_qt_d[7 * (size_t)k + c] = (double)v;
+            }
+        for (size_t i = 0; i < 3 * (size_t)P; i++) {
+            pos_out[i] = pos_w[i];
+            if (pos_d) pos_d[i] = (double)pos_w[i];
+        }
+        if (E) std::memset(f.edge_outlier, 0, (size_t)E);
+        return MSORB_OK;
     }
     if (int rc = msorb::require_device(device)) return rc;
 
     // ---- the device block: [uploaded | state and workspaces | results]
     const int n_pairs = (int)plan.pair_i.size(), n_blocks = (E + kEdgeThreads - 1) / kEdgeThreads;
-    const size_t n_entries = plan.pair_a.size();
+    const size_t n_entries = plan.pair_a.size(), n_out = f.local ? (size_t)E : 0;
     Carve c;
     const size_t o_kf = c.take((size_t)K * sizeof(msorb_ba_keyframe)), o_free = c.take((size_t)K * 4), o_kof = c.take((size_t)Kf * 4);
     const size_t o_ekf = c.take((size_t)E * 4), o_ept = c.take((size_t)E * 4), o_pb = c.take(((size_t)P + 1) * 4);
@@ -82,20 +197,20 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
     const size_t o_pose1 = c.take((size_t)K * 56), o_pt1 = c.take((size_t)P * 24);
     const size_t o_lin = c.take((size_t)kPlanes * E * 8), o_hpp = c.take((size_t)Kf * 27 * 8), o_hll = c.take((size_t)P * 72);
     const size_t o_dinv = c.take((size_t)P * 72), o_S = c.take((size_t)n * n * 8), o_bs = c.take((size_t)n * 8), o_x = c.take((size_t)n * 8);
-    const size_t o_ws = c.take(ldlt::workspace_doubles(n) * 8);
+    const size_t o_ws = c.take(f.one_workgroup_solve ? 0 : ldlt::workspace_doubles(n) * 8);
     const size_t o_pc = c.take((size_t)n_blocks * 8), o_pv = c.take(((size_t)Kf + P) * 8);
-    const size_t o_res = c.take(sizeof(BaRes));
+    const size_t o_res = c.take(sizeof(BaRes)), o_out = c.take(n_out);
     const size_t dev_bytes = c.at;
-    // pinned: the upload, then [res | pose | points] for the read-backs
+    // pinned: the upload, then [res | pose | points | outlier] for the read-backs
     Carve hc;
     hc.at = in_bytes;
-    const size_t h_res = hc.take(sizeof(BaRes)), h_pose = hc.take((size_t)K * 56), h_pt = hc.take((size_t)P * 24);
+    const size_t h_res = hc.take(sizeof(BaRes)), h_pose = hc.take((size_t)K * 56), h_pt = hc.take((size_t)P * 24), h_out = hc.take(n_out);
     static thread_local ThreadScratch scr(true, 2);
     if (dev_bytes > scr.d.n) {   // the block has to grow (by 1.5x): a reduced system that does not fit is a matter of capacity
         if (hipSetDevice(device) != hipSuccess) return MSORB_E_HIP;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && dev_bytes + dev_bytes / 2 + 16 > free_b + (scr.device == device ? scr.d.n : 0)) {
-            set_last_error("bundle_adjustment: the device has no room for the reduced system");
+            set_last_error(name + "the device has no room for the reduced system");
             return MSORB_E_CAPACITY;
         }
     }
@@ -119,7 +234,7 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
     put(o_xy, xy, (size_t)E * 8);
     put(o_ur, u_right, (size_t)E * 4);
     put(o_w, inv_sigma2, (size_t)E * 4);
-    {   // :138, :202: the float pose widened, SE3Quat's constructor normalises (se3quat.h:62-64); the point widened
+    {   // :1134, :1150 / :138, :202: the float pose widened, SE3Quat's constructor normalises (se3quat.h:62-64); the point widened
         double* hp = reinterpret_cast<double*>(h + o_pose0);
         for (int k = 0; k < K; k++) {
             double q[4];
@@ -145,10 +260,10 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
     A.lin = dp(o_lin); A.Hpp = dp(o_hpp); A.Hll = dp(o_hll); A.Dinv = dp(o_dinv); A.S = dp(o_S); A.bs = dp(o_bs); A.x = dp(o_x);
     A.part_cost = dp(o_pc); A.part_vtx = dp(o_pv);
     A.res = reinterpret_cast<BaRes*>(d + o_res);
-    A.outlier = nullptr;   // no classification here
-    A.d_mono = (float)std::sqrt(5.99);      // :128-129: thHuber2D is sqrt(5.99) HERE (5.991 in LocalBundleAdjustment), thHuber3D sqrt(7.815)
+    A.outlier = f.local ? d + o_out : nullptr;
+    A.d_mono = f.d_mono;
     A.d_stereo = (float)std::sqrt(7.815);
-    A.robust = robust != 0;
+    A.robust = f.robust;
     ldlt::Work W{};
     W.n = n; W.S = A.S; W.b = A.bs; W.x = A.x;
     ldlt::carve_workspace(W, dp(o_ws));
@@ -156,7 +271,7 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
 
     hipError_t err = hipSuccess;
     auto fail = [&](const char* what) {
-        set_last_error(std::string("bundle_adjustment: ") + what + ": " + hipGetErrorString(err));
+        set_last_error(name + what + ": " + hipGetErrorString(err));
         scr.release();
         return MSORB_E_HIP;
     };
@@ -188,10 +303,10 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
     int cur = 0;
     double lambda = 0, ni = 2;
     int n_bad = 0, iterations = 0, trials = 0, rejected = 0;
-    std::memset(r, 0, sizeof *r);
+    std::memset(r, 0, sizeof *r);   // (global's first write of it)
     auto stopped = [&] { return stop_flag && *stop_flag; };   // SparseOptimizer::terminate
     bool ok = E > 0;   // without an edge there is nothing to optimise: zero iterations, the estimates as they came
-    for (int it = 0; it < n_iterations && !stopped() && ok; it++) {   // sparse_optimizer.cpp:376
+    for (int it = 0; it < f.iterations && !stopped() && ok; it++) {   // sparse_optimizer.cpp:376
         // ---- OptimizationAlgorithmLevenberg::solve (levenberg.cpp:61-170) ----
         BA_STAGE(kLinearise);
         BA_LAUNCH(ba_edges_kernel<true>, n_blocks, kEdgeThreads, A, cur);
@@ -216,7 +331,8 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
             BA_LAUNCH(ba_schur_kernel, task_blocks, kEdgeThreads, A, lambda);
             BA_STAGE(kSchur);
             BA_STAGE(kSolve);
-            BA_TRY(ldlt::launch(W, s));
+            if (f.one_workgroup_solve) BA_LAUNCH(ba_solve_kernel, n ? 1 : 0, kSolveThreads, A);
+            else BA_TRY(ldlt::launch(W, s));
             BA_STAGE(kSolve);
             BA_STAGE(kTrial);
             BA_LAUNCH(ba_update_kernel, vtx_blocks, kEdgeThreads, A, cur, cur ^ 1, lambda);   // push + update (:103, :115)
@@ -253,9 +369,11 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
         if (n_bad >= 3) ok = false;                             // :164-167
     }
     if (iterations == 0) r->chi2_final = r->chi2_initial;
+    if (f.local) BA_LAUNCH(ba_classify_kernel, n_blocks, kEdgeThreads, A, cur);
     if (elapsed_ms) BA_TRY(hipEventRecord(scr.ev[1], s));
     BA_TRY(hipMemcpyAsync(h + h_pose, d + (cur ? o_pose1 : o_pose0), (size_t)K * 56, hipMemcpyDeviceToHost, s));
     if (P) BA_TRY(hipMemcpyAsync(h + h_pt, d + (cur ? o_pt1 : o_pt0), (size_t)P * 24, hipMemcpyDeviceToHost, s));
+    if (n_out) BA_TRY(hipMemcpyAsync(h + h_out, d + o_out, n_out, hipMemcpyDeviceToHost, s));
     BA_TRY(hipStreamSynchronize(s));
     if (elapsed_ms) BA_TRY(hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]));
     if (timed) BA_TRY(g_stages.collect());
@@ -267,24 +385,52 @@ extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyf
         for (int a = 0; a < 7; a++) {
             const bool fx = fixed[k] != 0;   // a fixed KeyFrame's output repeats its input
             const float in = a < 4 ? kfs[k].q[a] : kfs[k].t[a - 4];
-            kf_qt_out[7 * (size_t)k + a] = fx ? in : (float)hp[7 * (size_t)k + a];   // :284-288
+            kf_qt_out[7 * (size_t)k + a] = fx ? in : (float)hp[7 * (size_t)k + a];   // :1393 / :284-288
             if (kf_qt_d) kf_qt_d[7 * (size_t)k + a] = fx ? (double)in : hp[7 * (size_t)k + a];
         }
     const double* hx = reinterpret_cast<const double*>(h + h_pt);
     for (int p = 0; p < P; p++) {
-        const bool in = plan.point_begin[p + 1] > plan.point_begin[p];   // :261-263: without an edge it is no vertex
-        point_included[p] = in ? 1 : 0;
+        const bool in = f.local || plan.point_begin[p + 1] > plan.point_begin[p];   // :261-263: without an edge it is no vertex
+        if (!f.local) f.point_included[p] = in ? 1 : 0;
         for (int a = 0; a < 3; a++) {
             const size_t i = 3 * (size_t)p + a;
-            pos_out[i] = in ? (float)hx[i] : pos_w[i];   // :356-362
+            pos_out[i] = in ? (float)hx[i] : pos_w[i];   // :1402 / :356-362
             if (pos_d) pos_d[i] = in ? hx[i] : (double)pos_w[i];
         }
     }
+    int n_outliers = 0;
+    for (size_t e = 0; e < n_out; e++) { f.edge_outlier[e] = h[h_out + e]; n_outliers += f.edge_outlier[e] != 0; }
     r->status = 0;
     r->iterations = iterations;
     r->trials = trials;
     r->rejected_trials = rejected;
-    r->n_outliers = 0;
+    r->n_outliers = n_outliers;
     r->lambda_final = lambda;
     return MSORB_OK;
+}
+
+}  // namespace
+
+extern "C" int msorb_local_ba_capacity(void) { return kLocalCapacity; }
+extern "C" int msorb_bundle_adjustment_capacity(void) { return kGlobalCapacity; }
+extern "C" int msorb_local_ba_stage_ms(float ms[4]) { return stage_ms(ms); }
+extern "C" int msorb_bundle_adjustment_stage_ms(float ms[4]) { return stage_ms(ms); }
+
+extern "C" int msorb_local_ba(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_points, const float* pos_w, int n_edges,
+                              const int* edge_kf, const int* edge_point, const float* xy, const float* u_right, const float* inv_sigma2,
+                              int max_iterations, const volatile int* stop_flag, float* kf_qt_out, double* kf_qt_d, float* pos_out,
+                              double* pos_d, uint8_t* edge_outlier, msorb_ba_result* r, float* elapsed_ms) {
+    const Entry f{"local_ba", kLocalCapacity, (float)std::sqrt(5.991), 1, max_iterations, true, true, edge_outlier, nullptr};
+    return ba_engine(f, device, n_kf, kfs, n_points, pos_w, n_edges, edge_kf, edge_point, xy, u_right, inv_sigma2, stop_flag, kf_qt_out,
+                     kf_qt_d, pos_out, pos_d, r, elapsed_ms);
+}
+
+extern "C" int msorb_bundle_adjustment(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_points, const float* pos_w,
+                                       int n_edges, const int* edge_kf, const int* edge_point, const float* xy, const float* u_right,
+                                       const float* inv_sigma2, int n_iterations, int robust, const volatile int* stop_flag,
+                                       float* kf_qt_out, double* kf_qt_d, float* pos_out, double* pos_d, uint8_t* point_included,
+                                       msorb_ba_result* r, float* elapsed_ms) {
+    const Entry f{"bundle_adjustment", kGlobalCapacity, (float)std::sqrt(5.99), robust != 0, n_iterations, false, false, nullptr, point_included};
+    return ba_engine(f, device, n_kf, kfs, n_points, pos_w, n_edges, edge_kf, edge_point, xy, u_right, inv_sigma2, stop_flag, kf_qt_out,
+                     kf_qt_d, pos_out, pos_d, r, elapsed_ms);
 }

@@ -1,7 +1,7 @@
 // Dense symmetric solve S x = b by a blocked, multi-workgroup L D L^T: square-root-free, unpivoted, natural order, right-looking
 // over the lower triangle, panel width kNB.  DESIGN.md section 16 has the whole story.
 //
-// Every entry of S goes through the arithmetic of the column-by-column factorisation (ba_solve_kernel of local_ba.hip,
+// Every entry of S goes through the arithmetic of the column-by-column factorisation (ba_solve_kernel of bundle_adjustment.hip,
 // ldlt_solve of tests/local_ba_cases.py): column m takes  l_im v_km  off entry (i, k), l = v / d_m by ONE reciprocal, v the
 // column before the scaling, for m ascending and each subtraction rounded on its own.  Blocking changes who does a subtraction and
 // when, not its operands or its place in the entry's sequence, so the factor equals the unblocked one bit for bit.  For that the

@@ -1,4 +1,4 @@
-// The index lists of one local bundle adjustment (local_ba.hip), built once per call on the host.  Host only: no HIP, no library,
+// The index lists of one bundle adjustment, local or global (bundle_adjustment.hip), built once per call on the host.  Host only: no HIP, no library,
 // so tests/local_ba_plan_main.cc checks it against a brute-force enumeration without a device (and under the sanitizers).
 //
 // Edges arrive point-major (point 0's edges, then point 1's, ...: Optimizer.cc:1196-1320 builds them that way), so the by-point

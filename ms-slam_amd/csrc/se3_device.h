@@ -1,4 +1,4 @@
-// Device pieces of g2o's SE3Quat and robust kernel that the optimisation kernels share (pose_opt.hip, local_ba.hip, sim3_opt.hip):
+// Device pieces of g2o's SE3Quat and robust kernel that the optimisation kernels share (pose_opt.hip, bundle_adjustment.hip, sim3_opt.hip):
 // the pose record, Eigen's quaternion rotation, Quaterniond(Matrix3d), SE3Quat::exp, VertexSE3Expmap::oplus, the Huber kernel and
 // the 64-lane shuffle of a double.  Plain double arithmetic in the order written (the library is built with -ffp-contract=off).
 // A host compiler reads the same statements (tests/sim3_opt_main.cc): everything but the shuffle is __host__ __device__.

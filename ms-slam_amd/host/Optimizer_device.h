@@ -127,6 +127,67 @@ int PoseOptimization(FrameT* pFrame) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// What LocalBundleAdjustment and BundleAdjustment below share.
+//
+// *flag is a bool another thread may set; the C ABI reads an int, so a watcher thread mirrors the one into the other for as long
+// as this object lives (the duration of the call).
+class StopFlagMirror {
+public:
+    explicit StopFlagMirror(bool* flag) : flag_(flag), stop_(flag && *flag ? 1 : 0) {
+        if (flag_ && !stop_)
+            watcher_ = std::thread([this] {
+                while (!done_.load(std::memory_order_acquire)) {
+                    if (*static_cast<volatile bool*>(flag_)) { stop_ = 1; return; }
+                    std::this_thread::sleep_for(std::chrono::microseconds(50));
+                }
+            });
+    }
+    ~StopFlagMirror() {
+        done_.store(true, std::memory_order_release);
+        if (watcher_.joinable()) watcher_.join();
+    }
+    const volatile int* get() const { return flag_ ? &stop_ : nullptr; }   // what msorb_local_ba / msorb_bundle_adjustment take
+
+private:
+    bool* flag_;
+    volatile int stop_;
+    std::atomic<bool> done_{false};
+    std::thread watcher_;
+};
+
+template <class KFPtr>
+msorb_ba_keyframe BaKeyFrame(const KFPtr& k, bool fixed) {
+    const auto Tcw = k->GetPose();                                                                       // :1133, :1149 / :138
+    const auto& q = Tcw.unit_quaternion();
+    const auto& t = Tcw.translation();
+    msorb_ba_keyframe r;
+    r.q[0] = q.x(); r.q[1] = q.y(); r.q[2] = q.z(); r.q[3] = q.w();
+    r.t[0] = t(0); r.t[1] = t(1); r.t[2] = t(2);
+    r.fx = k->fx; r.fy = k->fy; r.cx = k->cx; r.cy = k->cy; r.mbf = k->mbf;                              // :1267-1271 / :212-216
+    r.fixed = fixed ? 1 : 0;
+    return r;
+}
+
+// the edge arrays of msorb_local_ba / msorb_bundle_adjustment
+struct BaEdges {
+    std::vector<float> xy, u_right, inv_sigma2;
+    std::vector<int> edge_kf, edge_point;
+    // the observation of point `point` at keypoint leftIndex of pKF (vertex `kf`); false: the reference makes no edge of it
+    template <class KFPtr>
+    bool append(const KFPtr& pKF, int leftIndex, int kf, int point) {
+        if (leftIndex == -1) return false;
+        const float kp_ur = pKF->GetuRight(leftIndex);
+        const auto& kpUn = pKF->GetKeyUn(leftIndex);
+        if (kpUn.octave > 10) return false;                                                              // :1220, :1249 / :160, :190
+        edge_kf.push_back(kf);
+        edge_point.push_back(point);
+        xy.push_back(kpUn.pt.x); xy.push_back(kpUn.pt.y);
+        u_right.push_back(kp_ur < 0 ? -1.0f : kp_ur);                                                    // :1218, :1246 / :158, :187
+        inv_sigma2.push_back(pKF->mvInvLevelSigma2[kpUn.octave]);
+        return true;
+    }
+};
+
 // Optimizer::LocalBundleAdjustment (src/Optimizer.cc:1040-1407) on msorb_local_ba.
 //
 //   bool ORB_SLAM3::msorb_host::LocalBundleAdjustment(pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges)
@@ -143,15 +204,14 @@ int PoseOptimization(FrameT* pFrame) {
 //
 // What runs where.  The covisibility walk and the gathering (:1042-1102, :1196-1320) stay host code, as the reference's.  The
 // optimisation and the classification (:1326-1373) are the device's.  *pbStopFlag is a bool another thread may set (LocalMapping::
-// InterruptBA); the C ABI reads an int, so a watcher thread mirrors the one into the other for the duration of the call.
+// InterruptBA): StopFlagMirror.
 template <class KFPtr, class MPPtr>
-struct LocalBAProblem {
+struct LocalBAProblem : BaEdges {
     std::list<KFPtr> lLocalKeyFrames, lFixedCameras;
     std::list<MPPtr> lLocalMapPoints;
     std::vector<KFPtr> kf_of_index;        // local KeyFrames first, then the fixed cameras
     std::vector<msorb_ba_keyframe> kfs;
-    std::vector<float> pos_w, xy, u_right, inv_sigma2;
-    std::vector<int> edge_kf, edge_point;
+    std::vector<float> pos_w;
     std::vector<std::pair<KFPtr, MPPtr>> edge_objects;
     int num_fixedKF = 0;
     bool two_cameras = false;
@@ -205,16 +265,8 @@ auto GatherLocalBA(KFPtr pKF, MapT* pMap) {
     if (B.num_fixedKF == 0) return B;
     std::map<KFPtr, int> index;
     auto add_kf = [&](const KFPtr& k, bool fixed) {
-        const auto Tcw = k->GetPose();                                                                   // :1133, :1149
-        const auto& q = Tcw.unit_quaternion();
-        const auto& t = Tcw.translation();
-        msorb_ba_keyframe r;
-        r.q[0] = q.x(); r.q[1] = q.y(); r.q[2] = q.z(); r.q[3] = q.w();
-        r.t[0] = t(0); r.t[1] = t(1); r.t[2] = t(2);
-        r.fx = k->fx; r.fy = k->fy; r.cx = k->cx; r.cy = k->cy; r.mbf = k->mbf;                          // :1267-1271
-        r.fixed = fixed ? 1 : 0;
         index[k] = (int)B.kfs.size();
-        B.kfs.push_back(r);
+        B.kfs.push_back(BaKeyFrame(k, fixed));
         B.kf_of_index.push_back(k);
         if (k->mpCamera2) B.two_cameras = true;
     };
@@ -231,17 +283,7 @@ auto GatherLocalBA(KFPtr pKF, MapT* pMap) {
             const auto at = index.find(pKFi);
             if (at == index.end()) continue;   // (a KeyFrame that is in neither list has no vertex; the reference's setVertex would get NULL)
             if (pKFi->mpCamera2) B.two_cameras = true;
-            const int leftIndex = std::get<0>(ob.second);
-            if (leftIndex == -1) continue;
-            const float kp_ur = pKFi->GetuRight(leftIndex);
-            const auto& kpUn = pKFi->GetKeyUn(leftIndex);
-            if (kpUn.octave > 10) continue;                                                              // :1220, :1249
-            B.edge_kf.push_back(at->second);
-            B.edge_point.push_back(nPoints);
-            B.xy.push_back(kpUn.pt.x); B.xy.push_back(kpUn.pt.y);
-            B.u_right.push_back(kp_ur < 0 ? -1.0f : kp_ur);                                              // :1218 / :1246
-            B.inv_sigma2.push_back(pKFi->mvInvLevelSigma2[kpUn.octave]);
-            B.edge_objects.push_back({pKFi, pMP});
+            if (B.append(pKFi, std::get<0>(ob.second), at->second, nPoints)) B.edge_objects.push_back({pKFi, pMP});
         }
         nPoints++;
     }
@@ -271,21 +313,13 @@ bool LocalBundleAdjustment(KFPtr pKF, bool* pbStopFlag, MapT* pMap, int& num_fix
     std::vector<float> kf_out(7 * (size_t)K), pos_out(3 * (size_t)P);
     std::vector<uint8_t> outlier((size_t)E);
     msorb_ba_result r;
-    volatile int stop = pbStopFlag && *pbStopFlag ? 1 : 0;
-    std::atomic<bool> done(false);
-    std::thread watcher;
-    if (pbStopFlag && !stop)
-        watcher = std::thread([&] {
-            while (!done.load(std::memory_order_acquire)) {
-                if (*static_cast<volatile bool*>(pbStopFlag)) { stop = 1; return; }
-                std::this_thread::sleep_for(std::chrono::microseconds(50));
-            }
-        });
-    const int rc = msorb_local_ba(device, K, B.kfs.data(), P, B.pos_w.data(), E, B.edge_kf.data(), B.edge_point.data(), B.xy.data(),
-                                  B.u_right.data(), B.inv_sigma2.data(), 10, pbStopFlag ? &stop : nullptr, kf_out.data(), nullptr,
-                                  pos_out.data(), nullptr, outlier.data(), &r, nullptr);
-    done.store(true, std::memory_order_release);
-    if (watcher.joinable()) watcher.join();
+    int rc;
+    {
+        StopFlagMirror stop(pbStopFlag);
+        rc = msorb_local_ba(device, K, B.kfs.data(), P, B.pos_w.data(), E, B.edge_kf.data(), B.edge_point.data(), B.xy.data(),
+                            B.u_right.data(), B.inv_sigma2.data(), 10, stop.get(), kf_out.data(), nullptr, pos_out.data(), nullptr,
+                            outlier.data(), &r, nullptr);
+    }
     if (rc == MSORB_E_CAPACITY) { B.restore_marks(); return false; }
     if (rc != MSORB_OK) fail_call("msorb_local_ba");
     if (r.status != 0) return true;                                                                      // :1323-1325
@@ -335,7 +369,7 @@ bool LocalBundleAdjustment(KFPtr pKF, bool* pbStopFlag, MapT* pMap, int& num_fix
 // for their reduced system).
 //
 // What runs where.  The gathering (:114-267) stays host code, as the reference's; the optimisation is the device's.  *pbStopFlag is
-// a bool another thread may set (LoopClosing's mbStopGBA); a watcher thread mirrors it into the int the C ABI reads, as above.
+// a bool another thread may set (LoopClosing's mbStopGBA): StopFlagMirror.
 template <class KFPtr, class MPPtr>
 bool BundleAdjustment(const std::vector<KFPtr>& vpKFs, const std::vector<MPPtr>& vpMP, int nIterations = 5, bool* pbStopFlag = nullptr,
                       const unsigned long nLoopKF = 0, const bool bRobust = true, int device = 0) {
@@ -349,14 +383,7 @@ bool BundleAdjustment(const std::vector<KFPtr>& vpKFs, const std::vector<MPPtr>&
     for (const KFPtr& pKF : vpKFs) {                                                                     // :114-126
         if (pKF->isBad()) continue;
         if (pKF->mpCamera2) return false;
-        const auto Tcw = pKF->GetPose();
-        const auto& q = Tcw.unit_quaternion();
-        const auto& t = Tcw.translation();
-        msorb_ba_keyframe r;
-        r.q[0] = q.x(); r.q[1] = q.y(); r.q[2] = q.z(); r.q[3] = q.w();
-        r.t[0] = t(0); r.t[1] = t(1); r.t[2] = t(2);
-        r.fx = pKF->fx; r.fy = pKF->fy; r.cx = pKF->cx; r.cy = pKF->cy; r.mbf = pKF->mbf;                // :212-216
-        r.fixed = pKF->mnId == pMap->GetInitKFid() ? 1 : 0;                                              // :122
+        const msorb_ba_keyframe r = BaKeyFrame(pKF, pKF->mnId == pMap->GetInitKFid());                   // :122
         n_free += r.fixed ? 0 : 1;
         index[pKF->mnId] = (int)kfs.size();
         kfs.push_back(r);
@@ -364,8 +391,8 @@ bool BundleAdjustment(const std::vector<KFPtr>& vpKFs, const std::vector<MPPtr>&
         if (pKF->mnId > maxKFid) maxKFid = pKF->mnId;
     }
     if (n_free > msorb_bundle_adjustment_capacity()) return false;
-    std::vector<float> pos_w, xy, u_right, inv_sigma2;
-    std::vector<int> edge_kf, edge_point;
+    std::vector<float> pos_w;
+    BaEdges G;
     std::vector<MPPtr> mp_of_index;
     std::vector<uint8_t> counted;                                                                        // !vbNotIncludedMP
     for (const MPPtr& pMP : vpMP) {                                                                      // :132-267
@@ -380,40 +407,23 @@ bool BundleAdjustment(const std::vector<KFPtr>& vpKFs, const std::vector<MPPtr>&
             const auto at = index.find(pKF->mnId);
             if (at == index.end()) continue;                                                             // :152
             nEdges++;                                                                                    // :154
-            const int leftIndex = std::get<0>(ob.second);
-            if (leftIndex == -1) continue;
-            const float kp_ur = pKF->GetuRight(leftIndex);
-            const auto& kpUn = pKF->GetKeyUn(leftIndex);
-            if (kpUn.octave > 10) continue;                                                              // :160, :190
-            edge_kf.push_back(at->second);
-            edge_point.push_back(nPoint);
-            xy.push_back(kpUn.pt.x); xy.push_back(kpUn.pt.y);
-            u_right.push_back(kp_ur < 0 ? -1.0f : kp_ur);                                                // :158 / :187
-            inv_sigma2.push_back(pKF->mvInvLevelSigma2[kpUn.octave]);
+            G.append(pKF, std::get<0>(ob.second), at->second, nPoint);
         }
         pos_w.push_back(Xw(0)); pos_w.push_back(Xw(1)); pos_w.push_back(Xw(2));
         mp_of_index.push_back(pMP);
         counted.push_back(nEdges ? 1 : 0);                                                               // :261-266
     }
-    const int K = (int)kfs.size(), P = (int)mp_of_index.size(), E = (int)edge_kf.size();
+    const int K = (int)kfs.size(), P = (int)mp_of_index.size(), E = (int)G.edge_kf.size();
     std::vector<float> kf_out(7 * (size_t)K), pos_out(3 * (size_t)P);
     std::vector<uint8_t> included((size_t)P);
     msorb_ba_result r;
-    volatile int stop = pbStopFlag && *pbStopFlag ? 1 : 0;
-    std::atomic<bool> done(false);
-    std::thread watcher;
-    if (pbStopFlag && !stop)
-        watcher = std::thread([&] {
-            while (!done.load(std::memory_order_acquire)) {
-                if (*static_cast<volatile bool*>(pbStopFlag)) { stop = 1; return; }
-                std::this_thread::sleep_for(std::chrono::microseconds(50));
-            }
-        });
-    const int rc = msorb_bundle_adjustment(device, K, kfs.data(), P, pos_w.data(), E, edge_kf.data(), edge_point.data(), xy.data(),
-                                           u_right.data(), inv_sigma2.data(), nIterations, bRobust ? 1 : 0, pbStopFlag ? &stop : nullptr,
-                                           kf_out.data(), nullptr, pos_out.data(), nullptr, included.data(), &r, nullptr);
-    done.store(true, std::memory_order_release);
-    if (watcher.joinable()) watcher.join();
+    int rc;
+    {
+        StopFlagMirror stop(pbStopFlag);
+        rc = msorb_bundle_adjustment(device, K, kfs.data(), P, pos_w.data(), E, G.edge_kf.data(), G.edge_point.data(), G.xy.data(),
+                                     G.u_right.data(), G.inv_sigma2.data(), nIterations, bRobust ? 1 : 0, stop.get(), kf_out.data(),
+                                     nullptr, pos_out.data(), nullptr, included.data(), &r, nullptr);
+    }
     if (rc == MSORB_E_CAPACITY) return false;
     if (rc != MSORB_OK) fail_call("msorb_bundle_adjustment");
     typedef typename std::decay<decltype(vpKFs[0]->GetPose())>::type SE3T;

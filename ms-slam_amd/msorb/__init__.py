@@ -1913,7 +1913,45 @@ def _ba_lib():
     L.msorb_local_ba_capacity.argtypes = []
     L.msorb_local_ba.argtypes = [ci, ci, vp, ci, vp, ci] + [vp] * 5 + [ci] + [vp] * 8
     L.msorb_local_ba_stage_ms.argtypes = [vp]
+    L.msorb_bundle_adjustment_capacity.argtypes = []
+    L.msorb_bundle_adjustment.argtypes = [ci, ci, vp, ci, vp, ci] + [vp] * 5 + [ci, ci] + [vp] * 8
+    L.msorb_bundle_adjustment_stage_ms.argtypes = [vp]
     return L
+
+
+def _ba_call(entry, keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, controls, stop_flag, device, timing, flags_key, per):
+    """msorb_local_ba / msorb_bundle_adjustment: controls = the ints between inv_sigma2 and stop_flag; flags_key names the uint8
+    output that follows pos_d, one entry per edge (per = "E") or per point ("P")"""
+    L = _ba_lib()
+    kf = _c(keyframes, BA_KEYFRAME_DTYPE).reshape(-1)
+    pw = _c(pos_w, np.float32).reshape(-1, 3)
+    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
+    ob, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
+    K, P, E = len(kf), len(pw), len(ek)
+    if [len(ep), len(ob), len(ur), len(inv)] != [E, 2 * E, E, E]:
+        raise ValueError("the edge arrays do not have one entry per edge")
+    if stop_flag is not None:
+        assert stop_flag.dtype == np.int32 and stop_flag.size == 1
+    qt, qtd = np.zeros((max(K, 1), 7), np.float32), np.zeros((max(K, 1), 7), np.float64)
+    po, pod = np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64)
+    n_flags = E if per == "E" else P
+    flags = np.zeros(max(n_flags, 1), np.uint8)
+    res = np.zeros(1, BA_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(getattr(L, entry)(device, K, _np_ptr(kf), P, _np_ptr(pw), E, _np_ptr(ek), _np_ptr(ep), _np_ptr(ob), _np_ptr(ur), _np_ptr(inv),
+                             *controls, None if stop_flag is None else _np_ptr(stop_flag), _np_ptr(qt), _np_ptr(qtd), _np_ptr(po),
+                             _np_ptr(pod), _np_ptr(flags), _np_ptr(res), C.addressof(ms)), entry)
+    r = dict(result=res[0], kf_qt=qt[:K], kf_qt_d=qtd[:K], pos=po[:P], pos_d=pod[:P])
+    r[flags_key] = flags[:n_flags].astype(bool)
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r
+
+
+def _ba_stage_ms(entry):
+    ms = np.zeros(4, np.float32)
+    _check(getattr(_ba_lib(), entry)(_np_ptr(ms)), entry)
+    return dict(zip(("linearise", "schur", "solve", "trial"), (float(v) for v in ms)))
 
 
 def local_ba_capacity():
@@ -1937,36 +1975,14 @@ def local_ba(keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, max
     array of one element that another thread may set.
     -> dict(result: BA_RESULT_DTYPE record, kf_qt float32 [K, 7], kf_qt_d float64 [K, 7], pos float32 [P, 3], pos_d float64 [P, 3],
     outlier bool [E]) and, with timing, elapsed_ms (device time)."""
-    L = _ba_lib()
-    kf = _c(keyframes, BA_KEYFRAME_DTYPE).reshape(-1)
-    pw = _c(pos_w, np.float32).reshape(-1, 3)
-    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
-    ob, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
-    K, P, E = len(kf), len(pw), len(ek)
-    if [len(ep), len(ob), len(ur), len(inv)] != [E, 2 * E, E, E]:
-        raise ValueError("the edge arrays do not have one entry per edge")
-    if stop_flag is not None:
-        assert stop_flag.dtype == np.int32 and stop_flag.size == 1
-    qt, qtd = np.zeros((max(K, 1), 7), np.float32), np.zeros((max(K, 1), 7), np.float64)
-    po, pod = np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64)
-    out = np.zeros(max(E, 1), np.uint8)
-    res = np.zeros(1, BA_RESULT_DTYPE)
-    ms = C.c_float()
-    _check(L.msorb_local_ba(device, K, _np_ptr(kf), P, _np_ptr(pw), E, _np_ptr(ek), _np_ptr(ep), _np_ptr(ob), _np_ptr(ur), _np_ptr(inv),
-                            int(max_iterations), None if stop_flag is None else _np_ptr(stop_flag), _np_ptr(qt), _np_ptr(qtd),
-                            _np_ptr(po), _np_ptr(pod), _np_ptr(out), _np_ptr(res), C.addressof(ms)), "msorb_local_ba")
-    r = dict(result=res[0], kf_qt=qt[:K], kf_qt_d=qtd[:K], pos=po[:P], pos_d=pod[:P], outlier=out[:E].astype(bool))
-    if timing:
-        r["elapsed_ms"] = ms.value
-    return r
+    return _ba_call("msorb_local_ba", keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, (int(max_iterations),), stop_flag,
+                    device, timing, "outlier", "E")
 
 
 def local_ba_stage_ms():
     """msorb_local_ba_stage_ms: dict(linearise, schur, solve, trial) in device ms of this thread's last local_ba call; needs
     MSORB_LOCAL_BA_STAGES=1 in the environment before the library is loaded"""
-    ms = np.zeros(4, np.float32)
-    _check(_ba_lib().msorb_local_ba_stage_ms(_np_ptr(ms)), "msorb_local_ba_stage_ms")
-    return dict(zip(("linearise", "schur", "solve", "trial"), (float(v) for v in ms)))
+    return _ba_stage_ms("msorb_local_ba_stage_ms")
 
 
 # ---- Optimizer::BundleAdjustment (global BA) and its blocked dense solver on the device (include/msorb.h, appended to ABI 6002)
@@ -1975,11 +1991,8 @@ EXPORTS = EXPORTS + ("msorb_bundle_adjustment_capacity", "msorb_bundle_adjustmen
 
 
 def _gba_lib():
-    L = lib()
+    L = _ba_lib()
     vp, ci = C.c_void_p, C.c_int
-    L.msorb_bundle_adjustment_capacity.argtypes = []
-    L.msorb_bundle_adjustment.argtypes = [ci, ci, vp, ci, vp, ci] + [vp] * 5 + [ci, ci] + [vp] * 8
-    L.msorb_bundle_adjustment_stage_ms.argtypes = [vp]
     L.msorb_ldlt_block_sizes.argtypes = [vp, vp]
     L.msorb_ldlt_solve.argtypes = [ci, ci] + [vp] * 5
     return L
@@ -1987,7 +2000,7 @@ def _gba_lib():
 
 def bundle_adjustment_capacity():
     """the largest number of free KeyFrames msorb_bundle_adjustment accepts"""
-    return _gba_lib().msorb_bundle_adjustment_capacity()
+    return _ba_lib().msorb_bundle_adjustment_capacity()
 
 
 def ldlt_block_sizes():
@@ -2016,36 +2029,13 @@ def bundle_adjustment(keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_si
     """msorb_bundle_adjustment: Optimizer::BundleAdjustment on the device.  The arrays are local_ba's; fixed marks the InitKFid
     KeyFrame.  -> dict(result: BA_RESULT_DTYPE record, kf_qt, kf_qt_d [K, 7], pos, pos_d [P, 3], point_included bool [P]) and, with
     timing, elapsed_ms (device time)."""
-    L = _gba_lib()
-    kf = _c(keyframes, BA_KEYFRAME_DTYPE).reshape(-1)
-    pw = _c(pos_w, np.float32).reshape(-1, 3)
-    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
-    ob, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
-    K, P, E = len(kf), len(pw), len(ek)
-    if [len(ep), len(ob), len(ur), len(inv)] != [E, 2 * E, E, E]:
-        raise ValueError("the edge arrays do not have one entry per edge")
-    if stop_flag is not None:
-        assert stop_flag.dtype == np.int32 and stop_flag.size == 1
-    qt, qtd = np.zeros((max(K, 1), 7), np.float32), np.zeros((max(K, 1), 7), np.float64)
-    po, pod = np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64)
-    inc = np.zeros(max(P, 1), np.uint8)
-    res = np.zeros(1, BA_RESULT_DTYPE)
-    ms = C.c_float()
-    _check(L.msorb_bundle_adjustment(device, K, _np_ptr(kf), P, _np_ptr(pw), E, _np_ptr(ek), _np_ptr(ep), _np_ptr(ob), _np_ptr(ur),
-                                     _np_ptr(inv), int(n_iterations), int(bool(robust)),
-                                     None if stop_flag is None else _np_ptr(stop_flag), _np_ptr(qt), _np_ptr(qtd), _np_ptr(po),
-                                     _np_ptr(pod), _np_ptr(inc), _np_ptr(res), C.addressof(ms)), "msorb_bundle_adjustment")
-    r = dict(result=res[0], kf_qt=qt[:K], kf_qt_d=qtd[:K], pos=po[:P], pos_d=pod[:P], point_included=inc[:P].astype(bool))
-    if timing:
-        r["elapsed_ms"] = ms.value
-    return r
+    return _ba_call("msorb_bundle_adjustment", keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2,
+                    (int(n_iterations), int(bool(robust))), stop_flag, device, timing, "point_included", "P")
 
 
 def bundle_adjustment_stage_ms():
     """local_ba_stage_ms for this thread's last bundle_adjustment call (MSORB_LOCAL_BA_STAGES=1)"""
-    ms = np.zeros(4, np.float32)
-    _check(_gba_lib().msorb_bundle_adjustment_stage_ms(_np_ptr(ms)), "msorb_bundle_adjustment_stage_ms")
-    return dict(zip(("linearise", "schur", "solve", "trial"), (float(v) for v in ms)))
+    return _ba_stage_ms("msorb_bundle_adjustment_stage_ms")
 
 
 EXPORTS = EXPORTS + ("msorb_create_new_map_points_kf", "msorb_create_new_map_points_stage_ms")

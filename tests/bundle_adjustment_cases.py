@@ -1,6 +1,6 @@
 """Optimizer::BundleAdjustment (src/Optimizer.cc:60-364, the body of GlobalBundleAdjustemnt; pinhole KeyFrames without a second
 camera) restated in float64 numpy on the pieces of tests/local_ba_cases.py, which are imported unchanged: the edges, the plan, the
-ordered sums, the L D L^T, the scene generator, the SE3 pieces.  Also the named scenes of the GPU tests.  No GPU, no library.
+ordered sums, the Levenberg loop (levenberg), the L D L^T, the scene generator, the SE3 pieces.  Also the named scenes of the GPU tests.  No GPU, no library.
 
 `python tests/bundle_adjustment_cases.py --measure` writes tests/golden/bundle_adjustment_sensitivity.json.
 
@@ -25,23 +25,18 @@ import numpy as np
 
 import local_ba_cases as lc
 import pose_opt_cases as pc
-from local_ba_cases import Problem, Plan, seg_sum, ldlt_solve, make_scene, point_inverse, estimate_distance, smallest_movement  # noqa: F401
-from pose_opt_cases import F32, F64, DBL_MAX, rotate, normalize_rotation, oplus, ordered_sum
+from local_ba_cases import Problem, ldlt_solve, make_scene, estimate_distance, smallest_movement
+from pose_opt_cases import F32, F64, rotate, normalize_rotation
 
 VARIANTS = ("forward", "reverse", "pairwise", "lapack")
 DELTA_MONO = float(F32(math.sqrt(5.99)))      # Optimizer.cc:128: thHuber2D is sqrt(5.99) in this routine, not LocalBundleAdjustment's sqrt(5.991)
 DELTA_STEREO = pc.DELTA_STEREO                # :129
 DENSE_MAX_KF = 40
-SYM3, UP6 = lc.SYM3, lc.UP6
 
 
 def variants_of(s):
     free = int((~np.asarray(s["kf"]["fixed"]).astype(bool)).sum())
     return VARIANTS + (("dense",) if free <= DENSE_MAX_KF else ())
-
-
-def _order(variant):
-    return variant if variant in ("reverse", "pairwise") else "forward"
 
 
 def lapack_solve(S, b, x):
@@ -56,51 +51,10 @@ def lapack_solve(S, b, x):
     return True
 
 
-def _solve_schur(pr, Hpp, bp, Hll, bl, W, lam, x, order, solve):
-    """local_ba_cases._solve_schur with the solver of the reduced system as an argument"""
-    pl = pr.plan
-    Kf, n = pl.Kf, 6 * pl.Kf
-    Dinv, db = point_inverse(Hll, bl, lam)
-    xs = x[:n].copy()
-    if Kf:
-        with np.errstate(all="ignore"):
-            a, b = pl.pair_a, pl.pair_b
-            Di = Dinv[pr.ep[a]]
-            Wa, Wb = W[a], W[b]
-            Y = np.stack([(Wa[:, :, 0] * Di[:, SYM3[c][0], None] + Wa[:, :, 1] * Di[:, SYM3[c][1], None]) + Wa[:, :, 2] * Di[:, SYM3[c][2], None]
-                          for c in range(3)], -1)
-            T = (Y[:, :, None, 0] * Wb[:, None, :, 0] + Y[:, :, None, 1] * Wb[:, None, :, 1]) + Y[:, :, None, 2] * Wb[:, None, :, 2]
-            Hd = np.zeros((Kf, 6, 6), F64)
-            for k, (r, c) in enumerate(UP6):
-                Hd[:, r, c] = Hd[:, c, r] = Hpp[:, k]
-            Hd[:, range(6), range(6)] += lam
-            seg = np.concatenate([pl.diag_pair, pl.pair_seg])
-            terms = np.concatenate([Hd.reshape(Kf, 36), -T.reshape(-1, 36)])
-            o = np.argsort(seg, kind="stable")
-            blocks = seg_sum(terms[o], seg[o], len(pl.pair_key), order).reshape(-1, 6, 6)
-            S = np.zeros((n, n), F64)
-            for k in range(len(pl.pair_key)):
-                i, j = int(pl.pair_i[k]), int(pl.pair_j[k])
-                if i == j:
-                    S[6 * i:6 * i + 6, 6 * i:6 * i + 6] = np.triu(blocks[k]).T + np.triu(blocks[k], 1)
-                else:
-                    S[6 * j:6 * j + 6, 6 * i:6 * i + 6] = blocks[k].T
-            fe = pl.kf_edge
-            dbe = db[pr.ep[fe]]
-            ct = np.stack([(W[fe, r, 0] * dbe[:, 0] + W[fe, r, 1] * dbe[:, 1]) + W[fe, r, 2] * dbe[:, 2] for r in range(6)], -1)
-            bs = (bp - seg_sum(ct, pl.kf_seg, Kf, order)).ravel()
-        if not solve(S, bs, xs):
-            return False
-    x[:n] = xs
-    x[n:] = lc._point_update(pr, W, bl, Dinv, x, order).ravel()
-    return True
-
-
 def bundle_adjustment(s, variant="forward", n_iterations=5, robust=True, stop=False):
     """s: a scene (kf, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2).  stop: the stop flag is set on entry.
     -> dict(status, iterations, trials, rejected_trials, n_outliers (0), kf_qt_d [K, 7], kf_qt, pos_d [P, 3], pos,
     point_included [P], chi2_initial, chi2_final, lambda_final)"""
-    order = _order(variant)
     P_all = len(s["pos_w"])
     ep_all = np.asarray(s["edge_point"], int)
     included = np.bincount(ep_all, minlength=P_all) > 0                   # :261-263
@@ -108,11 +62,9 @@ def bundle_adjustment(s, variant="forward", n_iterations=5, robust=True, stop=Fa
     sub = dict(s, pos_w=np.asarray(s["pos_w"])[included], edge_point=new_index[ep_all])
     pr = Problem(sub)
     pr.delta = np.where(pr.stereo, DELTA_STEREO, DELTA_MONO)              # :128-129, :177, :209
-    pl = pr.plan
-    P, E, Kf = pr.P, pr.E, pl.Kf
     kf = s["kf"]
     q_in, t_in = np.asarray(kf["q"]), np.asarray(kf["t"])
-    res = dict(status=0, iterations=0, trials=0, rejected_trials=0, n_outliers=0, chi2_initial=0.0, chi2_final=0.0, lambda_final=0.0)
+    res = dict(status=0, n_outliers=0)
 
     def huber(chi2):
         return pr.huber(chi2) if robust else (chi2, np.ones_like(chi2))    # :174, :206
@@ -120,75 +72,8 @@ def bundle_adjustment(s, variant="forward", n_iterations=5, robust=True, stop=Fa
     q = np.array([normalize_rotation(v) for v in q_in.astype(F64)]).reshape(-1, 4)      # :138 (SE3Quat's constructor normalises)
     t = t_in.astype(F64).copy()
     X = np.asarray(sub["pos_w"]).astype(F64).copy()                       # :159
-    n = 6 * Kf
-    x = np.zeros(n + 3 * P, F64)
-    lam, ni, n_bad, ok = 0.0, 2.0, 0, E > 0
-    it = 0
-    while it < n_iterations and ok and not stop:                          # sparse_optimizer.cpp:376 (terminate())
-        e, p, chi2 = pr.error(q, t, X)
-        rho0, rho1 = huber(chi2)
-        current = float(ordered_sum(rho0[:, None], order)[0])
-        ini = current
-        Ja, Jb = pr.jacobians(q, p)
-        eHll, ebl, eHpp, ebp, W = pr.quadratic_forms(e, rho1, Ja, Jb)
-        Hl = seg_sum(np.concatenate([eHll, ebl], 1), pr.ep, P, order)
-        Hll, bl = Hl[:, :6], Hl[:, 6:]
-        Hp = seg_sum(np.concatenate([eHpp, ebp], 1)[pl.kf_edge], pl.kf_seg, Kf, order)
-        Hpp, bp = Hp[:, :21], Hp[:, 21:]
-        if it == 0:
-            res["chi2_initial"] = current
-            diag = np.concatenate([np.abs(Hpp[:, [0, 6, 11, 15, 18, 20]]).ravel(), np.abs(Hll[:, [0, 3, 5]]).ravel()])
-            lam, ni, n_bad = 1e-5 * float(max(diag.max() if len(diag) else 0.0, 0.0)), 2.0, 0
-        rho, qmax = 0.0, 0
-        while True:
-            bq, bt, bX = q.copy(), t.copy(), X.copy()
-            if variant == "dense":
-                ok2 = lc._solve_dense(pr, Hpp, bp, Hll, bl, W, lam, x)
-            else:
-                ok2 = _solve_schur(pr, Hpp, bp, Hll, bl, W, lam, x, order, lapack_solve if variant == "lapack" else ldlt_solve)
-            for i in range(Kf):
-                k = pl.kf_of_free[i]
-                nq, nt = oplus(list(q[k]), list(t[k]), [float(v) for v in x[6 * i:6 * i + 6]])
-                q[k], t[k] = nq, nt
-            X = X + x[n:].reshape(P, 3)
-            _, _, chi2 = pr.error(q, t, X)
-            r0, _ = huber(chi2)
-            temp = float(ordered_sum(r0[:, None], order)[0])
-            if not ok2:
-                temp = DBL_MAX
-            b_all = np.concatenate([bp.ravel(), bl.ravel()])
-            with np.errstate(all="ignore"):
-                scale = float(ordered_sum((x * (lam * x + b_all))[:, None], order)[0]) + 1e-3
-                rho = float((F64(current) - F64(temp)) / F64(scale))
-            res["trials"] += 1
-            if rho > 0 and math.isfinite(temp):
-                yy = 2 * rho - 1
-                alpha = min(1. - (yy * yy) * yy, 2. / 3.)
-                lam *= max(1. / 3., alpha)
-                ni = 2.0
-                current = temp
-            else:
-                lam *= ni
-                ni *= 2
-                q, t, X = bq, bt, bX
-                res["rejected_trials"] += 1
-            qmax += 1
-            if not (rho < 0 and qmax < 10):
-                break
-        res["iterations"] += 1
-        res["chi2_final"] = current
-        it += 1
-        if qmax == 10 or rho == 0:
-            ok = False
-            continue
-        if (ini - current) * 1e3 < ini:
-            n_bad += 1
-        else:
-            n_bad = 0
-        if n_bad >= 3:
-            ok = False
-    if res["iterations"] == 0:
-        res["chi2_final"] = res["chi2_initial"]
+    q, t, X, lam, counts_ = lc.levenberg(pr, q, t, X, variant, n_iterations, huber, stop, lapack_solve if variant == "lapack" else ldlt_solve)
+    res.update(counts_)
     qt = np.concatenate([q, t], 1)
     qt[pr.fixed] = np.concatenate([q_in, t_in], 1).astype(F64)[pr.fixed]  # a fixed KeyFrame's output repeats its input
     pos = np.asarray(s["pos_w"]).astype(F64).copy()

@@ -15,7 +15,7 @@ coefficients of bschur, the cost, computeScale):
             first (the order that keeps the fill inside the pose block; g2o's sparse Cholesky picks a fill-reducing order too).
             It measures what the elimination order alone moves.
 
-What the restatement fixes where the reference leaves it to Eigen (ms-slam_amd/csrc/local_ba.hip does the same):
+What the restatement fixes where the reference leaves it to Eigen (ms-slam_amd/csrc/bundle_adjustment.hip does the same):
   * a product of small matrices is the plain row-by-column sum, left to right, no fused multiply-adds;
   * the products with the structural zeros of projectJac are left out;
   * D->inverse() (block_solver.hpp:389) is Eigen's 3x3 inverse: cofactors times 1 / det, det along the first column, D read
@@ -68,7 +68,7 @@ def seg_sum(terms, seg, nseg, order):
 
 
 def _order(variant):
-    return "forward" if variant == "dense" else variant
+    return variant if variant in ("reverse", "pairwise") else "forward"
 
 
 # ------------------------------------------------------------------------------------------------------------------ plan
@@ -280,37 +280,23 @@ def ldlt_solve(A, b, x):
 
 
 # ------------------------------------------------------------------------------------------------------------ the routine
-def local_ba(s, variant="forward", max_iterations=10):
-    """s: a scene of make_scene (or any dict with kf, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2).
-    -> dict(status, iterations, trials, rejected_trials, n_outliers, kf_qt_d [K, 7], kf_qt (float32), pos_d, pos, outlier [E],
-    chi2 [E] (at the final estimate), depth [E], chi2_initial, chi2_final, lambda_final)"""
+def levenberg(pr, q, t, X, variant, iterations, huber, stop=False, solve=ldlt_solve):
+    """g2o's loop (sparse_optimizer.cpp:376-389 around OptimizationAlgorithmLevenberg::solve, levenberg.cpp:61-170) from the state
+    q [K, 4], t [K, 3], X [P, 3] of the Problem pr; q and t are updated in place.  huber: chi2 -> (rho, rho'); stop: terminate()
+    holds; solve: the solver of the reduced system.
+    -> q, t, X, lambda, dict(iterations, trials, rejected_trials, chi2_initial, chi2_final)"""
     order = _order(variant)
-    pr = Problem(s)
     pl = pr.plan
-    K, P, E, Kf = pr.K, pr.P, pr.E, pl.Kf
-    kf = s["kf"]
-    q_in, t_in, X_in = np.asarray(kf["q"]), np.asarray(kf["t"]), np.asarray(s["pos_w"])
-    res = dict(status=0, iterations=0, trials=0, rejected_trials=0, n_outliers=0, chi2_initial=0.0, chi2_final=0.0, lambda_final=0.0)
-
-    def untouched(status):
-        res.update(status=status, kf_qt_d=np.concatenate([q_in, t_in], 1).astype(F64), pos_d=X_in.astype(F64),
-                   outlier=np.zeros(E, bool), chi2=np.zeros(E), depth=np.zeros(E))
-        res["kf_qt"], res["pos"] = res["kf_qt_d"].astype(F32), res["pos_d"].astype(F32)
-        return res
-
-    if Kf == K:                                                  # :1098-1102
-        return untouched(1)
-    q = np.array([normalize_rotation(v) for v in q_in.astype(F64)])      # :1134, :1150 (SE3Quat's constructor normalises)
-    t = t_in.astype(F64).copy()
-    X = X_in.astype(F64).copy()                                  # :1200
+    P, E, Kf = pr.P, pr.E, pl.Kf
+    res = dict(iterations=0, trials=0, rejected_trials=0, chi2_initial=0.0, chi2_final=0.0)
     n = 6 * Kf
     x = np.zeros(n + 3 * P, F64)
     lam, ni, n_bad, ok = 0.0, 2.0, 0, E > 0
     it = 0
-    while it < max_iterations and ok:                            # sparse_optimizer.cpp:376
+    while it < iterations and ok and not stop:                   # sparse_optimizer.cpp:376 (terminate())
         # ---- OptimizationAlgorithmLevenberg::solve ----
         e, p, chi2 = pr.error(q, t, X)                           # :75
-        rho0, rho1 = pr.huber(chi2)
+        rho0, rho1 = huber(chi2)
         current = float(ordered_sum(rho0[:, None], order)[0])    # :82
         ini = current
         Ja, Jb = pr.jacobians(q, p)                              # :87 buildSystem
@@ -329,14 +315,14 @@ def local_ba(s, variant="forward", max_iterations=10):
             if variant == "dense":
                 ok2 = _solve_dense(pr, Hpp, bp, Hll, bl, W, lam, x)
             else:
-                ok2 = _solve_schur(pr, Hpp, bp, Hll, bl, W, lam, x, order)
+                ok2 = _solve_schur(pr, Hpp, bp, Hll, bl, W, lam, x, order, solve)
             for i in range(Kf):                                  # update (:115): VertexSE3Expmap::oplusImpl
                 k = pl.kf_of_free[i]
                 nq, nt = oplus(list(q[k]), list(t[k]), [float(v) for v in x[6 * i:6 * i + 6]])
                 q[k], t[k] = nq, nt
             X = X + x[n:].reshape(P, 3)                          # VertexSBAPointXYZ::oplusImpl
             _, _, chi2 = pr.error(q, t, X)                       # :123
-            r0, _ = pr.huber(chi2)
+            r0, _ = huber(chi2)
             temp = float(ordered_sum(r0[:, None], order)[0])     # :124
             if not ok2:
                 temp = DBL_MAX                                   # :126-127
@@ -373,6 +359,32 @@ def local_ba(s, variant="forward", max_iterations=10):
             ok = False
     if res["iterations"] == 0:
         res["chi2_final"] = res["chi2_initial"]
+    return q, t, X, lam, res
+
+
+def local_ba(s, variant="forward", max_iterations=10):
+    """s: a scene of make_scene (or any dict with kf, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2).
+    -> dict(status, iterations, trials, rejected_trials, n_outliers, kf_qt_d [K, 7], kf_qt (float32), pos_d, pos, outlier [E],
+    chi2 [E] (at the final estimate), depth [E], chi2_initial, chi2_final, lambda_final)"""
+    pr = Problem(s)
+    K, E, Kf = pr.K, pr.E, pr.plan.Kf
+    kf = s["kf"]
+    q_in, t_in, X_in = np.asarray(kf["q"]), np.asarray(kf["t"]), np.asarray(s["pos_w"])
+    res = dict(status=0, iterations=0, trials=0, rejected_trials=0, n_outliers=0, chi2_initial=0.0, chi2_final=0.0, lambda_final=0.0)
+
+    def untouched(status):
+        res.update(status=status, kf_qt_d=np.concatenate([q_in, t_in], 1).astype(F64), pos_d=X_in.astype(F64),
+                   outlier=np.zeros(E, bool), chi2=np.zeros(E), depth=np.zeros(E))
+        res["kf_qt"], res["pos"] = res["kf_qt_d"].astype(F32), res["pos_d"].astype(F32)
+        return res
+
+    if Kf == K:                                                  # :1098-1102
+        return untouched(1)
+    q = np.array([normalize_rotation(v) for v in q_in.astype(F64)])      # :1134, :1150 (SE3Quat's constructor normalises)
+    t = t_in.astype(F64).copy()
+    X = X_in.astype(F64).copy()                                  # :1200
+    q, t, X, lam, counts_ = levenberg(pr, q, t, X, variant, max_iterations, pr.huber)
+    res.update(counts_)
     # ---- :1331-1373 ----
     _, p, chi2 = pr.error(q, t, X)
     with np.errstate(all="ignore"):
@@ -402,7 +414,7 @@ def _point_update(pr, W, bl, Dinv, x, order):
     return sym3_times(Dinv, cl)
 
 
-def _solve_schur(pr, Hpp, bp, Hll, bl, W, lam, x, order):
+def _solve_schur(pr, Hpp, bp, Hll, bl, W, lam, x, order, solve=ldlt_solve):
     pl = pr.plan
     Kf, P, n = pl.Kf, pr.P, 6 * pl.Kf
     Dinv, db = point_inverse(Hll, bl, lam)
@@ -436,7 +448,7 @@ def _solve_schur(pr, Hpp, bp, Hll, bl, W, lam, x, order):
             ct = np.stack([(W[fe, r, 0] * dbe[:, 0] + W[fe, r, 1] * dbe[:, 1]) + W[fe, r, 2] * dbe[:, 2] for r in range(6)], -1)   # Bi db (:413)
             coeff = seg_sum(ct, pl.kf_seg, Kf, order)
             bs = (bp - coeff).ravel()                            # :436-439
-        ok = ldlt_solve(S, bs, xs)
+        ok = solve(S, bs, xs)
         if not ok:
             return False                                         # :456-457: x as it was
     x[:n] = xs

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 
 COUNTS = ("status", "iterations", "trials", "rejected_trials", "n_outliers")
 ARGS = ("kf", "pos_w", "edge_kf", "edge_point", "xy", "u_right", "inv_sigma2")
+ESTIMATES = ("kf_qt_d", "pos_d", "kf_qt", "pos")
 
 
 @pytest.fixture(scope="module")
@@ -88,10 +89,34 @@ def test_against_local_ba_on_a_problem_both_accept(msorb_mod, golden):
     b = _run(msorb_mod, s, n_iterations=10, robust=True)
     ra, rb = a["result"], b["result"]
     d = lc.estimate_distance(s, a, b)
-    print(f"local_ba vs bundle_adjustment: pose {d[0]:.3e}, points {d[1]:.3e}, bound {golden['bound']:.3e}; bit-equal: "
-          f"{a['kf_qt_d'].tobytes() == b['kf_qt_d'].tobytes() and a['pos_d'].tobytes() == b['pos_d'].tobytes()}")
+    print(f"local_ba vs bundle_adjustment: pose {d[0]:.3e}, points {d[1]:.3e}, bound {golden['bound']:.3e}")
     assert [int(ra[k]) for k in COUNTS[:4]] == [int(rb[k]) for k in COUNTS[:4]]
     assert max(d) <= golden["bound"]
+    # one engine, the same kernels, stereo edges only (the mono Huber widths differ), and two solvers that return the same bits
+    assert all(a[k].tobytes() == b[k].tobytes() for k in ESTIMATES)
+
+
+@pytest.fixture(scope="module")
+def k128():
+    """local BA at its capacity: 128 free KeyFrames, n = 768 = 16 panels of the blocked solve (one panel up to n = 48; the largest
+    other scene that both entries take has 24 free KeyFrames).  Stereo edges only, as k24_small; not an entry of SCENES, so no
+    golden D moves.  K = 129, P = 400, E = 2378; the restatements: 5 iterations, 5 trials, none rejected, 0.45 s each."""
+    s = bc._without_mono_edges(bc.make_windowed_scene(seed=39, free=128, points=400, stereo=1.0))
+    return s, lc.local_ba(s, "forward", 5), bc.bundle_adjustment(s, "forward", 5, True, False)
+
+
+def test_local_ba_at_its_capacity_against_this_entry(msorb_mod, golden, k128):
+    s, ref_local, ref = k128
+    assert int((s["kf"]["fixed"] == 0).sum()) == msorb_mod.local_ba_capacity() == 128
+    a = msorb_mod.local_ba(*(s[k] for k in ARGS), max_iterations=5)
+    b = msorb_mod.bundle_adjustment(*(s[k] for k in ARGS), n_iterations=5, robust=True)
+    d = [lc.estimate_distance(s, r, ref) for r in (a, b)]
+    print(f"k128: local_ba {d[0][0]:.3e} {d[0][1]:.3e}, bundle_adjustment {d[1][0]:.3e} {d[1][1]:.3e}, bound {golden['bound']:.3e}; "
+          f"counts {[int(a['result'][k]) for k in COUNTS[:4]]} {[int(b['result'][k]) for k in COUNTS[:4]]} ref {[ref[k] for k in COUNTS[:4]]}")
+    assert all(a[k].tobytes() == b[k].tobytes() for k in ESTIMATES)
+    assert [int(a["result"][k]) for k in COUNTS[:4]] == [int(b["result"][k]) for k in COUNTS[:4]] == [ref[k] for k in COUNTS[:4]]
+    assert max(max(x) for x in d) <= golden["bound"]
+    assert np.array_equal(a["outlier"], ref_local["outlier"])
 
 
 def test_the_existing_entry_refuses_the_chain_and_this_one_does_not(msorb_mod):

@@ -1,4 +1,4 @@
-"""Optimizer::LocalBundleAdjustment on the device (csrc/local_ba.hip) through the C ABI against the float64 restatement of
+"""Optimizer::LocalBundleAdjustment on the device (csrc/bundle_adjustment.hip) through the C ABI against the float64 restatement of
 tests/local_ba_cases.py ('forward' = g2o's order).
 
 Bounds.  D is the largest difference between any two of the restatement's four variants (three summation orders and the
