@@ -1313,6 +1313,39 @@ int msorb_two_view_reconstruct(int device, int n1, const float* keys1, int n2, c
                                float* p3d, uint8_t* inlier_out, float* hyp_score_out, int* hyp_count_out, uint8_t* hyp_mask_out,
                                float* elapsed_ms);
 
+/* Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1410-1675 for loop closing, :1677-1985 for map merging; not the 4-DoF
+ * inertial form) after the gathering loops, on the device: g2o's 7-DoF pose graph of VertexSim3Expmap and EdgeSim3 with the
+ * identity for information and no kernel, the edge's NUMERIC Jacobian (central differences of 1e-9 through oplus), Levenberg from
+ * the user lambda 1e-16, in double.  Appended to ABI 6002 as the bundle adjustments were: MSORB_ABI_VERSION stays 6002.
+ * vertices [n_vertices]: the estimate (q = x, y, z, w; nothing normalises it), fixed (setFixed) and fix_scale (_fix_scale: the
+ * update's seventh entry is zeroed).  Edge e joins vertices edge_v0[e] -> edge_v1[e] with measurement Sjw * Swi as 8 doubles
+ * (q[4], t[3], s); error = log(C * v0 * v1^-1).  Several edges on one pair are legal.  g2o's active set holds: an edge with two
+ * fixed ends enters neither the cost nor H; a free vertex without an active edge keeps its estimate bit for bit.  The 7 Kf x 7 Kf
+ * system (Kf: free vertices with an active edge, in the caller's order) is solved DENSELY by the blocked L D L^T of
+ * msorb_ldlt_solve, unpivoted, where the reference runs a sparse Cholesky.  estimates_out [8 per vertex]: q, t, s.
+ * Errors: MSORB_E_ARG for an edge that names a vertex out of range or has v0 == v1, a null required array, a negative count.
+ * More than msorb_essential_graph_capacity() free vertices in the system, or no room on the device for it: MSORB_E_CAPACITY,
+ * nothing launched, no output written.  No active edge: zero iterations and the estimates as they came.  Two calls on the same
+ * input return the same bits.  Re-entrant like msorb_local_ba.  *elapsed_ms (may be NULL): device time. */
+typedef struct msorb_eg_vertex {
+    double q[4], t[3], s;
+    int32_t fixed, fix_scale;
+} msorb_eg_vertex;
+typedef struct msorb_eg_result {
+    int32_t status;            /* 0 */
+    int32_t iterations, trials, rejected_trials;
+    int32_t solver_failures;   /* trials whose factorisation met a pivot that was not positive */
+    int32_t stop;              /* 0: every iteration ran; 1: Terminate (ten trials, or rho == 0); 2: the fork's _nBad >= 3 */
+    double chi2_initial, chi2_final, lambda_final;
+} msorb_eg_result;
+int msorb_essential_graph_capacity(void);              /* free vertices: 1024 (the system is 7168^2 doubles = 411 MB) */
+int msorb_essential_graph(int device, int n_vertices, const msorb_eg_vertex* vertices, int n_edges, const int* edge_v0,
+                          const int* edge_v1, const double* measurements, int iterations, double* estimates_out,
+                          msorb_eg_result* result, float* elapsed_ms);
+/* Device ms of the calling thread's last msorb_essential_graph call: linearise, assemble, solve, trial.  Needs
+ * MSORB_LOCAL_BA_STAGES=1 in the environment before the library is loaded (MSORB_E_ARG otherwise, zeros). */
+int msorb_essential_graph_stage_ms(float ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037), LocalBundleAdjustment, BundleAdjustment / GlobalBundleAdjustemnt and the two OptimizeSim3 (further down), each on
+// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037), LocalBundleAdjustment, BundleAdjustment / GlobalBundleAdjustemnt, the two OptimizeSim3 and the loop-closing OptimizeEssentialGraph (further down), each on
 // its device entry of libmsorb.  First PoseOptimization (msorb_pose_optimization_batch /
 // msorb_frame_pose_optimization), written against the reference's own types by name (a template: this header compiles inside
 // MS-SLAM, where Frame / MapPoint are the real classes, and in tests/dropin_poseopt_main.cc, where they are minimal stand-ins
@@ -25,14 +25,17 @@
 #ifndef MSORB_OPTIMIZER_DEVICE_H
 #define MSORB_OPTIMIZER_DEVICE_H
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <list>
 #include <map>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <tuple>
 #include <utility>
@@ -42,6 +45,7 @@
 #include <vector>
 
 #include "msorb.h"
+#include "../csrc/sim3_opt_device.h"   // the product, inverse and map of Sim3 in double (OptimizeEssentialGraph)
 
 namespace ORB_SLAM3 {
 namespace msorb_host {
@@ -643,6 +647,327 @@ int OptimizeSim3(KFPtr pKF1, KFPtr pKF2, std::vector<MPPtr>& vpMatches1, std::ve
             vpMatches2[G.vnIndexEdge[k]].reset();
         }
     return nIn;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::OptimizeEssentialGraph, the loop-closing overload (src/Optimizer.cc:1410-1675, LoopClosing.cc:1137), on
+// msorb_essential_graph.  The merge overload (:1677-1985) follows it.
+//
+//   bool ORB_SLAM3::msorb_host::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+//                                                      bFixScale)
+//
+// the reference's parameter list, and its effects: under pMap->mMutexMapUpdate SetPose of every KeyFrame with the corrected Sim3 as
+// [R t / s], every point that is not bad moved by correctedSwr.map(Srw.map(P)) through its reference KeyFrame (mnCorrectedReference
+// when mnCorrectedByKF == pCurKF->mnId) and UpdateNormalAndDepth, then IncreaseChangeIndex.  true = done.
+//
+// false = NOT handled, nothing touched, the caller runs Optimizer::OptimizeEssentialGraph: a KeyFrame of GetAllKeyFrames() that is
+// bad (the reference would dereference its missing vertex at :1639-1640), a KeyFrame id above GetMaxKFid() (the reference would read
+// past its vectors), or more free KeyFrames than msorb_essential_graph_capacity() (or no room on the device for their system).
+// An edge to a KeyFrame that is no vertex (a parent, loop edge or mPrevKF outside GetAllKeyFrames()) is not added, as g2o's addEdge
+// refuses it, and the rest is optimised.
+//
+// What runs where.  The vertex loop, the CorrectedSim3 / NonCorrectedSim3 look-ups, the weight gate, the five edge arms and the
+// measurements Sjw * Swi (double, through the product and inverse of csrc/sim3_opt_device.h: the device's own) stay host code, as
+// the reference's; optimize(20) is the device's.  Sophus' cast<double>() of a pose normalises the widened quaternion again
+// (so3.hpp:401-408): restated as q / sqrt(((x^2 + y^2) + z^2) + w^2).
+template <class S>
+inline msorb::sim3opt::Sim3 EgSim3(const S& s) {
+    const auto q = s.rotation();
+    const auto t = s.translation();
+    return msorb::sim3opt::Sim3{(double)q.x(), (double)q.y(), (double)q.z(), (double)q.w(), (double)t(0), (double)t(1), (double)t(2),
+                                (double)s.scale()};
+}
+
+template <class MapT, class KFPtr, class PoseMapT, class ConnectionsT>
+bool OptimizeEssentialGraph(MapT* pMap, KFPtr pLoopKF, KFPtr pCurKF, const PoseMapT& NonCorrectedSim3, const PoseMapT& CorrectedSim3,
+                            const ConnectionsT& LoopConnections, const bool& bFixScale, int device = 0) {
+    using msorb::sim3opt::Sim3;
+    using msorb::sim3opt::sim3_inverse;
+    using msorb::sim3opt::sim3_mul;
+    const auto vpKFs = pMap->GetAllKeyFrames();                                                          // :1426-1427
+    const auto vpMPs = pMap->GetAllMapPoints();
+    const unsigned long nMaxKFid = pMap->GetMaxKFid();
+    const Sim3 identity{0, 0, 0, 1, 0, 0, 0, 1};                                                         // g2o::Sim3(): what the vectors of :1431-1432 hold by default
+    std::vector<Sim3> vScw(nMaxKFid + 1, identity);
+    std::vector<int> index(nMaxKFid + 1, -1);                                                            // optimizer.vertex(mnId)
+    std::vector<msorb_eg_vertex> vertices;
+    const int minFeat = 100;                                                                             // :1439
+    int n_free = 0;
+    for (const auto& pKF : vpKFs) {                                                                      // :1442-1473
+        if (pKF->isBad()) return false;
+        const unsigned long nIDi = pKF->mnId;
+        const auto it = CorrectedSim3.find(pKF);
+        if (it != CorrectedSim3.end()) {
+            vScw[nIDi] = EgSim3(it->second);
+        } else {                                                                                         // :1456-1457
+            const auto Tcw = pKF->GetPose();
+            const auto q = Tcw.unit_quaternion();
+            const auto t = Tcw.translation();
+            const double x = (double)q.x(), y = (double)q.y(), z = (double)q.z(), w = (double)q.w();
+            const double len = std::sqrt(((x * x + y * y) + z * z) + w * w);
+            vScw[nIDi] = Sim3{x / len, y / len, z / len, w / len, (double)t(0), (double)t(1), (double)t(2), 1.0};
+        }
+        msorb_eg_vertex v;
+        const Sim3& S = vScw[nIDi];
+        v.q[0] = S.qx; v.q[1] = S.qy; v.q[2] = S.qz; v.q[3] = S.qw; v.t[0] = S.tx; v.t[1] = S.ty; v.t[2] = S.tz; v.s = S.s;
+        v.fixed = pKF->mnId == pMap->GetInitKFid() ? 1 : 0;                                              // :1462-1463
+        v.fix_scale = bFixScale ? 1 : 0;                                                                 // :1467
+        n_free += v.fixed ? 0 : 1;
+        index[nIDi] = (int)vertices.size();
+        vertices.push_back(v);
+    }
+    if (n_free > msorb_essential_graph_capacity()) return false;
+    std::vector<int> v0, v1;
+    std::vector<double> meas;
+    bool missing = false;
+    auto add_edge = [&](unsigned long nIDi, unsigned long nIDj, const Sim3& Sji) {   // vertex 0 = i, vertex 1 = j
+        if (nIDi > nMaxKFid || nIDj > nMaxKFid) { missing = true; return; }   // (the reference would read past its vectors)
+        if (index[nIDi] < 0 || index[nIDj] < 0) return;   // optimizer.vertex() is null: g2o's addEdge refuses the edge, the rest goes on
+        v0.push_back(index[nIDi]);
+        v1.push_back(index[nIDj]);
+        const double m[8] = {Sji.qx, Sji.qy, Sji.qz, Sji.qw, Sji.tx, Sji.ty, Sji.tz, Sji.s};
+        meas.insert(meas.end(), m, m + 8);
+    };
+    auto non_corrected = [&](const KFPtr& pKFx) -> Sim3 {                            // "if in NonCorrectedSim3, that; else vScw"
+        const auto itx = NonCorrectedSim3.find(pKFx);
+        if (itx != NonCorrectedSim3.end()) return EgSim3(itx->second);
+        if (pKFx->mnId > nMaxKFid) { missing = true; return Sim3{0, 0, 0, 1, 0, 0, 0, 1}; }
+        return vScw[pKFx->mnId];
+    };
+    std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+    const float ratio = 0.3;                                                                             // :1481
+    for (const auto& mit : LoopConnections) {                                                            // :1483-1511
+        const KFPtr& pKF = mit.first;
+        const unsigned long nIDi = pKF->mnId;
+        if (nIDi > nMaxKFid) return false;
+        const Sim3 Swi = sim3_inverse(vScw[nIDi]);
+        for (const KFPtr& pKFj : mit.second) {
+            const unsigned long nIDj = pKFj->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat * ratio) continue;   // :1494
+            if (nIDj > nMaxKFid) return false;
+            add_edge(nIDi, nIDj, sim3_mul(vScw[nIDj], Swi));
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    for (const KFPtr& pKF : vpKFs) {                                                                     // :1514-1625
+        const unsigned long nIDi = pKF->mnId;
+        const Sim3 Swi = sim3_inverse(non_corrected(pKF));                                               // :1521-1526
+        const KFPtr pParentKF = pKF->GetParent();
+        if (pParentKF) add_edge(nIDi, pParentKF->mnId, sim3_mul(non_corrected(pParentKF), Swi));         // :1531-1551
+        const auto sLoopEdges = pKF->GetLoopEdges();                                                     // :1554-1576
+        for (const KFPtr& pLKF : sLoopEdges)
+            if (pLKF->mnId < pKF->mnId) add_edge(nIDi, pLKF->mnId, sim3_mul(non_corrected(pLKF), Swi));
+        const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);                                 // :1579-1606
+        for (const KFPtr& pKFn : vpConnectedKFs) {
+            if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                    add_edge(nIDi, pKFn->mnId, sim3_mul(non_corrected(pKFn), Swi));
+                }
+            }
+        }
+        if (pKF->bImu && pKF->mPrevKF)                                                                   // :1609-1624: a plain EdgeSim3
+            add_edge(nIDi, pKF->mPrevKF->mnId, sim3_mul(non_corrected(pKF->mPrevKF), Swi));
+    }
+    if (missing) return false;
+    std::vector<double> est(8 * vertices.size());
+    msorb_eg_result r;
+    const int rc = msorb_essential_graph(device, (int)vertices.size(), vertices.data(), (int)v0.size(), v0.data(), v1.data(), meas.data(), 20,
+                                         est.data(), &r, nullptr);                                      // :1627-1630
+    if (rc == MSORB_E_CAPACITY) return false;
+    if (rc != MSORB_OK) fail_call("msorb_essential_graph");
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                                            // :1631
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose().unit_quaternion())>::type QuatT;
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose().translation())>::type VecT;
+    std::vector<Sim3> vCorrectedSwc(nMaxKFid + 1, identity);
+    for (const KFPtr& pKFi : vpKFs) {                                                                    // :1634-1646
+        const double* o = est.data() + 8 * (size_t)index[pKFi->mnId];
+        const Sim3 CorrectedSiw{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
+        vCorrectedSwc[pKFi->mnId] = sim3_inverse(CorrectedSiw);
+        // translation().cast<float>() / s with the double s: Eigen narrows the scalar to the expression's float first
+        // (promote_scalar_arg), so the quotient is float / float
+        const float sf = (float)CorrectedSiw.s;
+        pKFi->SetPose(SE3T(QuatT((float)o[3], (float)o[0], (float)o[1], (float)o[2]), VecT((float)o[4] / sf, (float)o[5] / sf, (float)o[6] / sf)));
+    }
+    for (const auto& pMP : vpMPs) {                                                                      // :1649-1671
+        if (pMP->isBad()) continue;
+        unsigned long nIDr;
+        if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = pMP->mnCorrectedReference;
+        else nIDr = pMP->GetReferenceKeyFrame()->mnId;
+        const auto P = pMP->GetWorldPos();
+        double x, y, z, cx, cy, cz;
+        msorb::sim3opt::sim3_map(vScw[nIDr], (double)P(0), (double)P(1), (double)P(2), x, y, z);         // :1667
+        msorb::sim3opt::sim3_map(vCorrectedSwc[nIDr], x, y, z, cx, cy, cz);
+        typedef typename std::decay<decltype(pMP->GetWorldPos())>::type PosT;
+        pMP->SetWorldPos(PosT((float)cx, (float)cy, (float)cz));
+        pMP->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();                                                                         // :1674
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::OptimizeEssentialGraph, the merge overload (src/Optimizer.cc:1677-1985, LoopClosing.cc:1661), on msorb_essential_graph.
+//
+//   bool ORB_SLAM3::msorb_host::OptimizeEssentialGraph(pCurKF, vpFixedKFs, vpFixedCorrectedKFs, vpNonFixedKFs, vpNonCorrectedMPs)
+//
+// the reference's parameter list, and its effects: under pMap->mMutexMapUpdate, for every KeyFrame of vpNonFixedKFs that is not
+// bad, mTcwBefMerge = GetPose(), mTwcBefMerge = GetPoseInverse() and SetPose with the corrected Sim3 as [R t / s]; every point of
+// vpNonCorrectedMPs that is not bad, with the EraseObservation walk to a reference KeyFrame that is not bad, moved IN FLOAT by
+// Twr * TNonCorrectedwr.inverse() * P (the types' own operators, so inside MS-SLAM they are Sophus') and UpdateNormalAndDepth when
+// its reference KeyFrame has vpBadPose, left alone otherwise (the "another map" arm, :1980-1982).  true = done.
+//
+// The three vertex classes (:1713-1805): vpFixedKFs fixed with _fix_scale = true (the only class that sets it, :1731) and
+// vpGoodPose; vpFixedCorrectedKFs fixed, vScw from mTcwBefMerge, vpGoodPose and vpBadPose; vpNonFixedKFs free unless already in
+// sIdKF, vpBadPose.  The three edge arms (:1816-1929) take the corrected relation when both ends have vpGoodPose, else the
+// non-corrected one when both have vpBadPose, else no edge; Swi is the identity unless vpBadPose[i] (:1821-1826), as it stands.
+//
+// false = NOT handled, nothing touched: a KeyFrame id above GetMaxKFid() (the reference would write past its vectors), a KeyFrame
+// that would be added as a vertex twice, or more free KeyFrames than msorb_essential_graph_capacity().
+template <class KFPtr, class MPPtr>
+bool OptimizeEssentialGraph(KFPtr pCurKF, std::vector<KFPtr>& vpFixedKFs, std::vector<KFPtr>& vpFixedCorrectedKFs,
+                            std::vector<KFPtr>& vpNonFixedKFs, std::vector<MPPtr>& vpNonCorrectedMPs, int device = 0) {
+    using msorb::sim3opt::Sim3;
+    using msorb::sim3opt::sim3_inverse;
+    using msorb::sim3opt::sim3_mul;
+    auto* pMap = pCurKF->GetMap();                                                                       // :1701-1702
+    const unsigned long nMaxKFid = pMap->GetMaxKFid();
+    const Sim3 identity{0, 0, 0, 1, 0, 0, 0, 1};                                                         // g2o::Sim3()
+    std::vector<Sim3> vScw(nMaxKFid + 1, identity), vCorrectedSwc(nMaxKFid + 1, identity);
+    std::vector<char> vpGoodPose(nMaxKFid + 1, 0), vpBadPose(nMaxKFid + 1, 0);
+    std::vector<int> index(nMaxKFid + 1, -1);                                                            // optimizer.vertex(mnId)
+    std::vector<msorb_eg_vertex> vertices;
+    auto sim3_of_pose = [](const auto& Tcw) {   // Tcw.cast<double>() (Sophus normalises the widened quaternion), then Sim3(q, t, 1.0)
+        const auto q = Tcw.unit_quaternion();
+        const auto t = Tcw.translation();
+        const double x = (double)q.x(), y = (double)q.y(), z = (double)q.z(), w = (double)q.w();
+        const double len = std::sqrt(((x * x + y * y) + z * z) + w * w);
+        return Sim3{x / len, y / len, z / len, w / len, (double)t(0), (double)t(1), (double)t(2), 1.0};
+    };
+    bool refused = false;
+    int n_free = 0;
+    auto add_vertex = [&](unsigned long nIDi, const Sim3& S, bool fixed, bool fix_scale) {
+        if (index[nIDi] >= 0) { refused = true; return; }
+        msorb_eg_vertex v;
+        v.q[0] = S.qx; v.q[1] = S.qy; v.q[2] = S.qz; v.q[3] = S.qw; v.t[0] = S.tx; v.t[1] = S.ty; v.t[2] = S.tz; v.s = S.s;
+        v.fixed = fixed ? 1 : 0;
+        v.fix_scale = fix_scale ? 1 : 0;
+        n_free += fixed ? 0 : 1;
+        index[nIDi] = (int)vertices.size();
+        vertices.push_back(v);
+    };
+    for (const auto* list : {&vpFixedKFs, &vpFixedCorrectedKFs, &vpNonFixedKFs})
+        for (const KFPtr& pKFi : *list)
+            if (pKFi->mnId > nMaxKFid) return false;
+    for (const KFPtr& pKFi : vpFixedKFs) {                                                               // :1713-1739
+        if (pKFi->isBad()) continue;
+        const unsigned long nIDi = pKFi->mnId;
+        const Sim3 Siw = sim3_of_pose(pKFi->GetPose());
+        vCorrectedSwc[nIDi] = sim3_inverse(Siw);
+        add_vertex(nIDi, Siw, true, true);
+        vpGoodPose[nIDi] = 1;
+        vpBadPose[nIDi] = 0;
+    }
+    std::set<unsigned long> sIdKF;
+    for (const KFPtr& pKFi : vpFixedCorrectedKFs) {                                                      // :1743-1773
+        if (pKFi->isBad()) continue;
+        const unsigned long nIDi = pKFi->mnId;
+        const Sim3 Siw = sim3_of_pose(pKFi->GetPose());
+        vCorrectedSwc[nIDi] = sim3_inverse(Siw);
+        vScw[nIDi] = sim3_of_pose(pKFi->mTcwBefMerge);
+        add_vertex(nIDi, Siw, true, false);
+        sIdKF.insert(nIDi);
+        vpGoodPose[nIDi] = 1;
+        vpBadPose[nIDi] = 1;
+    }
+    for (const KFPtr& pKFi : vpNonFixedKFs) {                                                            // :1775-1805
+        if (pKFi->isBad()) continue;
+        const unsigned long nIDi = pKFi->mnId;
+        if (sIdKF.count(nIDi)) continue;
+        const Sim3 Siw = sim3_of_pose(pKFi->GetPose());
+        vScw[nIDi] = Siw;
+        add_vertex(nIDi, Siw, false, false);
+        sIdKF.insert(nIDi);
+        vpGoodPose[nIDi] = 0;
+        vpBadPose[nIDi] = 1;
+    }
+    if (refused || n_free > msorb_essential_graph_capacity()) return false;
+    std::vector<KFPtr> vpKFs;                                                                            // :1807-1812
+    vpKFs.insert(vpKFs.end(), vpFixedKFs.begin(), vpFixedKFs.end());
+    vpKFs.insert(vpKFs.end(), vpFixedCorrectedKFs.begin(), vpFixedCorrectedKFs.end());
+    vpKFs.insert(vpKFs.end(), vpNonFixedKFs.begin(), vpNonFixedKFs.end());
+    const std::set<KFPtr> spKFs(vpKFs.begin(), vpKFs.end());
+    std::vector<int> v0, v1;
+    std::vector<double> meas;
+    const int minFeat = 100;                                                                             // :1711
+    for (const KFPtr& pKFi : vpKFs) {                                                                    // :1816-1929
+        const unsigned long nIDi = pKFi->mnId;
+        Sim3 Swi = identity;
+        if (vpBadPose[nIDi]) Swi = sim3_inverse(vScw[nIDi]);                                             // :1825-1826
+        // the relation to KeyFrame j, when there is one: corrected for two good poses, else non-corrected for two bad ones
+        auto relate = [&](unsigned long nIDj) {
+            Sim3 Sjw;
+            if (vpGoodPose[nIDi] && vpGoodPose[nIDj]) Sjw = sim3_inverse(vCorrectedSwc[nIDj]);
+            else if (vpBadPose[nIDi] && vpBadPose[nIDj]) Sjw = vScw[nIDj];
+            else return;
+            if (index[nIDi] < 0 || index[nIDj] < 0) return;   // (a flag is only set with a vertex: cannot happen)
+            const Sim3 Sji = sim3_mul(Sjw, Swi);
+            v0.push_back(index[nIDi]);
+            v1.push_back(index[nIDj]);
+            const double m[8] = {Sji.qx, Sji.qy, Sji.qz, Sji.qw, Sji.tx, Sji.ty, Sji.tz, Sji.s};
+            meas.insert(meas.end(), m, m + 8);
+        };
+        const KFPtr pParentKFi = pKFi->GetParent();
+        if (pParentKFi && spKFs.find(pParentKFi) != spKFs.end()) relate(pParentKFi->mnId);               // :1831-1858
+        const auto sLoopEdges = pKFi->GetLoopEdges();                                                    // :1861-1888
+        for (const KFPtr& pLKF : sLoopEdges)
+            if (spKFs.find(pLKF) != spKFs.end() && pLKF->mnId < pKFi->mnId) relate(pLKF->mnId);
+        const auto vpConnectedKFs = pKFi->GetCovisiblesByWeight(minFeat);                                // :1891-1923
+        for (const KFPtr& pKFn : vpConnectedKFs)
+            if (pKFn && pKFn != pParentKFi && !pKFi->hasChild(pKFn) && !sLoopEdges.count(pKFn) && spKFs.find(pKFn) != spKFs.end())
+                if (!pKFn->isBad() && pKFn->mnId < pKFi->mnId) relate(pKFn->mnId);
+    }
+    std::vector<double> est(8 * vertices.size() + 8);
+    msorb_eg_result r;
+    const int rc = msorb_essential_graph(device, (int)vertices.size(), vertices.data(), (int)v0.size(), v0.data(), v1.data(), meas.data(), 20,
+                                         est.data(), &r, nullptr);                                      // :1932-1933
+    if (rc == MSORB_E_CAPACITY) return false;
+    if (rc != MSORB_OK) fail_call("msorb_essential_graph");
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                                            // :1935
+    for (const KFPtr& pKFi : vpNonFixedKFs) {                                                            // :1938-1953
+        if (pKFi->isBad()) continue;
+        typedef typename std::decay<decltype(pKFi->GetPose())>::type SE3T;
+        typedef typename std::decay<decltype(pKFi->GetPose().unit_quaternion())>::type QuatT;
+        typedef typename std::decay<decltype(pKFi->GetPose().translation())>::type VecT;
+        const double* o = est.data() + 8 * (size_t)index[pKFi->mnId];
+        const double s = o[7];
+        // Sophus::SE3d Tiw(rotation, translation / s): the constructor normalises the quaternion, in double; cast<float>() narrows
+        // (and SE3T's own constructor normalises again, in float, inside MS-SLAM)
+        const double len = std::sqrt(((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]) + o[3] * o[3]);
+        const SE3T Tiw(QuatT((float)(o[3] / len), (float)(o[0] / len), (float)(o[1] / len), (float)(o[2] / len)),
+                       VecT((float)(o[4] / s), (float)(o[5] / s), (float)(o[6] / s)));
+        pKFi->mTcwBefMerge = pKFi->GetPose();
+        pKFi->mTwcBefMerge = pKFi->GetPoseInverse();
+        pKFi->SetPose(Tiw);
+    }
+    for (const MPPtr& pMPi : vpNonCorrectedMPs) {                                                        // :1956-1983
+        if (pMPi->isBad()) continue;
+        KFPtr pRefKF = pMPi->GetReferenceKeyFrame();
+        while (pRefKF->isBad()) {                                                                        // :1961-1970, as it stands
+            if (!pRefKF) break;
+            pMPi->EraseObservation(pRefKF);
+            pRefKF = pMPi->GetReferenceKeyFrame();
+        }
+        if (pRefKF->mnId <= nMaxKFid && vpBadPose[pRefKF->mnId]) {
+            const auto TNonCorrectedwr = pRefKF->mTwcBefMerge;
+            const auto Twr = pRefKF->GetPoseInverse();
+            const auto eigCorrectedP3Dw = Twr * TNonCorrectedwr.inverse() * pMPi->GetWorldPos();         // :1976, in float
+            pMPi->SetWorldPos(eigCorrectedP3Dw);
+            pMPi->UpdateNormalAndDepth();
+        }   // else: "MapPoint has a reference KF from another map", nothing done (:1980-1982)
+    }
+    return true;
 }
 
 }  // namespace msorb_host

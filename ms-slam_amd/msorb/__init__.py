@@ -2332,3 +2332,64 @@ def two_view_reconstruct(keys1, keys2, matches12, sets, cam, sigma=1.0, h_ratio=
     if hypotheses:
         out.update(scores=scores[:, :H], counts=counts[:, :H], masks=masks[:, :H, :n].astype(bool))
     return (out, ms.value) if timing else out
+
+
+# ---- Optimizer::OptimizeEssentialGraph on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_essential_graph_capacity", "msorb_essential_graph", "msorb_essential_graph_stage_ms")
+
+EG_VERTEX_DTYPE = np.dtype([("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8"), ("fixed", "<i4"), ("fix_scale", "<i4")])   # msorb_eg_vertex
+EG_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("rejected_trials", "<i4"),
+                            ("solver_failures", "<i4"), ("stop", "<i4"), ("chi2_initial", "<f8"), ("chi2_final", "<f8"),
+                            ("lambda_final", "<f8")])                                                                   # msorb_eg_result
+assert EG_VERTEX_DTYPE.itemsize == 72 and EG_RESULT_DTYPE.itemsize == 48
+
+
+def _eg_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_essential_graph_capacity.argtypes = []
+    L.msorb_essential_graph.argtypes = [ci, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp]
+    L.msorb_essential_graph_stage_ms.argtypes = [vp]
+    return L
+
+
+def essential_graph_capacity():
+    """the largest number of free vertices (with an active edge) msorb_essential_graph accepts"""
+    return _eg_lib().msorb_essential_graph_capacity()
+
+
+def eg_vertices(q, t, s, fixed, fix_scale):
+    """msorb_eg_vertex records: q [N, 4] (x, y, z, w), t [N, 3], s [N], fixed [N], fix_scale [N] (or one value for all)"""
+    v = np.zeros(len(s), EG_VERTEX_DTYPE)
+    v["q"], v["t"], v["s"], v["fixed"], v["fix_scale"] = q, t, s, fixed, fix_scale
+    return v
+
+
+def essential_graph(vertices, edge_v0, edge_v1, measurements, iterations=20, device=0, timing=False, estimates_out=None):
+    """msorb_essential_graph: Optimizer::OptimizeEssentialGraph after its gathering loops, on the device.  vertices:
+    EG_VERTEX_DTYPE [N]; edge e joins edge_v0[e] -> edge_v1[e] with measurements[e] = (q[4], t[3], s) of Sjw * Swi.
+    -> dict(result: EG_RESULT_DTYPE record, estimates float64 [N, 8]) and, with timing, elapsed_ms (device time).
+    estimates_out: an [N, 8] float64 array to be written instead of a fresh one (it keeps its contents when the call is refused)."""
+    L = _eg_lib()
+    vt = _c(vertices, EG_VERTEX_DTYPE).reshape(-1)
+    e0, e1 = _c(edge_v0, np.int32).reshape(-1), _c(edge_v1, np.int32).reshape(-1)
+    me = _c(measurements, np.float64).reshape(-1, 8)
+    if [len(e1), len(me)] != [len(e0)] * 2:
+        raise ValueError("the edge arrays do not have one entry per edge")
+    out = np.zeros((max(len(vt), 1), 8), np.float64) if estimates_out is None else estimates_out
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.size >= 8 * len(vt)
+    res = np.zeros(1, EG_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_essential_graph(device, len(vt), _np_ptr(vt), len(e0), _np_ptr(e0), _np_ptr(e1), _np_ptr(me), int(iterations),
+                                   _np_ptr(out), _np_ptr(res), C.addressof(ms)), "msorb_essential_graph")
+    r = dict(result=res[0], estimates=out[:len(vt)])
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r
+
+
+def essential_graph_stage_ms():
+    """dict(linearise, assemble, solve, trial) in device ms of this thread's last essential_graph call (MSORB_LOCAL_BA_STAGES=1)"""
+    ms = np.zeros(4, np.float32)
+    _check(_eg_lib().msorb_essential_graph_stage_ms(_np_ptr(ms)), "msorb_essential_graph_stage_ms")
+    return dict(zip(("linearise", "assemble", "solve", "trial"), (float(v) for v in ms)))

@@ -1,0 +1,183 @@
+// ms-slam_amd/csrc/essential_graph_device.h (the text the kernels compile) and essential_graph_plan.h on the host, serially: every sum
+// walks its index list in ascending position, the dense system is factored column by column (L D L^T, no pivoting, one reciprocal per
+// pivot: what ldlt_blocked.h is bit-equal to).
+//
+//   essential_graph_main in.bin out.bin
+// The two files are tests/essential_graph_cases.py's write_scenes / read_results.
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../ms-slam_amd/csrc/essential_graph_device.h"
+#include "../ms-slam_amd/csrc/essential_graph_plan.h"
+
+using namespace msorb::eg;
+
+namespace {
+
+struct HostBackend {
+    const msorb::EssentialGraphPlan& plan;
+    const int *v0, *v1, *fix_scale;
+    const double* meas;
+    std::vector<double> state[2], lin, chi, Hd, Hp, b, S, x;
+    Sim3 tab[kTable];
+    int current = 0;
+
+    static Sim3 load(const double* p) { return Sim3{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]}; }
+    double cost() const {
+        double c = 0;
+        for (int a = 0; a < plan.Ea; a++) c += chi[a];
+        return c;
+    }
+    int linearise(int cur, double& out) {
+        const size_t Ea = (size_t)plan.Ea;
+        const std::vector<double>& st = state[cur];
+        for (int a = 0; a < plan.Ea; a++) {
+            const int e = plan.active_edge[a], i0 = v0[e], i1 = v1[e];
+            const bool free0 = plan.free_of_vertex[i0] >= 0, free1 = plan.free_of_vertex[i1] >= 0;
+            const Sim3 C = load(meas + 8 * (size_t)e), s0 = load(&st[8 * (size_t)i0]), s1 = load(&st[8 * (size_t)i1]);
+            double err[kErrors * 7] = {0}, J[98] = {0};
+            for (int w = 0; w < kErrors; w++)
+                if (w == 0 || (w < 15 ? free0 : free1)) edge_error_variant(tab, C, s0, s1, fix_scale[i0] != 0, fix_scale[i1] != 0, w, err + 7 * w);
+            chi[a] = edge_chi2(err);
+            for (int q = 0; q < 98; q++)
+                if (q / 49 ? free1 : free0) J[q] = jacobian_entry(err, q / 49, (q % 49) / 7, q % 7);
+            for (int q = 0; q < kPlanes; q++) {
+                const bool uses0 = q < kHbb || (q >= kHab && q < kBb), uses1 = (q >= kHbb && q < kBa) || q >= kBb;
+                if ((uses0 && !free0) || (uses1 && !free1)) continue;
+                lin[(size_t)q * Ea + a] = quadratic_term(J, err, q);
+            }
+        }
+        for (int i = 0; i < plan.Kf; i++) {
+            double s[35] = {0};
+            for (int m = plan.inc_begin[i]; m < plan.inc_begin[i + 1]; m++) {
+                const int a = plan.inc_entry[m] >> 1, side = plan.inc_entry[m] & 1;
+                for (int q = 0; q < 28; q++) s[q] += lin[(size_t)((side ? kHbb : kHaa) + q) * Ea + a];
+                for (int q = 0; q < 7; q++) s[28 + q] += lin[(size_t)((side ? kBb : kBa) + q) * Ea + a];
+            }
+            for (int q = 0; q < 28; q++) Hd[28 * (size_t)i + q] = s[q];
+            for (int q = 0; q < 7; q++) b[7 * (size_t)i + q] = s[28 + q];
+        }
+        for (size_t p = 0; p < plan.pair_i.size(); p++) {
+            double t[49] = {0};
+            for (int m = plan.pair_begin[p]; m < plan.pair_begin[p + 1]; m++) {
+                const int a = plan.pair_entry[m] >> 1, flip = plan.pair_entry[m] & 1;
+                for (int r = 0; r < 7; r++)
+                    for (int c = 0; c < 7; c++) t[7 * r + c] += lin[(size_t)(kHab + (flip ? 7 * c + r : 7 * r + c)) * Ea + a];
+            }
+            for (int q = 0; q < 49; q++) Hp[49 * p + q] = t[q];
+        }
+        out = cost();
+        return 0;
+    }
+    bool solve(int n) {   // column by column; false on a pivot !(d > 0), x untouched
+        std::vector<double> v((size_t)n), rd((size_t)n), y(b);
+        for (int j = 0; j < n; j++) {
+            const double d = S[(size_t)j * n + j];
+            if (!(d > 0)) return false;
+            const double r = 1.0 / d;
+            rd[j] = r;
+            for (int i = j + 1; i < n; i++) { v[i] = S[(size_t)i * n + j]; S[(size_t)i * n + j] = v[i] * r; }
+            for (int i = j + 1; i < n; i++) {
+                const double l = S[(size_t)i * n + j];
+                if (l == 0.0) continue;   // (a zero multiplier changes no bit of a finite row)
+                for (int k = j + 1; k <= i; k++) S[(size_t)i * n + k] -= l * v[k];
+            }
+        }
+        for (int m = 0; m < n; m++)
+            for (int i = m + 1; i < n; i++) y[i] -= S[(size_t)i * n + m] * y[m];
+        for (int i = 0; i < n; i++) y[i] *= rd[i];
+        for (int m = n - 1; m >= 0; m--)
+            for (int i = 0; i < m; i++) y[i] -= S[(size_t)m * n + i] * y[m];
+        x = y;
+        return true;
+    }
+    int trial(int cur, double lambda, double& out, double& scale, int& solved) {
+        const int n = 7 * plan.Kf;
+        std::fill(S.begin(), S.end(), 0.0);
+        for (int i = 0; i < plan.Kf; i++)
+            for (int r = 0; r < 7; r++)
+                for (int c = 0; c <= r; c++) S[(size_t)(7 * i + r) * n + 7 * i + c] = Hd[28 * (size_t)i + upper7(c, r)] + (r == c ? lambda : 0.0);
+        for (size_t p = 0; p < plan.pair_i.size(); p++)
+            for (int r = 0; r < 7; r++)
+                for (int c = 0; c < 7; c++) S[(size_t)(7 * plan.pair_j[p] + c) * n + 7 * plan.pair_i[p] + r] = Hp[49 * p + 7 * r + c];
+        solved = solve(n) ? 1 : 0;
+        state[cur ^ 1] = state[cur];
+        scale = 0;
+        for (int i = 0; i < plan.Kf; i++) {
+            const int k = plan.vertex_of_free[i];
+            const Sim3 N = msorb::sim3opt::sim3_oplus(load(&state[cur][8 * (size_t)k]), &x[7 * (size_t)i], fix_scale[k] != 0);
+            double sc = 0;
+            for (int r = 0; r < 7; r++) sc += x[7 * (size_t)i + r] * (lambda * x[7 * (size_t)i + r] + b[7 * (size_t)i + r]);
+            scale += sc;
+            double* o = &state[cur ^ 1][8 * (size_t)k];
+            o[0] = N.qx; o[1] = N.qy; o[2] = N.qz; o[3] = N.qw; o[4] = N.tx; o[5] = N.ty; o[6] = N.tz; o[7] = N.s;
+        }
+        for (int a = 0; a < plan.Ea; a++) {
+            const int e = plan.active_edge[a];
+            double err[7];
+            edge_error(load(meas + 8 * (size_t)e), load(&state[cur ^ 1][8 * (size_t)v0[e]]), load(&state[cur ^ 1][8 * (size_t)v1[e]]), err);
+            chi[a] = edge_chi2(err);
+        }
+        out = cost();
+        return 0;
+    }
+};
+
+bool read_exact(FILE* f, void* p, size_t bytes) { return bytes == 0 || std::fread(p, 1, bytes, f) == bytes; }
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc < 3) return 2;
+    FILE* in = std::fopen(argv[1], "rb");
+    FILE* out = std::fopen(argv[2], "wb");
+    if (!in || !out) return 2;
+    int n_scenes = 0;
+    if (!read_exact(in, &n_scenes, 4)) return 2;
+    for (int sidx = 0; sidx < n_scenes; sidx++) {
+        int dims[3];
+        if (!read_exact(in, dims, 12)) return 2;
+        const int N = dims[0], E = dims[1], iterations = dims[2];
+        std::vector<double> est((size_t)N * 8), meas((size_t)E * 8);
+        std::vector<int> fixed((size_t)N), fs((size_t)N), v0((size_t)E), v1((size_t)E);
+        if (!read_exact(in, est.data(), est.size() * 8) || !read_exact(in, fixed.data(), (size_t)N * 4) || !read_exact(in, fs.data(), (size_t)N * 4) ||
+            !read_exact(in, v0.data(), (size_t)E * 4) || !read_exact(in, v1.data(), (size_t)E * 4) || !read_exact(in, meas.data(), meas.size() * 8))
+            return 2;
+        msorb::EssentialGraphPlan plan;
+        if (msorb::build_essential_graph_plan(N, fixed.data(), E, v0.data(), v1.data(), plan) != msorb::kEgPlanOk) return 3;
+        const size_t n = 7 * (size_t)plan.Kf, Ea = (size_t)plan.Ea;
+        HostBackend be{plan, v0.data(), v1.data(), fs.data(), meas.data()};
+        be.state[0] = est;
+        be.state[1] = est;
+        be.lin.assign(kPlanes * Ea, 0.0);
+        be.chi.assign(Ea, 0.0);
+        be.Hd.assign(28 * (size_t)plan.Kf, 0.0);
+        be.Hp.assign(49 * plan.pair_i.size(), 0.0);
+        be.b.assign(n, 0.0);
+        be.S.assign(n * n, 0.0);
+        be.x.assign(n, 0.0);
+        for (int k = 0; k < kTable; k++) be.tab[k] = table_entry(k);
+        Outcome o;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (levenberg(be, iterations, plan.Ea > 0, o)) return 4;
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        const int counts[6] = {0, o.iterations, o.trials, o.rejected, o.solver_failures, o.stop};
+        const double d[3] = {o.chi2_initial, o.chi2_final, o.lambda};
+        std::fwrite(counts, 4, 6, out);
+        std::fwrite(d, 8, 3, out);
+        std::vector<double> result = est;   // a vertex outside the system repeats its input
+        for (int i = 0; i < plan.Kf; i++) {
+            const int k = plan.vertex_of_free[i];
+            std::memcpy(&result[8 * (size_t)k], &be.state[be.current][8 * (size_t)k], 64);
+        }
+        std::fwrite(result.data(), 8, result.size(), out);
+        std::printf("scene %d: N %d free %d edges %d active %d pairs %zu iterations %d trials %d rejected %d stop %d chi2 %.6e -> %.6e ms %.3f\n", sidx, N,
+                    plan.Kf, E, plan.Ea, plan.pair_i.size(), o.iterations, o.trials, o.rejected, o.stop, o.chi2_initial, o.chi2_final, ms);
+    }
+    std::fclose(in);
+    std::fclose(out);
+    return 0;
+}
