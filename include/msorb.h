@@ -1346,6 +1346,42 @@ int msorb_essential_graph(int device, int n_vertices, const msorb_eg_vertex* ver
  * MSORB_LOCAL_BA_STAGES=1 in the environment before the library is loaded (MSORB_E_ARG otherwise, zeros). */
 int msorb_essential_graph_stage_ms(float ms[4]);
 
+/* Optimizer::OptimizeEssentialGraph4DoF (src/Optimizer.cc:5174-5458: what LoopClosing::CorrectLoop runs on an inertial map) after
+ * the gathering loops, on the device: g2o's pose graph of VertexPose4DoF (yaw about the world's z and a world-frame translation,
+ * through ImuCamPose::UpdateW) and Edge4DoF (LogSO3 of the rotation residual, the translation residual) with the information
+ * diag(1e3, 1e3, 1, 1, 1, 1), no kernel, the edge's NUMERIC Jacobian (central differences of 1e-9 through oplus) and Levenberg
+ * from computeLambdaInit = 1e-5 max |H(j,j)|, in double.  Appended to ABI 6002: MSORB_ABI_VERSION stays 6002.
+ * vertices [n_vertices], 3x3 matrices row major: the camera pose Rcw, tcw and the body pose Rwb, twb the estimate starts from
+ * (inputs of their own: ImuCamPose(pKF) does not derive one from the other), the constants Rcb, tcb, and fixed (setFixed).
+ * Edge e joins vertices edge_v0[e] -> edge_v1[e] with measurement dRij[9], dtij[3] (12 doubles).  Several edges on one pair are
+ * legal.  g2o's active set holds: an edge with two fixed ends enters neither the cost nor H; a free vertex without an active edge
+ * keeps its pose bit for bit.  The 4 Kf x 4 Kf system (Kf: free vertices with an active edge, in the caller's order) is solved
+ * DENSELY by the blocked L D L^T of msorb_ldlt_solve, unpivoted, where the reference runs a sparse Cholesky.
+ * poses_out [12 per vertex]: Rcw[9], tcw[3].
+ * Errors: MSORB_E_ARG for an edge that names a vertex out of range or has v0 == v1, a null required array, a negative count.
+ * More than msorb_essential_graph4_capacity() free vertices in the system, or no room on the device for it: MSORB_E_CAPACITY,
+ * nothing launched, no output written.  No active edge: zero iterations and the poses as they came.  Two calls on the same
+ * input return the same bits.  Re-entrant like msorb_local_ba.  *elapsed_ms (may be NULL): device time. */
+typedef struct msorb_eg4_vertex {
+    double Rcw[9], tcw[3], Rwb[9], twb[3], Rcb[9], tcb[3];
+    int32_t fixed, reserved;
+} msorb_eg4_vertex;
+typedef struct msorb_eg4_result {
+    int32_t status;            /* 0 */
+    int32_t iterations, trials, rejected_trials;
+    int32_t solver_failures;   /* trials whose factorisation met a pivot that was not positive */
+    int32_t stop;              /* 0: every iteration ran; 1: Terminate (ten trials, or rho == 0); 2: the fork's _nBad >= 3 */
+    double chi2_initial, chi2_final, lambda_final;
+    double lambda_initial;     /* computeLambdaInit at the first linearisation */
+} msorb_eg4_result;
+int msorb_essential_graph4_capacity(void);             /* free vertices: 1792 (the system is 7168^2 doubles = 411 MB) */
+int msorb_essential_graph4(int device, int n_vertices, const msorb_eg4_vertex* vertices, int n_edges, const int* edge_v0,
+                           const int* edge_v1, const double* measurements, int iterations, double* poses_out,
+                           msorb_eg4_result* result, float* elapsed_ms);
+/* Device ms of the calling thread's last msorb_essential_graph4 call: linearise, assemble, solve, trial.  Needs
+ * MSORB_LOCAL_BA_STAGES=1 in the environment before the library is loaded (MSORB_E_ARG otherwise, zeros). */
+int msorb_essential_graph4_stage_ms(float ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,15 +183,17 @@ SE3_HD int upper7(int r, int c) { return r * 7 - (r * (r - 1)) / 2 + (c - r); }
 struct Outcome {
     int iterations, trials, rejected, solver_failures, stop;   // stop: 0 all iterations ran, 1 Terminate (:151-155), 2 _nBad (:164-167)
     double chi2_initial, chi2_final, lambda;
+    double lambda_initial;   // what the first linearisation started from
 };
 
 // optimizer.optimize(max_it) (sparse_optimizer.cpp:376-389 with levenberg.cpp:61-170).  The backend keeps two copies of the state;
 // push / pop is which copy is current.
 //   be.linearise(cur, chi)                       computeActiveErrors + activeRobustChi2 + buildSystem at copy `cur`
 //   be.trial(cur, lambda, chi, scale, solved)    setLambda, solve, update into copy cur ^ 1, the cost there, computeScale
-// Both return 0 or an error code, which ends the loop and is returned.
-template <typename Backend>
-inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o) {
+// Both return 0 or an error code, which ends the loop and is returned.  lambda_init(be) is computeLambdaInit (:172-186), asked once,
+// after the first linearisation.
+template <typename Backend, typename LambdaInit>
+inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o, LambdaInit lambda_init) {
     o = Outcome();
     int cur = 0, n_bad = 0;
     double lambda = 0, ni = 2;
@@ -201,9 +203,9 @@ inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o) {
         if (int rc = be.linearise(cur, current)) return rc;
         double temp = current;
         const double ini = current;
-        if (it == 0) {                                     // :93-97; computeLambdaInit returns the user value (:174-175)
+        if (it == 0) {                                     // :93-97
             o.chi2_initial = current;
-            lambda = 1e-16;                                // solver->setUserLambdaInit(1e-16) (Optimizer.cc:1423, :1698)
+            lambda = o.lambda_initial = lambda_init(be);
             ni = 2;
             n_bad = 0;
         }
@@ -244,6 +246,12 @@ inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o) {
     o.lambda = lambda;
     be.current = cur;
     return 0;
+}
+
+// the 7-DoF form: computeLambdaInit returns the user value (:174-175), solver->setUserLambdaInit(1e-16) (Optimizer.cc:1423, :1698)
+template <typename Backend>
+inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o) {
+    return levenberg(be, max_it, any_edge, o, [](Backend&) { return 1e-16; });
 }
 
 }  // namespace eg

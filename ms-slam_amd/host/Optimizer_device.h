@@ -970,6 +970,218 @@ bool OptimizeEssentialGraph(KFPtr pCurKF, std::vector<KFPtr>& vpFixedKFs, std::v
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::OptimizeEssentialGraph4DoF (src/Optimizer.cc:5174-5458, LoopClosing.cc:1130-1134: the arm an inertial map with an
+// initialised IMU takes) on msorb_essential_graph4.
+//
+//   bool ORB_SLAM3::msorb_host::OptimizeEssentialGraph4DoF(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections)
+//
+// the reference's parameter list, and its effects: under pMap->mMutexMapUpdate SetPose of every KeyFrame with the optimised
+// Rcw, tcw (through g2o::Sim3(Ri, ti, 1.), i.e. Eigen's matrix-to-quaternion conversion, and Sophus::SE3d, whose constructor
+// normalises the quaternion in double, narrowed), every point that is not bad moved by correctedSwr.map(Srw.map(P)) through its
+// reference KeyFrame and UpdateNormalAndDepth, then IncreaseChangeIndex.  true = done.
+//
+// false = NOT handled, nothing touched, the caller runs Optimizer::OptimizeEssentialGraph4DoF: a KeyFrame of GetAllKeyFrames() that
+// is bad (the reference would dereference its missing vertex at :5425-5426), a KeyFrame id above GetMaxKFid() (the reference would
+// read past its vectors), or more free KeyFrames than msorb_essential_graph4_capacity() (or no room on the device for their
+// system).  An edge to a KeyFrame that is no vertex (a loop edge or mPrevKF outside GetAllKeyFrames()) is not added, as g2o's
+// addEdge refuses it, and the rest is optimised.
+//
+// What runs where.  The vertex loop with both ImuCamPose constructors (G2oTypes.cc:25-71 for a KeyFrame outside CorrectedSim3:
+// four floats of the KeyFrame widened, the camera pose NOT derived from the body pose; :121-146 from Swc's rotation matrix and
+// translation, which drops the Sim3's scale), the look-ups, the weight gate, the edge arms (the spanning-tree arm is dead in this
+// fork: pParentKF is NULL at :5297) and the measurements Siw * Sjw^-1 in Sim3 arithmetic, of which the rotation matrix and the
+// translation go into the edge, stay host code; optimize(20) is the device's.
+inline void EgRotationOfQuaternion(const msorb::sim3opt::Sim3& S, double* R) {   // Eigen's Quaternion::toRotationMatrix, row major
+    const double tx = 2 * S.qx, ty = 2 * S.qy, tz = 2 * S.qz;
+    const double twx = tx * S.qw, twy = ty * S.qw, twz = tz * S.qw, txx = tx * S.qx, txy = ty * S.qx, txz = tz * S.qx;
+    const double tyy = ty * S.qy, tyz = tz * S.qy, tzz = tz * S.qz;
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+}
+inline void EgQuaternionOfRotation(const double* m, double* q) {   // Eigen's Quaternion(Matrix3) with its branches -> x, y, z, w
+    double t = (m[0] + m[4]) + m[8];
+    if (t > 0) {
+        t = std::sqrt(t + 1.0);
+        q[3] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (m[7] - m[5]) * t; q[1] = (m[2] - m[6]) * t; q[2] = (m[3] - m[1]) * t;
+    } else {
+        int i = 0;
+        if (m[4] > m[0]) i = 1;
+        if (m[8] > m[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(((m[4 * i] - m[4 * j]) - m[4 * k]) + 1.0);
+        q[i] = 0.5 * t;
+        t = 0.5 / t;
+        q[3] = (m[3 * k + j] - m[3 * j + k]) * t;
+        q[j] = (m[3 * j + i] + m[3 * i + j]) * t;
+        q[k] = (m[3 * k + i] + m[3 * i + k]) * t;
+    }
+}
+
+template <class MapT, class KFPtr, class PoseMapT, class ConnectionsT>
+bool OptimizeEssentialGraph4DoF(MapT* pMap, KFPtr pLoopKF, KFPtr pCurKF, const PoseMapT& NonCorrectedSim3, const PoseMapT& CorrectedSim3,
+                                const ConnectionsT& LoopConnections, int device = 0) {
+    using msorb::sim3opt::Sim3;
+    using msorb::sim3opt::sim3_inverse;
+    using msorb::sim3opt::sim3_mul;
+    const auto vpKFs = pMap->GetAllKeyFrames();                                                          // :5191-5192
+    const auto vpMPs = pMap->GetAllMapPoints();
+    const unsigned long nMaxKFid = pMap->GetMaxKFid();
+    const Sim3 identity{0, 0, 0, 1, 0, 0, 0, 1};                                                         // g2o::Sim3(): what the vectors of :5196-5197 hold by default
+    std::vector<Sim3> vScw(nMaxKFid + 1, identity);
+    std::vector<int> index(nMaxKFid + 1, -1);                                                            // optimizer.vertex(mnId)
+    std::vector<msorb_eg4_vertex> vertices;
+    const int minFeat = 100;                                                                             // :5201
+    int n_free = 0;
+    auto mul3 = [](const double* A, const double* B, double* C) {
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) C[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
+    };
+    for (const auto& pKF : vpKFs) {                                                                      // :5203-5236
+        if (pKF->isBad()) return false;
+        const unsigned long nIDi = pKF->mnId;
+        if (nIDi > nMaxKFid) return false;
+        msorb_eg4_vertex v;
+        const auto Rcb = pKF->mImuCalib.mTcb.rotationMatrix();                                           // G2oTypes.cc:49-50, :132-133
+        const auto tcb = pKF->mImuCalib.mTcb.translation();
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) v.Rcb[3 * r + c] = (double)Rcb(r, c);
+            v.tcb[r] = (double)tcb(r);
+        }
+        const auto it = CorrectedSim3.find(pKF);
+        if (it != CorrectedSim3.end()) {                                                                 // :5214-5219
+            vScw[nIDi] = EgSim3(it->second);
+            const Sim3 Swc = sim3_inverse(vScw[nIDi]);
+            double Rwc[9];
+            EgRotationOfQuaternion(Swc, Rwc);
+            const double twc[3] = {Swc.tx, Swc.ty, Swc.tz};
+            for (int r = 0; r < 3; r++)                                                                  // G2oTypes.cc:136: twb = Rwc tcb + twc
+                v.twb[r] = ((Rwc[3 * r] * v.tcb[0] + Rwc[3 * r + 1] * v.tcb[1]) + Rwc[3 * r + 2] * v.tcb[2]) + twc[r];
+            mul3(Rwc, v.Rcb, v.Rwb);                                                                     // :137
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) v.Rcw[3 * r + c] = Rwc[3 * c + r];                           // :138
+            for (int r = 0; r < 3; r++)                                                                  // :139: tcw = -Rcw twc
+                v.tcw[r] = -((v.Rcw[3 * r] * twc[0] + v.Rcw[3 * r + 1] * twc[1]) + v.Rcw[3 * r + 2] * twc[2]);
+        } else {                                                                                         // :5221-5225
+            const auto Tcw = pKF->GetPose();
+            const auto q = Tcw.unit_quaternion();
+            const auto t = Tcw.translation();
+            const double x = (double)q.x(), y = (double)q.y(), z = (double)q.z(), w = (double)q.w();
+            const double len = std::sqrt(((x * x + y * y) + z * z) + w * w);
+            vScw[nIDi] = Sim3{x / len, y / len, z / len, w / len, (double)t(0), (double)t(1), (double)t(2), 1.0};
+            const auto Rwb = pKF->GetImuRotation();                                                      // G2oTypes.cc:28-29, :47-48
+            const auto twb = pKF->GetImuPosition();
+            const auto Rcw = pKF->GetRotation();
+            const auto tcw = pKF->GetTranslation();
+            for (int r = 0; r < 3; r++) {
+                for (int c = 0; c < 3; c++) { v.Rwb[3 * r + c] = (double)Rwb(r, c); v.Rcw[3 * r + c] = (double)Rcw(r, c); }
+                v.twb[r] = (double)twb(r);
+                v.tcw[r] = (double)tcw(r);
+            }
+        }
+        v.fixed = pKF == pLoopKF ? 1 : 0;                                                                // :5228-5229
+        v.reserved = 0;
+        n_free += v.fixed ? 0 : 1;
+        index[nIDi] = (int)vertices.size();
+        vertices.push_back(v);
+    }
+    if (n_free > msorb_essential_graph4_capacity()) return false;
+    std::vector<int> v0, v1;
+    std::vector<double> meas;
+    bool missing = false;
+    auto add_edge = [&](unsigned long nIDi, unsigned long nIDj, const Sim3& Sij) {   // vertex 0 = i, vertex 1 = j
+        if (nIDi > nMaxKFid || nIDj > nMaxKFid) { missing = true; return; }   // (the reference would read past its vectors)
+        if (index[nIDi] < 0 || index[nIDj] < 0) return;   // optimizer.vertex() is null: g2o's addEdge refuses the edge, the rest goes on
+        v0.push_back(index[nIDi]);
+        v1.push_back(index[nIDj]);
+        double m[12];                                                          // Tij: the rotation matrix and the translation; the scale is dropped
+        EgRotationOfQuaternion(Sij, m);
+        m[9] = Sij.tx; m[10] = Sij.ty; m[11] = Sij.tz;
+        meas.insert(meas.end(), m, m + 12);
+    };
+    auto inverse_non_corrected = [&](const KFPtr& pKFx) -> Sim3 {              // "if in NonCorrectedSim3, that; else vScw", inverted
+        const auto itx = NonCorrectedSim3.find(pKFx);
+        if (itx != NonCorrectedSim3.end()) return sim3_inverse(EgSim3(itx->second));
+        if (pKFx->mnId > nMaxKFid) { missing = true; return Sim3{0, 0, 0, 1, 0, 0, 0, 1}; }
+        return sim3_inverse(vScw[pKFx->mnId]);
+    };
+    std::set<std::pair<unsigned long, unsigned long>> sInsertedEdges;
+    const float ratio = 0.3;                                                                             // :5246
+    for (const auto& mit : LoopConnections) {                                                            // :5248-5278
+        const KFPtr& pKF = mit.first;
+        const unsigned long nIDi = pKF->mnId;
+        if (nIDi > nMaxKFid) return false;
+        const Sim3 Siw = vScw[nIDi];
+        for (const KFPtr& pKFj : mit.second) {
+            const unsigned long nIDj = pKFj->mnId;
+            if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(pKFj) < minFeat * ratio) continue;   // :5258
+            if (nIDj > nMaxKFid) return false;
+            add_edge(nIDi, nIDj, sim3_mul(Siw, sim3_inverse(vScw[nIDj])));                               // :5261-5262
+            sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+        }
+    }
+    for (const KFPtr& pKF : vpKFs) {                                                                     // :5281-5411
+        const unsigned long nIDi = pKF->mnId;
+        Sim3 Siw;                                                                                        // :5286-5294
+        const auto iti = NonCorrectedSim3.find(pKF);
+        if (iti != NonCorrectedSim3.end()) Siw = EgSim3(iti->second);
+        else Siw = vScw[nIDi];
+        const KFPtr pParentKF;                                                                           // :5297: NULL, the spanning-tree arm (:5298-5321) is dead
+        const KFPtr prevKF = pKF->mPrevKF;                                                               // :5324-5348
+        if (prevKF) add_edge(nIDi, prevKF->mnId, sim3_mul(Siw, inverse_non_corrected(prevKF)));
+        const auto sLoopEdges = pKF->GetLoopEdges();                                                     // :5351-5377
+        for (const KFPtr& pLKF : sLoopEdges)
+            if (pLKF->mnId < pKF->mnId) add_edge(nIDi, pLKF->mnId, sim3_mul(Siw, inverse_non_corrected(pLKF)));
+        const auto vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);                                 // :5380-5410
+        for (const KFPtr& pKFn : vpConnectedKFs) {
+            if (pKFn && pKFn != pParentKF && pKFn != prevKF && pKFn != pKF->mNextKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                    if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                    add_edge(nIDi, pKFn->mnId, sim3_mul(Siw, inverse_non_corrected(pKFn)));
+                }
+            }
+        }
+    }
+    if (missing) return false;
+    std::vector<double> poses(12 * vertices.size());
+    msorb_eg4_result r;
+    const int rc = msorb_essential_graph4(device, (int)vertices.size(), vertices.data(), (int)v0.size(), v0.data(), v1.data(), meas.data(),
+                                          20, poses.data(), &r, nullptr);                               // :5413-5415
+    if (rc == MSORB_E_CAPACITY) return false;
+    if (rc != MSORB_OK) fail_call("msorb_essential_graph4");
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                                            // :5417
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose().unit_quaternion())>::type QuatT;
+    typedef typename std::decay<decltype(vpKFs[0]->GetPose().translation())>::type VecT;
+    std::vector<Sim3> vCorrectedSwc(nMaxKFid + 1, identity);
+    for (const KFPtr& pKFi : vpKFs) {                                                                    // :5420-5434
+        const double* o = poses.data() + 12 * (size_t)index[pKFi->mnId];
+        double q[4];
+        EgQuaternionOfRotation(o, q);                                                                    // g2o::Sim3(Ri, ti, 1.) (:5429)
+        const Sim3 CorrectedSiw{q[0], q[1], q[2], q[3], o[9], o[10], o[11], 1.0};
+        vCorrectedSwc[pKFi->mnId] = sim3_inverse(CorrectedSiw);
+        const double len = std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]);         // Sophus::SE3d(q, t) normalises (:5432)
+        pKFi->SetPose(SE3T(QuatT((float)(q[3] / len), (float)(q[0] / len), (float)(q[1] / len), (float)(q[2] / len)),
+                           VecT((float)o[9], (float)o[10], (float)o[11])));
+    }
+    for (const auto& pMP : vpMPs) {                                                                      // :5437-5456
+        if (pMP->isBad()) continue;
+        const unsigned long nIDr = pMP->GetReferenceKeyFrame()->mnId;
+        const auto P = pMP->GetWorldPos();
+        double x, y, z, cx, cy, cz;
+        msorb::sim3opt::sim3_map(vScw[nIDr], (double)P(0), (double)P(1), (double)P(2), x, y, z);         // :5452
+        msorb::sim3opt::sim3_map(vCorrectedSwc[nIDr], x, y, z, cx, cy, cz);
+        typedef typename std::decay<decltype(pMP->GetWorldPos())>::type PosT;
+        pMP->SetWorldPos(PosT((float)cx, (float)cy, (float)cz));
+        pMP->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();                                                                         // :5457
+    return true;
+}
+
 }  // namespace msorb_host
 }  // namespace ORB_SLAM3
 

@@ -2393,3 +2393,66 @@ def essential_graph_stage_ms():
     ms = np.zeros(4, np.float32)
     _check(_eg_lib().msorb_essential_graph_stage_ms(_np_ptr(ms)), "msorb_essential_graph_stage_ms")
     return dict(zip(("linearise", "assemble", "solve", "trial"), (float(v) for v in ms)))
+
+
+# ---- Optimizer::OptimizeEssentialGraph4DoF on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_essential_graph4_capacity", "msorb_essential_graph4", "msorb_essential_graph4_stage_ms")
+
+EG4_VERTEX_DTYPE = np.dtype([("Rcw", "<f8", 9), ("tcw", "<f8", 3), ("Rwb", "<f8", 9), ("twb", "<f8", 3), ("Rcb", "<f8", 9),
+                             ("tcb", "<f8", 3), ("fixed", "<i4"), ("reserved", "<i4")])                                  # msorb_eg4_vertex
+EG4_RESULT_DTYPE = np.dtype(EG_RESULT_DTYPE.descr + [("lambda_initial", "<f8")])                                        # msorb_eg4_result
+assert EG4_VERTEX_DTYPE.itemsize == 296 and EG4_RESULT_DTYPE.itemsize == 56
+
+
+def _eg4_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_essential_graph4_capacity.argtypes = []
+    L.msorb_essential_graph4.argtypes = [ci, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp]
+    L.msorb_essential_graph4_stage_ms.argtypes = [vp]
+    return L
+
+
+def essential_graph4_capacity():
+    """the largest number of free vertices (with an active edge) msorb_essential_graph4 accepts"""
+    return _eg4_lib().msorb_essential_graph4_capacity()
+
+
+def eg4_vertices(Rcw, tcw, Rwb, twb, Rcb, tcb, fixed):
+    """msorb_eg4_vertex records: Rcw, Rwb, Rcb [N, 3, 3] or [N, 9] (row major), tcw, twb, tcb [N, 3], fixed [N]; Rcb / tcb may be
+    one value for all"""
+    v = np.zeros(len(fixed), EG4_VERTEX_DTYPE)
+    for k, a in (("Rcw", Rcw), ("Rwb", Rwb), ("Rcb", Rcb)):
+        v[k] = np.asarray(a, np.float64).reshape(-1, 9)
+    v["tcw"], v["twb"], v["tcb"], v["fixed"] = tcw, twb, tcb, fixed
+    return v
+
+
+def essential_graph4(vertices, edge_v0, edge_v1, measurements, iterations=20, device=0, timing=False, poses_out=None):
+    """msorb_essential_graph4: Optimizer::OptimizeEssentialGraph4DoF after its gathering loops, on the device.  vertices:
+    EG4_VERTEX_DTYPE [N]; edge e joins edge_v0[e] -> edge_v1[e] with measurements[e] = (dRij[9], dtij[3]).
+    -> dict(result: EG4_RESULT_DTYPE record, poses float64 [N, 12] = Rcw[9], tcw[3]) and, with timing, elapsed_ms (device time).
+    poses_out: an [N, 12] float64 array to be written instead of a fresh one (it keeps its contents when the call is refused)."""
+    L = _eg4_lib()
+    vt = _c(vertices, EG4_VERTEX_DTYPE).reshape(-1)
+    e0, e1 = _c(edge_v0, np.int32).reshape(-1), _c(edge_v1, np.int32).reshape(-1)
+    me = _c(measurements, np.float64).reshape(-1, 12)
+    if [len(e1), len(me)] != [len(e0)] * 2:
+        raise ValueError("the edge arrays do not have one entry per edge")
+    out = np.zeros((max(len(vt), 1), 12), np.float64) if poses_out is None else poses_out
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.size >= 12 * len(vt)
+    res = np.zeros(1, EG4_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_essential_graph4(device, len(vt), _np_ptr(vt), len(e0), _np_ptr(e0), _np_ptr(e1), _np_ptr(me), int(iterations),
+                                    _np_ptr(out), _np_ptr(res), C.addressof(ms)), "msorb_essential_graph4")
+    r = dict(result=res[0], poses=out[:len(vt)])
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r
+
+
+def essential_graph4_stage_ms():
+    """dict(linearise, assemble, solve, trial) in device ms of this thread's last essential_graph4 call (MSORB_LOCAL_BA_STAGES=1)"""
+    ms = np.zeros(4, np.float32)
+    _check(_eg4_lib().msorb_essential_graph4_stage_ms(_np_ptr(ms)), "msorb_essential_graph4_stage_ms")
+    return dict(zip(("linearise", "assemble", "solve", "trial"), (float(v) for v in ms)))
