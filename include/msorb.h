@@ -1382,6 +1382,53 @@ int msorb_essential_graph4(int device, int n_vertices, const msorb_eg4_vertex* v
  * MSORB_LOCAL_BA_STAGES=1 in the environment before the library is loaded (MSORB_E_ARG otherwise, zeros). */
 int msorb_essential_graph4_stage_ms(float ms[4]);
 
+/* Optimizer::InertialOptimization (src/Optimizer.cc:3050-3227, :3230-3384, :3386-3491: IMU initialisation, the bias refit after a
+ * merge, ScaleRefinement) after the gathering loops, on the device, the whole optimize(its) in ONE launch: EdgeInertialGS
+ * (src/G2oTypes.cc:596-718) between consecutive KeyFrames with every pose fixed, EdgePriorAcc / EdgePriorGyro on the biases, the
+ * vertices VertexVelocity, VertexGyroBias, VertexAccBias, VertexGDir, VertexScale, Levenberg or Gauss-Newton, in double with the
+ * preintegration's bias correction in float as the reference has it.  The three overloads are one graph with different vertices
+ * fixed: the free_* flags.  Appended to ABI 6002: MSORB_ABI_VERSION stays 6002.
+ * kfs [n_kf]: the body pose Rwb (row major), twb and the velocity the estimate starts from; has_velocity_vertex = 0 for a KeyFrame
+ * the reference gives no vertex (mnId > maxKFid): no edge may name it.  edges [n_edges] in the order of the reference's edge list:
+ * the members of IMU::Preintegrated as floats (3x3 row major; bias = b: ba then bg), and info = the FULL 9x9 information the
+ * edge's constructor leaves (:604-612), row major, all 81 entries used.  Every KeyFrame may have one incoming and one outgoing
+ * edge and the edges may form no cycle (chains): anything else is MSORB_E_CAPACITY ("not handled"), as is n_kf above
+ * msorb_inertial_optimization_capacity().  A KeyFrame without an edge has no active vertex: v_out returns its velocity as it came.
+ * with_priors: the two prior edges exist (first and second overload), information prior_a I and prior_g I.  They are active
+ * only while the biases are free (g2o's initializeOptimization drops an edge whose vertices are all fixed): with free_biases == 0
+ * they enter neither chi2 nor n_active_edges.  n_edges == 0 is valid: gravity direction, scale and velocities are then
+ * inactive, and without a free bias under a prior nothing is optimised (status 1, g2o's "0 vertices to optimize").
+ * H is block-tridiagonal (3x3, velocities in chain order) with a dense border of at most 9 (bg, ba, gravity direction, scale):
+ * solved by block cyclic reduction and a Schur complement on the border, unpivoted L D L^T throughout, where the reference runs a
+ * sparse Cholesky.  v_out [3 n_kf]; edge_chi2 [n_edges] or NULL: chi2() of every inertial edge at the returned estimate.
+ * Errors, before anything is launched and with no output written: MSORB_E_INVALID for a null required pointer, a negative count,
+ * an index out of range, kf_prev == kf_cur, an edge on a KeyFrame without velocity vertex, iterations < 0 or > 10000, an unknown algorithm,
+ * a non-finite input.  Two calls on the same input return the same bits.  Re-entrant.  *elapsed_ms (may be NULL): device time. */
+typedef struct msorb_inertial_keyframe { double Rwb[9], twb[3], v[3]; int32_t has_velocity_vertex, reserved; } msorb_inertial_keyframe;
+typedef struct msorb_inertial_edge {
+    int32_t kf_prev, kf_cur;
+    float dR[9], dV[3], dP[3], JRg[9], JVg[9], JVa[9], JPg[9], JPa[9], bias[6], dT;
+    double info[81];
+} msorb_inertial_edge;
+typedef struct msorb_inertial_problem {
+    double Rwg[9], scale, bg[3], ba[3], prior_g, prior_a;
+    int32_t free_velocities, free_biases, free_gdir, free_scale, with_priors;
+    int32_t algorithm;          /* 0 Levenberg, 1 Gauss-Newton */
+    int32_t user_lambda_init;   /* 1: setUserLambdaInit(1e3); 0: computeLambdaInit = 1e-5 max |H(j,j)| */
+    int32_t huber;              /* 1: RobustKernelHuber with delta 1 on every inertial edge */
+    int32_t iterations, reserved;
+} msorb_inertial_problem;
+typedef struct msorb_inertial_result {
+    double Rwg[9], scale, bg[3], ba[3], chi2_initial, chi2_final;
+    int32_t status;             /* 0 optimised; 1 no vertex to optimise (optimize returns -1, nothing moved); 2 Gauss-Newton's
+                                   solve failed: update(x) ran with the x it held, then the loop stopped (optimize returns 0) */
+    int32_t iterations, rejected_trials, n_active_edges;
+} msorb_inertial_result;
+int msorb_inertial_optimization_capacity(void);        /* KeyFrames: 4096 */
+int msorb_inertial_optimization(int device, const msorb_inertial_problem* p, int n_kf, const msorb_inertial_keyframe* kfs,
+                                int n_edges, const msorb_inertial_edge* edges, double* v_out, double* edge_chi2,
+                                msorb_inertial_result* r, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

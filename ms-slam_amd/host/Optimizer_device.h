@@ -46,6 +46,8 @@
 
 #include "msorb.h"
 #include "../csrc/sim3_opt_device.h"   // the product, inverse and map of Sim3 in double (OptimizeEssentialGraph)
+#include "../csrc/inertial_device.h"   // info_from_covariance (InertialOptimization)
+#include "../csrc/inertial_plan.h"     // make_plan: the chains the device solves
 
 namespace ORB_SLAM3 {
 namespace msorb_host {
@@ -1179,6 +1181,217 @@ bool OptimizeEssentialGraph4DoF(MapT* pMap, KFPtr pLoopKF, KFPtr pCurKF, const P
         pMP->UpdateNormalAndDepth();
     }
     pMap->IncreaseChangeIndex();                                                                         // :5457
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::InertialOptimization (src/Optimizer.cc:3050-3227, :3230-3384, :3386-3491; LocalMapping.cc:1288 InitializeIMU,
+// LoopClosing.cc:1807 after a merge, LocalMapping.cc:1481 ScaleRefinement) on msorb_inertial_optimization.
+//
+//   bool ORB_SLAM3::msorb_host::InertialOptimization(pMap, Rwg, scale, bg, ba, bMono, covInertial, bFixedVel, bGauss, priorG, priorA)
+//   bool ORB_SLAM3::msorb_host::InertialOptimization(pMap, bg, ba, priorG, priorA)
+//   bool ORB_SLAM3::msorb_host::InertialOptimization(pMap, Rwg, scale)
+//
+// the reference's parameter lists (a trailing `device` besides), and its effects.  Gathering stays host code, in the reference's
+// order: the `mnId > maxKFid` skips, mpImuPreintegrated->SetNewBias(mPrevKF->GetImuBias()) per edge in the first two overloads
+// only, the bias vertices built from vpKFs.front() (in the third overload one pair per KeyFrame, all from vpKFs.front() alike).
+// Afterwards scale, Rwg, bg, ba are written, every KeyFrame with a vertex gets SetVelocity(Vw.cast<float>()) and SetNewBias(b), with
+// Reintegrate() when (GetGyroBias() - bg.cast<float>()).norm() > 0.01 held before the new bias was set (:3218-3223).  The third
+// overload writes scale and Rwg only; its two activeRobustChi2 floats have no effect and are not restated.  covInertial and bGauss
+// are read by nothing in the reference; bMono only frees the scale (:3131).  bg and ba are outputs: the estimates start from
+// vpKFs.front()'s biases.
+//
+// false = NOT handled, nothing touched (decided before the first side effect), the caller runs Optimizer::InertialOptimization: an
+// empty map, more KeyFrames than msorb_inertial_optimization_capacity(), an edge whose KeyFrame lacks mpImuPreintegrated, an edge
+// whose mPrevKF has no vertex (not among GetAllKeyFrames(): the reference's error branch, which dereferences null in the third
+// overload), a covariance whose inverse does not exist, a structure the plan rejects (two KeyFrames with one mPrevKF).  A device
+// error after the gathering also returns false; the SetNewBias calls made until then are the ones the reference repeats.
+namespace inertial_detail {
+struct Gathered {
+    std::vector<msorb_inertial_keyframe> kfs;
+    std::vector<msorb_inertial_edge> edges;
+    std::vector<int> edge_kf;                                                                            // per edge: the position of its KeyFrame in vpKFs
+};
+
+// Everything the device needs from vpKFs, WITHOUT a side effect, and "would it be handled".  vpKFs and maxKFid are fetched once by
+// the caller, as the reference fetches them (:3055-3056), and serve the gathering and the write-back alike.
+template <class KFVec>
+bool Gather(const KFVec& vpKFs, unsigned long maxKFid, Gathered& G) {
+    if (vpKFs.empty() || (int)vpKFs.size() > msorb_inertial_optimization_capacity()) return false;      // (vpKFs.front() of :3094)
+    G.kfs.assign(vpKFs.size(), msorb_inertial_keyframe());
+    G.edges.clear();
+    G.edge_kf.clear();
+    std::vector<int> index(maxKFid + 1, -1);                                                             // optimizer.vertex(mnId): position in vpKFs
+    for (size_t i = 0; i < vpKFs.size(); i++) {                                                          // :3074-3091
+        const auto& pKFi = vpKFs[i];
+        msorb_inertial_keyframe& k = G.kfs[i];
+        const auto Rwb = pKFi->GetImuRotation();                                                         // ImuCamPose(pKF) (G2oTypes.cc:28-29)
+        const auto twb = pKFi->GetImuPosition();
+        const auto v = pKFi->GetVelocity();                                                              // VertexVelocity(pKF) (:456-459)
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) k.Rwb[3 * r + c] = (double)Rwb(r, c);
+            k.twb[r] = (double)twb(r);
+            k.v[r] = (double)v(r);
+        }
+        k.has_velocity_vertex = pKFi->mnId > maxKFid ? 0 : 1;
+        k.reserved = 0;
+        if (k.has_velocity_vertex) index[pKFi->mnId] = (int)i;
+    }
+    std::vector<int> prev, cur;
+    for (size_t i = 0; i < vpKFs.size(); i++) {                                                          // :3142-3182
+        const auto& pKFi = vpKFs[i];
+        if (!(pKFi->mPrevKF && pKFi->mnId <= maxKFid)) continue;
+        if (pKFi->isBad() || pKFi->mPrevKF->mnId > maxKFid) continue;
+        const auto pInt = pKFi->mpImuPreintegrated;
+        if (!pInt) return false;                                                                         // :3148-3151 would dereference it
+        const int at = index[pKFi->mPrevKF->mnId];
+        if (at < 0 || vpKFs[at] != pKFi->mPrevKF) return false;                                          // :3160-3165: no such vertex
+        msorb_inertial_edge e;
+        e.kf_prev = at;
+        e.kf_cur = (int)i;
+        const auto &dR = pInt->dR, &JRg = pInt->JRg, &JVg = pInt->JVg, &JVa = pInt->JVa, &JPg = pInt->JPg, &JPa = pInt->JPa;   // Matrix3f
+        const auto &dV = pInt->dV, &dP = pInt->dP;                                                       // Vector3f
+        const auto& C = pInt->C;                                                                         // Matrix<float, 15, 15>
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) {
+                e.dR[3 * r + c] = dR(r, c); e.JRg[3 * r + c] = JRg(r, c); e.JVg[3 * r + c] = JVg(r, c);
+                e.JVa[3 * r + c] = JVa(r, c); e.JPg[3 * r + c] = JPg(r, c); e.JPa[3 * r + c] = JPa(r, c);
+            }
+            e.dV[r] = dV(r);
+            e.dP[r] = dP(r);
+        }
+        const auto& imuBias = pInt->b;
+        e.bias[0] = imuBias.bax; e.bias[1] = imuBias.bay; e.bias[2] = imuBias.baz;
+        e.bias[3] = imuBias.bwx; e.bias[4] = imuBias.bwy; e.bias[5] = imuBias.bwz;
+        e.dT = pInt->dT;
+        float C9[81];
+        for (int r = 0; r < 9; r++)
+            for (int c = 0; c < 9; c++) C9[9 * r + c] = C(r, c);
+        if (!msorb::inertial::info_from_covariance(C9, 9, e.info)) return false;                         // G2oTypes.cc:604-612
+        prev.push_back(e.kf_prev);
+        cur.push_back(e.kf_cur);
+        G.edges.push_back(e);
+        G.edge_kf.push_back((int)i);
+    }
+    msorb::inertial::Plan plan;
+    return msorb::inertial::make_plan((int)G.kfs.size(), (int)G.edges.size(), prev.data(), cur.data(), plan) == msorb::inertial::kPlanOk;
+}
+
+// which: 1, 2, 3 = the overload
+template <class KFVec>
+bool Run(const KFVec& vpKFs, unsigned long maxKFid, int which, msorb_inertial_problem& P, Gathered& G, std::vector<double>& v,
+         msorb_inertial_result& R, int device) {
+    if (!Gather(vpKFs, maxKFid, G)) return false;                                                        // nothing touched so far
+    if (which != 3)                                                                                      // :3151, :3316, in the edges' order
+        for (int at : G.edge_kf) {
+            const auto& pKFi = vpKFs[at];
+            const auto pInt = pKFi->mpImuPreintegrated;
+            pInt->SetNewBias(pKFi->mPrevKF->GetImuBias());
+        }
+    const auto& pKF = vpKFs.front();
+    const auto bg0 = pKF->GetGyroBias();                                                                 // VertexGyroBias(vpKFs.front()) (:3094, :3418)
+    const auto ba0 = pKF->GetAccBias();
+    for (int k = 0; k < 3; k++) { P.bg[k] = (double)bg0(k); P.ba[k] = (double)ba0(k); }
+    v.assign(3 * G.kfs.size(), 0.0);
+    return msorb_inertial_optimization(device, &P, (int)G.kfs.size(), G.kfs.data(), (int)G.edges.size(), G.edges.data(), v.data(), nullptr, &R,
+                                       nullptr) == MSORB_OK;
+}
+
+// :3193-3226 / :3355-3383, over the vector the velocities were gathered from: v[3 i] belongs to vpKFs[i]
+template <class KFVec, class Vec3d>
+void WriteBack(const KFVec& vpKFs, unsigned long maxKFid, const std::vector<double>& v, const msorb_inertial_result& R, Vec3d& bg, Vec3d& ba) {
+    for (int k = 0; k < 3; k++) { bg(k) = R.bg[k]; ba(k) = R.ba[k]; }
+    for (size_t i = 0; i < vpKFs.size(); i++) {
+        const auto& pKFi = vpKFs[i];
+        if (pKFi->mnId > maxKFid) continue;
+        typedef typename std::decay<decltype(pKFi->GetVelocity())>::type VelT;
+        typedef typename std::decay<decltype(pKFi->GetImuBias())>::type BiasT;
+        pKFi->SetVelocity(VelT((float)v[3 * i], (float)v[3 * i + 1], (float)v[3 * i + 2]));              // :3216
+        const BiasT b((float)R.ba[0], (float)R.ba[1], (float)R.ba[2], (float)R.bg[0], (float)R.bg[1], (float)R.bg[2]);   // :3204
+        const auto gb = pKFi->GetGyroBias();
+        const float dx = gb(0) - (float)R.bg[0], dy = gb(1) - (float)R.bg[1], dz = gb(2) - (float)R.bg[2];
+        const float norm = std::sqrt((dx * dx + dy * dy) + dz * dz);                                     // :3218, in float
+        if (norm > 0.01) {
+            pKFi->SetNewBias(b);
+            const auto pInt = pKFi->mpImuPreintegrated;
+            if (pInt) pInt->Reintegrate();
+        } else {
+            pKFi->SetNewBias(b);
+        }
+    }
+}
+}  // namespace inertial_detail
+
+template <class MapT, class Mat3d, class Vec3d, class MatXd>
+bool InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale, Vec3d& bg, Vec3d& ba, bool bMono, MatXd& covInertial, bool bFixedVel = false,
+                          bool bGauss = false, float priorG = 1e2, float priorA = 1e6, int device = 0) {
+    (void)covInertial; (void)bGauss;                                                                     // read by nothing in :3050-3227
+    msorb_inertial_problem P = msorb_inertial_problem();
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) P.Rwg[3 * r + c] = Rwg(r, c);
+    P.scale = scale;
+    P.prior_g = (double)priorG;                                                                          // double infoPriorG = priorG (:3120)
+    P.prior_a = (double)priorA;
+    P.free_velocities = P.free_biases = bFixedVel ? 0 : 1;                                               // :3085-3106
+    P.free_gdir = 1;
+    P.free_scale = bMono ? 1 : 0;                                                                        // :3131
+    P.with_priors = 1;
+    P.algorithm = 0;
+    P.user_lambda_init = priorG != 0.f ? 1 : 0;                                                          // :3068-3069
+    P.iterations = 200;                                                                                  // :3054
+    inertial_detail::Gathered G;
+    std::vector<double> v;
+    msorb_inertial_result R;
+    const unsigned long maxKFid = pMap->GetMaxKFid();                                                    // :3055-3056, once
+    const auto vpKFs = pMap->GetAllKeyFrames();
+    if (!inertial_detail::Run(vpKFs, maxKFid, 1, P, G, v, R, device)) return false;
+    scale = R.scale;                                                                                     // :3191
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Rwg(r, c) = R.Rwg[3 * r + c];                                        // :3205
+    inertial_detail::WriteBack(vpKFs, maxKFid, v, R, bg, ba);
+    return true;
+}
+
+template <class MapT, class Vec3d>
+bool InertialOptimization(MapT* pMap, Vec3d& bg, Vec3d& ba, float priorG = 1e2, float priorA = 1e6, int device = 0) {
+    msorb_inertial_problem P = msorb_inertial_problem();
+    P.Rwg[0] = P.Rwg[4] = P.Rwg[8] = 1.0;                                                                // VertexGDir(Identity), fixed (:3293-3295)
+    P.scale = 1.0;                                                                                       // VertexScale(1.0), fixed (:3297-3299)
+    P.prior_g = (double)priorG;
+    P.prior_a = (double)priorA;
+    P.free_velocities = P.free_biases = 1;
+    P.with_priors = 1;
+    P.user_lambda_init = 1;                                                                              // :3245
+    P.iterations = 200;                                                                                  // :3232
+    inertial_detail::Gathered G;
+    std::vector<double> v;
+    msorb_inertial_result R;
+    const unsigned long maxKFid = pMap->GetMaxKFid();                                                    // :3233-3234, once
+    const auto vpKFs = pMap->GetAllKeyFrames();
+    if (!inertial_detail::Run(vpKFs, maxKFid, 2, P, G, v, R, device)) return false;
+    inertial_detail::WriteBack(vpKFs, maxKFid, v, R, bg, ba);
+    return true;
+}
+
+template <class MapT, class Mat3d>
+bool InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale, int device = 0) {
+    msorb_inertial_problem P = msorb_inertial_problem();
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) P.Rwg[3 * r + c] = Rwg(r, c);
+    P.scale = scale;
+    P.free_gdir = P.free_scale = 1;                                                                      // :3431, :3435
+    P.algorithm = 1;                                                                                     // :3399 Gauss-Newton
+    P.huber = 1;                                                                                         // :3473-3475
+    P.iterations = 10;                                                                                   // :3387
+    inertial_detail::Gathered G;
+    std::vector<double> v;
+    msorb_inertial_result R;
+    const unsigned long maxKFid = pMap->GetMaxKFid();                                                    // :3388-3389, once
+    const auto vpKFs = pMap->GetAllKeyFrames();
+    if (!inertial_detail::Run(vpKFs, maxKFid, 3, P, G, v, R, device)) return false;
+    scale = R.scale;                                                                                     // :3489
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) Rwg(r, c) = R.Rwg[3 * r + c];                                        // :3490
     return true;
 }
 

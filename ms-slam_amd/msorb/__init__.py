@@ -2456,3 +2456,60 @@ def essential_graph4_stage_ms():
     ms = np.zeros(4, np.float32)
     _check(_eg4_lib().msorb_essential_graph4_stage_ms(_np_ptr(ms)), "msorb_essential_graph4_stage_ms")
     return dict(zip(("linearise", "assemble", "solve", "trial"), (float(v) for v in ms)))
+
+
+# ---- Optimizer::InertialOptimization on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_inertial_optimization_capacity", "msorb_inertial_optimization")
+
+INERTIAL_KF_DTYPE = np.dtype([("Rwb", "<f8", 9), ("twb", "<f8", 3), ("v", "<f8", 3), ("has_velocity_vertex", "<i4"),
+                              ("reserved", "<i4")])                                                                       # msorb_inertial_keyframe
+INERTIAL_EDGE_DTYPE = np.dtype([("kf_prev", "<i4"), ("kf_cur", "<i4"), ("dR", "<f4", 9), ("dV", "<f4", 3), ("dP", "<f4", 3),
+                                ("JRg", "<f4", 9), ("JVg", "<f4", 9), ("JVa", "<f4", 9), ("JPg", "<f4", 9), ("JPa", "<f4", 9),
+                                ("bias", "<f4", 6), ("dT", "<f4"), ("pad", "<i4"), ("info", "<f8", 81)])                 # msorb_inertial_edge
+INERTIAL_PROBLEM_DTYPE = np.dtype([("Rwg", "<f8", 9), ("scale", "<f8"), ("bg", "<f8", 3), ("ba", "<f8", 3), ("prior_g", "<f8"),
+                                   ("prior_a", "<f8"), ("free_velocities", "<i4"), ("free_biases", "<i4"), ("free_gdir", "<i4"),
+                                   ("free_scale", "<i4"), ("with_priors", "<i4"), ("algorithm", "<i4"), ("user_lambda_init", "<i4"),
+                                   ("huber", "<i4"), ("iterations", "<i4"), ("reserved", "<i4")])                        # msorb_inertial_problem
+INERTIAL_RESULT_DTYPE = np.dtype([("Rwg", "<f8", 9), ("scale", "<f8"), ("bg", "<f8", 3), ("ba", "<f8", 3), ("chi2_initial", "<f8"),
+                                  ("chi2_final", "<f8"), ("status", "<i4"), ("iterations", "<i4"), ("rejected_trials", "<i4"),
+                                  ("n_active_edges", "<i4")])                                                             # msorb_inertial_result
+assert (INERTIAL_KF_DTYPE.itemsize, INERTIAL_EDGE_DTYPE.itemsize, INERTIAL_PROBLEM_DTYPE.itemsize,
+        INERTIAL_RESULT_DTYPE.itemsize) == (128, 928, 184, 160)
+
+
+def _inertial_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_inertial_optimization_capacity.argtypes = []
+    L.msorb_inertial_optimization.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    return L
+
+
+def inertial_optimization_capacity():
+    """the largest number of KeyFrames msorb_inertial_optimization accepts"""
+    return _inertial_lib().msorb_inertial_optimization_capacity()
+
+
+def inertial_optimization(problem, keyframes, edges, device=0, timing=False, v_out=None):
+    """msorb_inertial_optimization: Optimizer::InertialOptimization (any of its three overloads: the problem's free_* flags) after
+    its gathering loops, on the device.  problem: an INERTIAL_PROBLEM_DTYPE record; keyframes: INERTIAL_KF_DTYPE [K]; edges:
+    INERTIAL_EDGE_DTYPE [E] in the order of the reference's edge list.
+    -> dict(result: INERTIAL_RESULT_DTYPE record, v float64 [K, 3], edge_chi2 float64 [E]) and, with timing, elapsed_ms (device
+    time).  v_out: a [K, 3] float64 array to be written instead of a fresh one (it keeps its contents when the call is refused)."""
+    L = _inertial_lib()
+    pr = _c(problem, INERTIAL_PROBLEM_DTYPE).reshape(-1)
+    kf = _c(keyframes, INERTIAL_KF_DTYPE).reshape(-1)
+    ed = _c(edges, INERTIAL_EDGE_DTYPE).reshape(-1)
+    if len(pr) != 1:
+        raise ValueError("one problem record is needed")
+    out = np.zeros((max(len(kf), 1), 3), np.float64) if v_out is None else v_out
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.size >= 3 * len(kf)
+    chi2 = np.zeros(max(len(ed), 1), np.float64)
+    res = np.zeros(1, INERTIAL_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_inertial_optimization(device, _np_ptr(pr), len(kf), _np_ptr(kf), len(ed), _np_ptr(ed), _np_ptr(out), _np_ptr(chi2),
+                                         _np_ptr(res), C.addressof(ms)), "msorb_inertial_optimization")
+    r = dict(result=res[0], v=out[:len(kf)], edge_chi2=chi2[:len(ed)])
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r

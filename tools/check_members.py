@@ -43,6 +43,8 @@ OBJECT_CLASS = [
     (re.compile(r"^(F|F1|F2|CurrentFrame|LastFrame)$"), "Frame", "."),
     (re.compile(r"^(pMP\w*|p|pMPinKF|points)$"), "MapPoint", "->"),
     (re.compile(r"^(mpCamera\w*|pCamera\w*)$"), "GeometricCamera", "->"),
+    (re.compile(r"^pInt$"), "Preintegrated", "->"),      # IMU::Preintegrated (Optimizer_device.h's InertialOptimization)
+    (re.compile(r"^imuBias$"), "Bias", "."),             # IMU::Bias
 ]
 # names that look like member accesses on those objects but are not (local structs of the host layer)
 IGNORE_OBJECT_FILES = {}
@@ -213,7 +215,7 @@ def members(kind, body):
 
 def parse_reference():
     classes = {}
-    for h in ("Frame.h", "KeyFrame.h", "MapPoint.h", "ORBextractor.h", "ORBmatcher.h", "GeometricCamera.h"):
+    for h in ("Frame.h", "KeyFrame.h", "MapPoint.h", "ORBextractor.h", "ORBmatcher.h", "GeometricCamera.h", "ImuTypes.h"):
         path = os.path.join(REF, "include", h)
         if not os.path.exists(path):
             path = os.path.join(REF, "include", "CameraModels", h)
