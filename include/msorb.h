@@ -1429,6 +1429,53 @@ int msorb_inertial_optimization(int device, const msorb_inertial_problem* p, int
                                 int n_edges, const msorb_inertial_edge* edges, double* v_out, double* edge_chi2,
                                 msorb_inertial_result* r, float* elapsed_ms);
 
+/* Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:4422-4779) and PoseInertialOptimizationLastFrame (:4781-5172)
+ * after their gathering loops, for pinhole mono / stereo frames without a second camera: the four rounds of Gauss-Newton, the
+ * classifications, the recovery arm and the final Hessian in ONE launch, in double with the preintegration's bias correction in
+ * float as the reference has it; the marginalisation (:2975-3048) and ConstraintPoseImu's constructor (G2oTypes.h:711-722) run on
+ * the host inside the call.  Appended to ABI 6002: MSORB_ABI_VERSION stays 6002.
+ * form 0: the other end is the last KeyFrame, its four vertices fixed (15 unknowns).  form 1: the other end is the previous frame,
+ * free, under EdgePriorPoseImu with the information H and the linearisation point `prior` (30 unknowns, the frame's first).
+ * frame / other: {Rwb (row major), twb, v, bg, ba} the estimates start from.  Rcw, tcw: GetPose() widened (ImuCamPose does not
+ * derive them from Rwb / twb); Rcb, tcb: mTcb; tbc: mTbc.translation().  pre: the preintegration of the inertial edge (kf_prev /
+ * kf_cur ignored; info = the full 9x9 information of EdgeInertial's constructor).  info_gyro, info_acc: the 3x3 informations of
+ * EdgeGyroRW / EdgeAccRW, row major.  rec_init: bRecInit.  n: observations (u_right >= 0 = stereo; close = mTrackDepth < 10.f).
+ * Result: est = the frame's four vertices in double; Rwb_f, twb_f, v_f = what SetImuPoseVelocity receives; n_initial - n_bad is
+ * the reference's return value; iterations[k] = passes of round k (-1: round not run), solve_failed[k] = its solve failed (the
+ * update ran with the x the solver held; x starts at zero); H_raw = the 15x15 (form 0) or 30x30 (form 1, previous frame first)
+ * Hessian of :4743-4773 / :5120-5162, row major; H_prior = the H the new ConstraintPoseImu holds.
+ * Errors, before anything is launched and with no output written: MSORB_E_INVALID for a null required pointer, a negative count,
+ * an unknown form, offsets that do not match the problems' n, a non-finite input.  Two calls on the same input return the same
+ * bits.  Re-entrant. */
+typedef struct msorb_pose_inertial_state { double Rwb[9], twb[3], v[3], bg[3], ba[3]; } msorb_pose_inertial_state;
+typedef struct msorb_pose_inertial_problem {
+    int32_t form, rec_init, n, reserved;
+    msorb_pose_inertial_state frame, other, prior;
+    double Rcw[9], tcw[3], Rcb[9], tcb[3], tbc[3];
+    float fx, fy, cx, cy, mbf, reserved_f;
+    msorb_inertial_edge pre;
+    double info_gyro[9], info_acc[9];
+    double H[225];              /* form 1: mpcpi->H, row major */
+} msorb_pose_inertial_problem;
+typedef struct msorb_pose_inertial_result {
+    msorb_pose_inertial_state est;
+    float Rwb_f[9], twb_f[3], v_f[3];
+    int32_t n_initial, n_bad, n_inliers;
+    int32_t iterations[4], solve_failed[4];
+    double H_raw[900];
+    double H_prior[225];
+} msorb_pose_inertial_result;
+int msorb_pose_inertial_optimization_capacity(void);   /* observations a problem keeps in registers: 2048 */
+int msorb_pose_inertial_optimization_batch(int device, int n_problems, const msorb_pose_inertial_problem* problems,
+                                           const int* obs_offset, const float* xy, const float* u_right, const float* inv_sigma2,
+                                           const float* pos_w, const uint8_t* close, uint8_t* outlier_out,
+                                           msorb_pose_inertial_result* results, float* elapsed_ms);
+/* The frame form over the keypoint table resident on the handle (rectified input, as msorb_frame_pose_optimization): has_point
+ * [N], pos_w [N, 3], close [N]; outlier [N] is written where has_point is set.  Bit-equal to the flat form. */
+int msorb_frame_pose_inertial_optimization(msorb_frame* f, const msorb_pose_inertial_problem* p, const uint8_t* has_point,
+                                           const float* pos_w, const uint8_t* close, const float* inv_level_sigma2, int nlevels,
+                                           uint8_t* outlier, msorb_pose_inertial_result* r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,8 +14,8 @@
 // The four rounds, every Levenberg step and the classifications are one device launch.
 //
 // Scope: pinhole mono / stereo frames.  A frame with a second camera (pFrame->mpCamera2, the arm :870-931) is NOT handled:
-// the function returns -1 without touching the frame and the caller keeps Optimizer::PoseOptimization for it, as for the
-// inertial variants.  The camera is read from pFrame->fx, fy, cx, cy, mbf, which for Pinhole are the values pCamera->project
+// the function returns -1 without touching the frame and the caller keeps Optimizer::PoseOptimization for it (the inertial
+// variants, PoseInertialOptimizationLastKeyFrame / LastFrame, have templates of their own at the end of this header).  The camera is read from pFrame->fx, fy, cx, cy, mbf, which for Pinhole are the values pCamera->project
 // uses (mvParameters[0..3]).
 //
 // `resident`: a handle whose keypoint table holds THIS frame's mvKeysUn, mvuRight and octaves (DeviceFrame::Upload /
@@ -1393,6 +1393,237 @@ bool InertialOptimization(MapT* pMap, Mat3d& Rwg, double& scale, int device = 0)
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) Rwg(r, c) = R.Rwg[3 * r + c];                                        // :3490
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::PoseInertialOptimizationLastKeyFrame (src/Optimizer.cc:4422-4779) and PoseInertialOptimizationLastFrame
+// (:4781-5172; Tracking.cc:2946-2968) on msorb_pose_inertial_optimization_batch / msorb_frame_pose_inertial_optimization.
+//
+//   int ORB_SLAM3::msorb_host::PoseInertialOptimizationLastKeyFrame(Frame* pFrame, bool bRecInit = false)
+//   int ORB_SLAM3::msorb_host::PoseInertialOptimizationLastFrame(Frame* pFrame, bool bRecInit = false)
+//   ... (Frame* pFrame, msorb_frame* resident, bool bRecInit = false)      keypoints already on a handle, rectified input
+//
+// the reference's parameter lists and effects, in its order: mvbOutlier of every entry with a map point (`if (pMP)` alone, no
+// isBad() here), SetImuPoseVelocity with the narrowed estimate, mImuBias, pFrame->mpcpi = new ConstraintPoseImu(...) and, in the
+// LastFrame form, delete pFp->mpcpi; pFp->mpcpi = NULL.  The return value is nInitialCorrespondences - nBad.
+//
+// The gathering loops (:4473-4576, :4832-4934) stay host code; the information matrices are built here (info_from_covariance
+// for the 9x9 of EdgeInertial's constructor, a written-out 3x3 inverse in double for the two random-walk blocks of
+// pFrame->mpImuPreintegrated->C, which both forms read: :4610, :4971); then one call.
+//
+// The library returns H_prior, what ConstraintPoseImu's constructor leaves.  The constructor would clip that matrix once more
+// (another eigen-decomposition, not the identity in floating point), so the object is constructed and its public member H is then
+// assigned the returned matrix: mpcpi->H is H_prior bit for bit.
+//
+// -1 = NOT handled, nothing touched, the caller keeps the g2o routine: a second camera (mpCamera2), Nleft != -1, a missing
+// preintegration or other end, a covariance without inverse and, in the LastFrame form, !pFp->mpcpi (the reference
+// dereferences null there).
+namespace pose_inertial_detail {
+template <class PreT>
+bool EdgeOf(const PreT& pInt, msorb_inertial_edge& e) {
+    e.kf_prev = 0;
+    e.kf_cur = 0;
+    const auto &dR = pInt->dR, &JRg = pInt->JRg, &JVg = pInt->JVg, &JVa = pInt->JVa, &JPg = pInt->JPg, &JPa = pInt->JPa;   // Matrix3f
+    const auto &dV = pInt->dV, &dP = pInt->dP;                                                           // Vector3f
+    const auto& C = pInt->C;                                                                             // Matrix<float, 15, 15>
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) {
+            e.dR[3 * r + c] = dR(r, c); e.JRg[3 * r + c] = JRg(r, c); e.JVg[3 * r + c] = JVg(r, c);
+            e.JVa[3 * r + c] = JVa(r, c); e.JPg[3 * r + c] = JPg(r, c); e.JPa[3 * r + c] = JPa(r, c);
+        }
+        e.dV[r] = dV(r);
+        e.dP[r] = dP(r);
+    }
+    const auto& imuBias = pInt->b;
+    e.bias[0] = imuBias.bax; e.bias[1] = imuBias.bay; e.bias[2] = imuBias.baz;
+    e.bias[3] = imuBias.bwx; e.bias[4] = imuBias.bwy; e.bias[5] = imuBias.bwz;
+    e.dT = pInt->dT;
+    float C9[81];
+    for (int r = 0; r < 9; r++)
+        for (int c = 0; c < 9; c++) C9[9 * r + c] = C(r, c);
+    return msorb::inertial::info_from_covariance(C9, 9, e.info);                                         // G2oTypes.cc:500-508
+}
+
+// C.block<3, 3>(at, at).cast<double>().inverse() (:4610, :4617): the adjugate over the determinant, in double
+template <class PreT>
+bool RandomWalkInformation(const PreT& pInt, int at, double* info) {
+    double m[9];
+    const auto& C = pInt->C;
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) m[3 * r + c] = (double)C(at + r, at + c);
+    const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
+    const double det = (m[0] * c00 + m[1] * c01) + m[2] * c02;
+    if (!(std::fabs(det) > 0) || !std::isfinite(det)) return false;
+    const double inv = 1.0 / det;
+    info[0] = c00 * inv; info[1] = (m[2] * m[7] - m[1] * m[8]) * inv; info[2] = (m[1] * m[5] - m[2] * m[4]) * inv;
+    info[3] = c01 * inv; info[4] = (m[0] * m[8] - m[2] * m[6]) * inv; info[5] = (m[2] * m[3] - m[0] * m[5]) * inv;
+    info[6] = c02 * inv; info[7] = (m[1] * m[6] - m[0] * m[7]) * inv; info[8] = (m[0] * m[4] - m[1] * m[3]) * inv;
+    return true;
+}
+
+template <class RotT, class VecT, class VelT>
+void StateOf(const RotT& Rwb, const VecT& twb, const VelT& v, msorb_pose_inertial_state& s) {
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) s.Rwb[3 * r + c] = (double)Rwb(r, c);
+        s.twb[r] = (double)twb(r);
+        s.v[r] = (double)v(r);
+    }
+}
+template <class BiasT>
+void BiasOf(const BiasT& b, msorb_pose_inertial_state& s) {                                              // G2oTypes.cc:471-488
+    s.bg[0] = b.bwx; s.bg[1] = b.bwy; s.bg[2] = b.bwz;
+    s.ba[0] = b.bax; s.ba[1] = b.bay; s.ba[2] = b.baz;
+}
+
+// form 0: the last KeyFrame; form 1: the previous frame
+template <class FrameT>
+int Run(FrameT* pFrame, int form, msorb_frame* resident, bool bRecInit, int device) {
+    if (pFrame->mpCamera2 || pFrame->Nleft != -1) return -1;
+    const auto pIntKF = pFrame->mpImuPreintegrated;                                                      // the random-walk blocks, both forms
+    if (!pIntKF) return -1;
+    static thread_local msorb_pose_inertial_problem p;
+    static thread_local msorb_pose_inertial_result r;
+    p = msorb_pose_inertial_problem();
+    p.form = form;
+    p.rec_init = bRecInit ? 1 : 0;
+    auto* pFp = pFrame->mpPrevFrame;
+    if (form == 0) {
+        const auto pKF = pFrame->mpLastKeyFrame;                                                         // :4579-4595
+        if (!pKF) return -1;
+        StateOf(pKF->GetImuRotation(), pKF->GetImuPosition(), pKF->GetVelocity(), p.other);
+        const auto bg = pKF->GetGyroBias();
+        const auto ba = pKF->GetAccBias();
+        for (int k = 0; k < 3; k++) { p.other.bg[k] = (double)bg(k); p.other.ba[k] = (double)ba(k); }
+        if (!EdgeOf(pIntKF, p.pre)) return -1;                                                           // :4597
+    } else {
+        if (!pFp || !pFp->mpcpi) return -1;                                                              // :4982-4986
+        const auto pIntF = pFrame->mpImuPreintegratedFrame;                                              // :4958
+        if (!pIntF || !EdgeOf(pIntF, p.pre)) return -1;
+        StateOf(pFp->GetImuRotation(), pFp->GetImuPosition(), pFp->GetVelocity(), p.other);              // :4938-4956
+        BiasOf(pFp->mImuBias, p.other);
+        const auto* c = pFp->mpcpi;                                                                      // G2oTypes.cc:720-729
+        StateOf(c->Rwb, c->twb, c->vwb, p.prior);
+        for (int k = 0; k < 3; k++) { p.prior.bg[k] = c->bg(k); p.prior.ba[k] = c->ba(k); }
+        for (int a = 0; a < 15; a++)
+            for (int b = 0; b < 15; b++) p.H[15 * a + b] = c->H(a, b);
+    }
+    if (!RandomWalkInformation(pIntKF, 9, p.info_gyro) || !RandomWalkInformation(pIntKF, 12, p.info_acc)) return -1;   // :4610, :4617
+    StateOf(pFrame->GetImuRotation(), pFrame->GetImuPosition(), pFrame->GetVelocity(), p.frame);         // :4439-4454
+    BiasOf(pFrame->mImuBias, p.frame);
+    {
+        const auto Tcw = pFrame->GetPose();                                                              // G2oTypes.cc:95-100
+        const auto Rcw = Tcw.rotationMatrix();
+        const auto tcw = Tcw.translation();
+        const auto Rcb = pFrame->mImuCalib.mTcb.rotationMatrix();
+        const auto tcb = pFrame->mImuCalib.mTcb.translation();
+        const auto tbc = pFrame->mImuCalib.mTbc.translation();
+        for (int a = 0; a < 3; a++) {
+            for (int b = 0; b < 3; b++) { p.Rcw[3 * a + b] = (double)Rcw(a, b); p.Rcb[3 * a + b] = (double)Rcb(a, b); }
+            p.tcw[a] = (double)tcw(a); p.tcb[a] = (double)tcb(a); p.tbc[a] = (double)tbc(a);
+        }
+    }
+    p.fx = pFrame->fx; p.fy = pFrame->fy; p.cx = pFrame->cx; p.cy = pFrame->cy; p.mbf = pFrame->mbf;
+    typedef typename std::decay<decltype(*pFrame->mvpMapPoints[0])>::type MapPointT;
+    const int N = pFrame->N;
+    static thread_local std::vector<uint8_t> has, out, close, closeN;
+    static thread_local std::vector<float> pos, xy, ur, inv;
+    static thread_local std::vector<int> index;
+    has.assign((size_t)N, 0);
+    closeN.assign((size_t)N, 0);
+    pos.resize(3 * (size_t)N);
+    index.clear();
+    {
+        std::unique_lock<std::mutex> lock(MapPointT::mGlobalMutex);                                      // :4474
+        for (int i = 0; i < N; i++) {
+            const auto pMP = pFrame->mvpMapPoints[i];
+            if (pMP) {                                                                                   // :4478: no isBad() here
+                pFrame->mvbOutlier[i] = false;                                                           // :4489, :4517
+                const auto Xw = pMP->GetWorldPos();
+                has[i] = 1;
+                closeN[i] = pMP->mTrackDepth < 10.f ? 1 : 0;                                             // :4657
+                pos[3 * (size_t)i] = Xw(0); pos[3 * (size_t)i + 1] = Xw(1); pos[3 * (size_t)i + 2] = Xw(2);
+                index.push_back(i);
+            }
+        }
+    }
+    p.n = (int)index.size();
+    out.assign((size_t)N, 0);
+    if (resident) {
+        if (msorb_frame_pose_inertial_optimization(resident, &p, has.data(), pos.data(), closeN.data(), pFrame->mvInvLevelSigma2.data(),
+                                                   (int)pFrame->mvInvLevelSigma2.size(), out.data(), &r) != MSORB_OK)
+            fail_call("msorb_frame_pose_inertial_optimization");
+        for (int i : index) pFrame->mvbOutlier[i] = out[i] != 0;
+    } else {
+        const size_t m = index.size();
+        xy.resize(2 * m); ur.resize(m); inv.resize(m); close.resize(m);
+        for (size_t k = 0; k < m; k++) {
+            const int i = index[k];
+            const auto& kpUn = pFrame->mvKeysUn[i];                                                      // :4486, :4519
+            xy[2 * k] = kpUn.pt.x; xy[2 * k + 1] = kpUn.pt.y;
+            ur[k] = pFrame->mvuRight[i];                                                                 // :4482, :4520
+            inv[k] = pFrame->mvInvLevelSigma2[kpUn.octave];                                              // :4502 (uncertainty2 == 1 for Pinhole)
+            close[k] = closeN[i];
+            pos[3 * k] = pos[3 * (size_t)i]; pos[3 * k + 1] = pos[3 * (size_t)i + 1]; pos[3 * k + 2] = pos[3 * (size_t)i + 2];   // (k <= i)
+        }
+        const int off[2] = {0, (int)m};
+        if (msorb_pose_inertial_optimization_batch(device, 1, &p, off, xy.data(), ur.data(), inv.data(), pos.data(), close.data(), out.data(), &r,
+                                                   nullptr) != MSORB_OK)
+            fail_call("msorb_pose_inertial_optimization_batch");
+        for (size_t k = 0; k < m; k++) pFrame->mvbOutlier[index[k]] = out[k] != 0;
+    }
+    typedef typename std::decay<decltype(pFrame->GetImuRotation())>::type RotF;
+    typedef typename std::decay<decltype(pFrame->GetImuPosition())>::type VecF;
+    typedef typename std::decay<decltype(pFrame->GetVelocity())>::type VelF;
+    RotF Rf;
+    VecF tf;
+    VelF vf;
+    for (int a = 0; a < 3; a++) {
+        for (int b = 0; b < 3; b++) Rf(a, b) = r.Rwb_f[3 * a + b];
+        tf(a) = r.twb_f[a];
+        vf(a) = r.v_f[a];
+    }
+    pFrame->SetImuPoseVelocity(Rf, tf, vf);                                                              // :4736-4737
+    typedef typename std::decay<decltype(pFrame->mImuBias)>::type BiasT;
+    pFrame->mImuBias = BiasT((float)r.est.ba[0], (float)r.est.ba[1], (float)r.est.ba[2], (float)r.est.bg[0], (float)r.est.bg[1],
+                             (float)r.est.bg[2]);                                                        // :4738-4740
+    typedef typename std::remove_pointer<typename std::decay<decltype(pFrame->mpcpi)>::type>::type ConstraintT;
+    typedef typename std::decay<decltype(ConstraintT::Rwb)>::type RotD;
+    typedef typename std::decay<decltype(ConstraintT::twb)>::type VecD;
+    typedef typename std::decay<decltype(ConstraintT::H)>::type HessD;
+    RotD Rd;
+    VecD td, vd, bgd, bad;
+    HessD Hd;
+    for (int a = 0; a < 3; a++) {
+        for (int b = 0; b < 3; b++) Rd(a, b) = r.est.Rwb[3 * a + b];
+        td(a) = r.est.twb[a]; vd(a) = r.est.v[a]; bgd(a) = r.est.bg[a]; bad(a) = r.est.ba[a];
+    }
+    for (int a = 0; a < 15; a++)
+        for (int b = 0; b < 15; b++) Hd(a, b) = r.H_prior[15 * a + b];
+    pFrame->mpcpi = new ConstraintT(Rd, td, vd, bgd, bad, Hd);                                           // :4775-4776
+    pFrame->mpcpi->H = Hd;                                                                               // (the constructor clipped it once more)
+    if (form == 1) {
+        delete pFp->mpcpi;                                                                               // :5168-5169
+        pFp->mpcpi = NULL;
+    }
+    return r.n_initial - r.n_bad;                                                                        // :4778
+}
+}  // namespace pose_inertial_detail
+
+template <class FrameT>
+int PoseInertialOptimizationLastKeyFrame(FrameT* pFrame, msorb_frame* resident, bool bRecInit = false, int device = 0) {
+    return pose_inertial_detail::Run(pFrame, 0, resident, bRecInit, device);
+}
+template <class FrameT>
+int PoseInertialOptimizationLastKeyFrame(FrameT* pFrame, bool bRecInit = false) {
+    return pose_inertial_detail::Run(pFrame, 0, static_cast<msorb_frame*>(nullptr), bRecInit, 0);
+}
+template <class FrameT>
+int PoseInertialOptimizationLastFrame(FrameT* pFrame, msorb_frame* resident, bool bRecInit = false, int device = 0) {
+    return pose_inertial_detail::Run(pFrame, 1, resident, bRecInit, device);
+}
+template <class FrameT>
+int PoseInertialOptimizationLastFrame(FrameT* pFrame, bool bRecInit = false) {
+    return pose_inertial_detail::Run(pFrame, 1, static_cast<msorb_frame*>(nullptr), bRecInit, 0);
 }
 
 }  // namespace msorb_host

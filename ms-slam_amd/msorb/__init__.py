@@ -588,6 +588,11 @@ class Frame:
         """msorb_frame_pose_optimization (Optimizer::PoseOptimization of this frame): see _frame_pose_optimization"""
         return _frame_pose_optimization(self, q, t, cam, has_point, pos_w, inv_level_sigma2, outlier)
 
+    def pose_inertial_optimization(self, problem, has_point, pos_w, close, inv_level_sigma2, outlier=None):
+        """msorb_frame_pose_inertial_optimization (Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame of this frame): see
+        frame_pose_inertial_optimization"""
+        return frame_pose_inertial_optimization(self, problem, has_point, pos_w, close, inv_level_sigma2, outlier)
+
 
 def _sim3_side(p):
     return [_c(p["valid"], np.uint8), _c(p["u"], np.float32), _c(p["v"], np.float32), _c(p["level"], np.int32),
@@ -2513,3 +2518,79 @@ def inertial_optimization(problem, keyframes, edges, device=0, timing=False, v_o
     if timing:
         r["elapsed_ms"] = ms.value
     return r
+
+
+# ---- Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_pose_inertial_optimization_capacity", "msorb_pose_inertial_optimization_batch",
+                     "msorb_frame_pose_inertial_optimization")
+
+POSE_INERTIAL_STATE_DTYPE = np.dtype([("Rwb", "<f8", 9), ("twb", "<f8", 3), ("v", "<f8", 3), ("bg", "<f8", 3),
+                                      ("ba", "<f8", 3)])                                         # msorb_pose_inertial_state
+POSE_INERTIAL_PROBLEM_DTYPE = np.dtype([("form", "<i4"), ("rec_init", "<i4"), ("n", "<i4"), ("reserved", "<i4"),
+                                        ("frame", POSE_INERTIAL_STATE_DTYPE), ("other", POSE_INERTIAL_STATE_DTYPE),
+                                        ("prior", POSE_INERTIAL_STATE_DTYPE), ("Rcw", "<f8", 9), ("tcw", "<f8", 3),
+                                        ("Rcb", "<f8", 9), ("tcb", "<f8", 3), ("tbc", "<f8", 3), ("fx", "<f4"), ("fy", "<f4"),
+                                        ("cx", "<f4"), ("cy", "<f4"), ("mbf", "<f4"), ("reserved_f", "<f4"),
+                                        ("pre", INERTIAL_EDGE_DTYPE), ("info_gyro", "<f8", 9), ("info_acc", "<f8", 9),
+                                        ("H", "<f8", 225)])                                      # msorb_pose_inertial_problem
+POSE_INERTIAL_RESULT_DTYPE = np.dtype([("est", POSE_INERTIAL_STATE_DTYPE), ("Rwb_f", "<f4", 9), ("twb_f", "<f4", 3),
+                                       ("v_f", "<f4", 3), ("n_initial", "<i4"), ("n_bad", "<i4"), ("n_inliers", "<i4"),
+                                       ("iterations", "<i4", 4), ("solve_failed", "<i4", 4), ("H_raw", "<f8", 900),
+                                       ("H_prior", "<f8", 225)])                                 # msorb_pose_inertial_result
+assert (POSE_INERTIAL_STATE_DTYPE.itemsize, POSE_INERTIAL_PROBLEM_DTYPE.itemsize, POSE_INERTIAL_RESULT_DTYPE.itemsize) == (168, 3632, 9272)
+
+
+def _pose_inertial_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_pose_inertial_optimization_capacity.argtypes = []
+    L.msorb_pose_inertial_optimization_batch.argtypes = [ci, ci] + [vp] * 10
+    L.msorb_frame_pose_inertial_optimization.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp]
+    return L
+
+
+def pose_inertial_optimization_capacity():
+    """observations up to which the kernel keeps a problem in registers"""
+    return _pose_inertial_lib().msorb_pose_inertial_optimization_capacity()
+
+
+def pose_inertial_optimization_batch(problems, xy, u_right, inv_sigma2, pos_w, close, device=0, timing=False):
+    """msorb_pose_inertial_optimization_batch: Optimizer::PoseInertialOptimizationLastKeyFrame (form 0) / LastFrame (form 1) of
+    every problem in one launch.  problems: POSE_INERTIAL_PROBLEM_DTYPE records whose n partition the flat arrays xy [M, 2],
+    u_right [M], inv_sigma2 [M], pos_w [M, 3], close [M] in order.
+    -> (results: POSE_INERTIAL_RESULT_DTYPE [n_problems], outlier: bool [M]) and, with timing, the kernel's device time in ms."""
+    L = _pose_inertial_lib()
+    pr = _c(problems, POSE_INERTIAL_PROBLEM_DTYPE).reshape(-1)
+    off = np.zeros(len(pr) + 1, np.int32)
+    off[1:] = np.cumsum(pr["n"])
+    m = int(off[-1])
+    arrs = [_c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1),
+            _c(pos_w, np.float32).reshape(-1), _c(close, np.uint8).reshape(-1)]
+    if [len(a) for a in arrs] != [2 * m, m, m, 3 * m, m]:
+        raise ValueError("the flat arrays do not hold sum(problems.n) observations")
+    res = np.zeros(len(pr), POSE_INERTIAL_RESULT_DTYPE)
+    out = np.zeros(max(m, 1), np.uint8)
+    ms = C.c_float()
+    _check(L.msorb_pose_inertial_optimization_batch(device, len(pr), _np_ptr(pr), _np_ptr(off), *[_np_ptr(a) for a in arrs],
+                                                    _np_ptr(out), _np_ptr(res), C.addressof(ms)),
+           "msorb_pose_inertial_optimization_batch")
+    return (res, out[:m].astype(bool), ms.value) if timing else (res, out[:m].astype(bool))
+
+
+def frame_pose_inertial_optimization(frame, problem, has_point, pos_w, close, inv_level_sigma2, outlier=None):
+    """msorb_frame_pose_inertial_optimization: the same routine over the keypoint table resident on the frame handle (keypoints,
+    mvuRight and octaves are the handle's; rectified input).  problem: one POSE_INERTIAL_PROBLEM_DTYPE record (its n is ignored);
+    has_point [N], pos_w [N, 3], close [N].
+    -> (POSE_INERTIAL_RESULT_DTYPE record, outlier uint8 [N]: written where has_point is set, the rest as passed in / zero)"""
+    L = _pose_inertial_lib()
+    pr = _c(problem, POSE_INERTIAL_PROBLEM_DTYPE).reshape(-1)
+    hp, pw, cl, inv = (_c(has_point, np.uint8), _c(pos_w, np.float32).reshape(-1), _c(close, np.uint8),
+                       _c(inv_level_sigma2, np.float32))
+    if len(pr) != 1 or len(hp) != frame.n or len(pw) != 3 * frame.n or len(cl) != frame.n:
+        raise ValueError("one problem record and has_point / pos_w / close of the frame's keypoints are needed")
+    out = np.zeros(max(frame.n, 1), np.uint8) if outlier is None else outlier
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and len(out) >= frame.n
+    res = np.zeros(1, POSE_INERTIAL_RESULT_DTYPE)
+    _check(L.msorb_frame_pose_inertial_optimization(frame.h, _np_ptr(pr), _np_ptr(hp), _np_ptr(pw), _np_ptr(cl), _np_ptr(inv),
+                                                    len(inv), _np_ptr(out), _np_ptr(res)), "msorb_frame_pose_inertial_optimization")
+    return res[0], out[:frame.n]
