@@ -292,6 +292,14 @@ int msorb_debug_fast_thread_table(int rows, int cols, int nfeatures, float scale
  * glibc sinf / cosf restatement can be held to the installed libm (inside the extractor a and b are seen only through the rounded
  * tap positions).  Appended to ABI 6002: MSORB_ABI_VERSION is unchanged, a caller that needs the entry asks the loader for it. */
 int msorb_debug_cos_sin(int device, const float* angles_deg, int n, float* cos_out, float* sin_out);
+/* One shared Lie-group primitive of the optimisers (the rotation arithmetic of se3_device.h, sim3_opt_device.h, essential_graph_device.h,
+ * essential_graph4_device.h, inertial_device.h and mlpnp_device.h), ALONE, on n <= 2^20 explicit records: the functions the
+ * optimisation kernels call, compiled with the library's flags against the device's libm.  op (0..21) and the record layouts are
+ * listed in ms-slam_amd/csrc/lie_probe_device.h: 16 doubles in (80 for op 16, bias_corrected) and 24 doubles out per record, float
+ * functions taking exactly representable floats and returning floats widened.  MSORB_E_INVALID, with out untouched, for a null
+ * pointer with n > 0, a negative n or an unknown op; n == 0 launches nothing.  Two calls on the same input return the same bits.
+ * Appended to ABI 6002: MSORB_ABI_VERSION is unchanged, a caller that needs the entry asks the loader for it. */
+int msorb_debug_lie(int device, int op, const double* in, int n, double* out);
 /* Host-only: DistributeOctTree (ORBextractor.cc:555-779) on explicit candidates; writes the indices of
  * the kept candidates in result order.  Needs no GPU. */
 int msorb_distribute_quadtree(const uint16_t* xs, const uint16_t* ys, const uint16_t* scores, int n, int min_x,

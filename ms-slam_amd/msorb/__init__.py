@@ -390,6 +390,31 @@ def debug_cos_sin(angles_deg, device=0):
     return a, b
 
 
+EXPORTS = EXPORTS + ("msorb_debug_lie",)
+LIE_IN, LIE_OUT = 16, 24   # doubles per record of msorb_debug_lie (ms-slam_amd/csrc/lie_probe_device.h)
+LIE_OPS = ("rotate", "normalize_rotation", "quaternion_of_matrix", "se3_exp", "oplus", "huber", "sim3_exp", "sim3_mul", "sim3_inverse",
+           "lu3_solve", "sim3_log", "normalize_rotation_eg4", "exp_so3", "log_so3", "normalize_rotation_f", "so3f_exp_matrix",
+           "bias_corrected", "right_jacobian_so3", "inverse_right_jacobian_so3", "mlpnp_nearest_rotation", "mlpnp_rodrigues2rot",
+           "mlpnp_rot2rodrigues")
+
+
+def lie_in_width(op):
+    """doubles one record of `op` reads: 16, and five records for bias_corrected"""
+    return LIE_IN * (5 if LIE_OPS[op] == "bias_corrected" else 1)
+
+
+def debug_lie(op, records, device=0):
+    """msorb_debug_lie: one shared Lie-group primitive (op: an index or a name of LIE_OPS) alone on the device, float64
+    [n, lie_in_width(op)] -> float64 [n, 24]."""
+    op = LIE_OPS.index(op) if isinstance(op, str) else int(op)
+    rec = np.ascontiguousarray(records, np.float64).reshape(-1, lie_in_width(op))
+    out = np.zeros((len(rec), LIE_OUT), np.float64)
+    L = lib()
+    L.msorb_debug_lie.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    _check(L.msorb_debug_lie(device, op, _np_ptr(rec), len(rec), _np_ptr(out)), "msorb_debug_lie")
+    return out
+
+
 def keypoints_from_device(d_kps, counts):
     """torch uint8 [n, cap, 28] -> list of numpy KP_DTYPE arrays."""
     host = d_kps.cpu().numpy()
