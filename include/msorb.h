@@ -1025,6 +1025,11 @@ int msorb_three_maxima(const int* bin_sizes, int n_bins, int* ind);
  * variable (th_grid: binary, cost GridLambda; th: integer 0..1000, cost Lambda) — see INTEGRATION.md for the
  * GUROBI C-API mapping.  n_max_obs_floor: max Observations() over map points of window keyframes that are in
  * no grid cell (normally 0).
+ * The caller's contract for obs_kf: the list of a point holds a keyframe id AT MOST ONCE, as the reference's
+ * std::map<KeyFrame, ...> of GetObservations() does.  It is not checked.  An id listed twice would be counted
+ * twice in the row's rhs and appear once in col_idx (one bit per column in the row's bitmap), so that
+ * row_begin and col_idx disagree.  A point MAY sit in several slots of one keyframe or cell: its column opens
+ * once and every slot is a term of the cell row and of the keyframe row, as :100-107 add them.
  * ---------------------------------------------------------------------------------------------- */
 int msorb_visibility_csr(int device, int n_window_kf, const int* kf_slot_begin, const int* slot_point,
                          const int* slot_cell, int n_points, const int* point_nobs, const int* obs_begin,
