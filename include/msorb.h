@@ -300,6 +300,17 @@ int msorb_debug_cos_sin(int device, const float* angles_deg, int n, float* cos_o
  * pointer with n > 0, a negative n or an unknown op; n == 0 launches nothing.  Two calls on the same input return the same bits.
  * Appended to ABI 6002: MSORB_ABI_VERSION is unchanged, a caller that needs the entry asks the loader for it. */
 int msorb_debug_lie(int device, int op, const double* in, int n, double* out);
+/* One small dense decomposition of the RANSAC solvers and optimisers (the 3x3 SVD, inverse and determinant and the 9-column null
+ * vector of two_view_device.h, the 4x4 null vector of new_points_device.h, the 4x4 eigenvector and quaternion rotation of
+ * sim3_device.h, the rank, eigenvectors, 6x6 solve and 12 / 9-column null vector of mlpnp_device.h, ldlt_factor / ldlt_apply of
+ * inertial_device.h), ALONE, on n <= 2^20 explicit records: the functions the kernels call, compiled with the library's flags.  The
+ * one-thread routines run a thread per record; the two cooperative null vectors run a workgroup per record, of the size and on the
+ * shared work of the kernel that calls them, and report how many lanes returned other bits than lane 0.  op (0..13), the record
+ * widths and layouts are listed in ms-slam_amd/csrc/decomp_probe_device.h; 24 doubles out per record, float functions taking exactly
+ * representable floats and returning floats widened.  MSORB_E_INVALID, with out untouched, for a null pointer with n > 0, a negative
+ * n or an unknown op; n == 0 launches nothing.  Two calls on the same input return the same bits.
+ * Appended to ABI 6002: MSORB_ABI_VERSION is unchanged, a caller that needs the entry asks the loader for it. */
+int msorb_debug_decomp(int device, int op, const double* in, int n, double* out);
 /* Host-only: DistributeOctTree (ORBextractor.cc:555-779) on explicit candidates; writes the indices of
  * the kept candidates in result order.  Needs no GPU. */
 int msorb_distribute_quadtree(const uint16_t* xs, const uint16_t* ys, const uint16_t* scores, int n, int min_x,

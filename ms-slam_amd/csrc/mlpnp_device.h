@@ -317,6 +317,47 @@ NP_HD double mlpnp_direction_error(const MlpnpWork& w, const double* R, const do
     return sum;
 }
 
+// The right singular vector of the smallest singular value of the symmetric nc x nc matrix in w.W (nc = 12 or 9; W filled, V the
+// identity, both synchronised by the caller): x[0..nc) = that column of V, x[nc..12) = 0.  Every lane returns the same x.
+NP_HD void mlpnp_null_vector(MlpnpWork& w, int lane, int stride, int nc, double* x) {
+    // :566-567 the cyclic Jacobi iteration: the rotation's c, s on every lane, row / column k of W and row k of V on lane k
+    double max_diag = fabs(w.W[0][0]);
+    for (int i = 1; i < nc; i++) if (fabs(w.W[i][i]) > max_diag) max_diag = fabs(w.W[i][i]);
+    for (int sweep = 0; sweep < kMlpnpMaxSweeps; sweep++) {
+        bool finished = true;
+        for (int p = 0; p < nc - 1; p++)
+            for (int q = p + 1; q < nc; q++) {
+                const double apq = w.W[p][q], thr = np_dmul(np_dmul(2.0, kMlpnpEps), max_diag);
+                if (!(fabs(apq) > (thr > kMlpnpTiny ? thr : kMlpnpTiny))) continue;   // the same on every lane
+                finished = false;
+                const double app = w.W[p][p], aqq = w.W[q][q];
+                double c, s, tt;
+                mp_jacobi(app, aqq, apq, c, s, tt);
+                const double npp = np_dsub(app, np_dmul(tt, apq)), nqq = np_dadd(aqq, np_dmul(tt, apq));
+                MLPNP_SYNC();
+                for (int k = lane; k < nc; k += stride) {
+                    if (k == p) { w.W[p][p] = npp; w.W[p][q] = 0.0; }
+                    else if (k == q) { w.W[q][q] = nqq; w.W[q][p] = 0.0; }
+                    else {
+                        const double akp = w.W[k][p], akq = w.W[k][q];
+                        const double nkp = np_dsub(np_dmul(c, akp), np_dmul(s, akq)), nkq = np_dadd(np_dmul(s, akp), np_dmul(c, akq));
+                        w.W[k][p] = nkp; w.W[p][k] = nkp; w.W[k][q] = nkq; w.W[q][k] = nkq;
+                    }
+                    const double vkp = w.V[k][p], vkq = w.V[k][q];
+                    w.V[k][p] = np_dsub(np_dmul(c, vkp), np_dmul(s, vkq));
+                    w.V[k][q] = np_dadd(np_dmul(s, vkp), np_dmul(c, vkq));
+                }
+                MLPNP_SYNC();
+                if (fabs(npp) > max_diag) max_diag = fabs(npp);
+                if (fabs(nqq) > max_diag) max_diag = fabs(nqq);
+            }
+        if (finished) break;
+    }
+    int col = 0;
+    for (int i = 1; i < nc; i++) if (fabs(w.W[i][i]) < fabs(w.W[col][col])) col = i;
+    for (int k = 0; k < 12; k++) x[k] = k < nc ? w.V[k][col] : 0.0;
+}
+
 // computePose (:399-701) of the correspondences set[0..5] of a problem: cam = fx, fy, cx, cy; p2d (2 floats) and p3d (3 floats) per
 // correspondence.  R (row major), t: the result block; returns the flags.  Every lane returns the same values.
 NP_HD unsigned mlpnp_compute_pose(MlpnpWork& w, int lane, int stride, const float* cam, const float* p2d, const float* p3d, const int* set,
@@ -383,43 +424,8 @@ NP_HD unsigned mlpnp_compute_pose(MlpnpWork& w, int lane, int stride, const floa
         w.V[a][b] = a == b ? 1.0 : 0.0;
     }
     MLPNP_SYNC();
-    // :566-567 the cyclic Jacobi iteration: the rotation's c, s on every lane, row / column k of W and row k of V on lane k
-    double max_diag = fabs(w.W[0][0]);
-    for (int i = 1; i < nc; i++) if (fabs(w.W[i][i]) > max_diag) max_diag = fabs(w.W[i][i]);
-    for (int sweep = 0; sweep < kMlpnpMaxSweeps; sweep++) {
-        bool finished = true;
-        for (int p = 0; p < nc - 1; p++)
-            for (int q = p + 1; q < nc; q++) {
-                const double apq = w.W[p][q], thr = np_dmul(np_dmul(2.0, kMlpnpEps), max_diag);
-                if (!(fabs(apq) > (thr > kMlpnpTiny ? thr : kMlpnpTiny))) continue;   // the same on every lane
-                finished = false;
-                const double app = w.W[p][p], aqq = w.W[q][q];
-                double c, s, tt;
-                mp_jacobi(app, aqq, apq, c, s, tt);
-                const double npp = np_dsub(app, np_dmul(tt, apq)), nqq = np_dadd(aqq, np_dmul(tt, apq));
-                MLPNP_SYNC();
-                for (int k = lane; k < nc; k += stride) {
-                    if (k == p) { w.W[p][p] = npp; w.W[p][q] = 0.0; }
-                    else if (k == q) { w.W[q][q] = nqq; w.W[q][p] = 0.0; }
-                    else {
-                        const double akp = w.W[k][p], akq = w.W[k][q];
-                        const double nkp = np_dsub(np_dmul(c, akp), np_dmul(s, akq)), nkq = np_dadd(np_dmul(s, akp), np_dmul(c, akq));
-                        w.W[k][p] = nkp; w.W[p][k] = nkp; w.W[k][q] = nkq; w.W[q][k] = nkq;
-                    }
-                    const double vkp = w.V[k][p], vkq = w.V[k][q];
-                    w.V[k][p] = np_dsub(np_dmul(c, vkp), np_dmul(s, vkq));
-                    w.V[k][q] = np_dadd(np_dmul(s, vkp), np_dmul(c, vkq));
-                }
-                MLPNP_SYNC();
-                if (fabs(npp) > max_diag) max_diag = fabs(npp);
-                if (fabs(nqq) > max_diag) max_diag = fabs(nqq);
-            }
-        if (finished) break;
-    }
-    int col = 0;
-    for (int i = 1; i < nc; i++) if (fabs(w.W[i][i]) < fabs(w.W[col][col])) col = i;
     double x[12];
-    for (int k = 0; k < 12; k++) x[k] = k < nc ? w.V[k][col] : 0.0;
+    mlpnp_null_vector(w, lane, stride, nc, x);
     // :573-680 the rotation nearest to the estimate and the disambiguation over the six points
     double Rout[9], tout[3];
     if (planar) {

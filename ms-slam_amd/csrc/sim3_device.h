@@ -24,8 +24,10 @@ struct Sim3Transform {
 // (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), a pair rotated when |A(p,q)| > max(FLT_MIN, 2 eps max|A(i,i)|), with
 //   tau = (A(q,q) - A(p,p)) / (2 A(p,q)),  t = 1 / (tau +- sqrt(tau^2 + 1)) (the sign of tau),  c = 1 / sqrt(t^2 + 1),  s = t c,
 // sweeps until one passes without a rotation or kSim3MaxSweeps are done.  The eigenvalue is the first maximum of the diagonal
-// (maxCoeff, :439); the vector's sign is whatever the rotations leave: q and -q are one rotation.  A non-finite A rotates nothing
-// (every comparison is false) and returns the first unit vector.
+// (maxCoeff, :439); the vector's sign is whatever the rotations leave: q and -q are one rotation.  An A whose entries are all
+// infinite (or all NaN) rotates nothing (every comparison is false) and returns the first unit vector.  A single NaN or infinity
+// does not stop the pairs it is not in (np_max keeps a NaN out of max_diag) and spreads through the rows they rotate; q is then
+// whatever column the comparisons, false against a NaN, leave as the first maximum, and may be finite.
 NP_HD void sim3_largest_eigenvector(const float* A, float* q) {
     const float tiny = 1.17549435e-38f, precision = 2.384185791015625e-07f;   // FLT_MIN, 2 * FLT_EPSILON
     float W[4][4], V[4][4];

@@ -181,8 +181,24 @@ NP_UNROLL
 //   tau = (beta - alpha) / (2 gamma),  t = 1 / (tau +- sqrt(tau^2 + 1)) (the sign of tau),  c = 1 / sqrt(t^2 + 1),  s = t c,
 //   a_p <- c a_p - s a_q,  a_q <- s a_p + c a_q,  the same on V's columns.
 // Sweeps until one passes without a rotation or kTvMaxSweeps are done.  x = the column of V whose column of A has the smallest norm
-// (the first minimum).  A non-finite A rotates nothing and returns the first unit vector that holds a minimum.  The sign of x is
-// whatever the rotations leave.  Every lane returns the same x; w may be reused after the closing TV_SYNC.
+// (the first minimum).  The sign of x is whatever the rotations leave.  Every lane returns the same x; w may be reused after the
+// closing TV_SYNC.
+//
+// Non-finite input: a column that holds a NaN is never rotated (its alpha, and every gamma against it, fails the comparisons; np_max
+// keeps it out of max_norm); the other columns rotate among themselves as usual and x comes from them, finite, unless the NaN is in
+// column 0, whose NaN norm no later one compares below: then x is the first unit vector.  One infinity makes max_norm and the floor
+// infinite: nothing rotates and x is the unit vector of the first smallest column (the first unit vector for an all-infinite A).
+// A NaN in A therefore does not show as a NaN in x.
+//
+// Domain.  With N the largest column norm of A at entry, the rotation test is the relative one stated above while
+// 2^-12 <= N <= 2^30: alpha beta is formed in float, every column the floor admits has alpha > 2^-38 N^2, so alpha beta > 2^-76 N^4
+// >= FLT_MIN, and no column outgrows the Frobenius norm <= 3 N, so alpha beta <= 81 N^4 < FLT_MAX.  The callers are inside it:
+// Normalize leaves mean deviation 1 per coordinate, so the column of ones has norm sqrt(8) and a coordinate is at most n / 2 for n
+// matches (mean deviation >= 2 |x_i - mean| / n), n <= 32 768: entries up to 2^28, N <= 2^29.5.  Outside (tests/decomp_cases.py
+// walks it): down to N ~ 2^-31 and up to 2^31 random matrices still give the same bits scaled; from 2^-36 to 2^-54 alpha beta
+// underflows, the threshold is FLT_MIN alone, rounding noise keeps rotating and the sweeps run to kTvMaxSweeps, x still accurate;
+// below 2^-56 x loses accuracy; below 2^-62 (gamma < FLT_MIN) and above 2^33 (alpha beta overflows, the threshold is infinite)
+// nothing rotates and x is the unit vector of the first smallest column of A as given.
 NP_HD void tv_null_vector(TvWork& w, int lane, int stride, int rows, float* x) {
     const float tiny = 1.17549435e-38f, precision = 2.384185791015625e-07f;   // FLT_MIN, 2 * FLT_EPSILON
     const float floor_rel = 3.63797880709171295e-12f;                          // (16 * FLT_EPSILON)^2 = 2^-38

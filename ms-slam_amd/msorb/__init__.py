@@ -415,6 +415,27 @@ def debug_lie(op, records, device=0):
     return out
 
 
+EXPORTS = EXPORTS + ("msorb_debug_decomp",)
+DECOMP_OUT = 24   # doubles out per record of msorb_debug_decomp (ms-slam_amd/csrc/decomp_probe_device.h)
+DECOMP_OPS = ("tv_inverse3", "tv_det3", "tv_svd3", "tv_null_vector_8", "tv_null_vector_16", "np_null_vector", "sim3_largest_eigenvector",
+              "sim3_rotation_of_quaternion", "mlpnp_rank3", "mlpnp_eig3", "mlpnp_solve6", "mlpnp_null_vector_12", "mlpnp_null_vector_9",
+              "inertial_ldlt")
+DECOMP_IN = (9, 9, 9, 72, 144, 16, 16, 4, 9, 9, 42, 144, 81, 91)   # doubles in per record, by op
+DECOMP_MISMATCH = {"tv_null_vector_8": 9, "tv_null_vector_16": 9, "mlpnp_null_vector_12": 12, "mlpnp_null_vector_9": 12}
+
+
+def debug_decomp(op, records, device=0):
+    """msorb_debug_decomp: one small dense decomposition (op: an index or a name of DECOMP_OPS) alone on the device, float64
+    [n, DECOMP_IN[op]] -> float64 [n, 24].  The cooperative ops keep, at DECOMP_MISMATCH[name], how many lanes differed from lane 0."""
+    op = DECOMP_OPS.index(op) if isinstance(op, str) else int(op)
+    rec = np.ascontiguousarray(records, np.float64).reshape(-1, DECOMP_IN[op])
+    out = np.zeros((len(rec), DECOMP_OUT), np.float64)
+    L = lib()
+    L.msorb_debug_decomp.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    _check(L.msorb_debug_decomp(device, op, _np_ptr(rec), len(rec), _np_ptr(out)), "msorb_debug_decomp")
+    return out
+
+
 def keypoints_from_device(d_kps, counts):
     """torch uint8 [n, cap, 28] -> list of numpy KP_DTYPE arrays."""
     host = d_kps.cpu().numpy()
