@@ -1500,6 +1500,62 @@ int msorb_frame_pose_inertial_optimization(msorb_frame* f, const msorb_pose_iner
                                            const float* pos_w, const uint8_t* close, const float* inv_level_sigma2, int nlevels,
                                            uint8_t* outlier, msorb_pose_inertial_result* r);
 
+/* Optimizer::LocalInertialBA (src/Optimizer.cc:2431-2973) after its gathering loops, on the device, for pinhole KeyFrames without a
+ * second camera (the mpCamera2 arm of :2820-2853 is not restated; FullInertialBA and MergeInertialBA are not either): EdgeMono /
+ * EdgeStereo over ImuCamPose and the points, EdgeInertial, EdgeGyroRW and EdgeAccRW along the chain of KeyFrames, g2o's Levenberg
+ * with setUserLambdaInit, the points eliminated by the Schur complement, in double with the preintegration's bias correction in
+ * float as the reference has it.  The whole optimize() is ONE launch of one workgroup.  Appended to ABI 6002: MSORB_ABI_VERSION
+ * stays 6002.
+ * problem: large = bLarge: lambda 1e-2 and 4 iterations against 1e0 and 10 (:2435-2440, :2547-2555), and no FAIL rule;
+ * iterations > 0 replaces the 4 / 10.
+ * kfs [n_kf]: everything VertexPose(pKF) / ImuCamPose(pKF) reads, in the conventions of msorb_pose_inertial_problem: Rcw / tcw =
+ * GetPose() widened, not derived.  kind: 0 = free, with pose, velocity and both biases (15 unknowns); 1 = fixed, with inertial
+ * vertices (the KeyFrame before the window, or the window's oldest without mPrevKF); 2 = fixed pose only.  A free KeyFrame without
+ * inertial vertices cannot be stated: the caller does not hand such a window over.
+ * iedges [n_inertial]: pre.kf_prev / pre.kf_cur index kfs; pre.info = the full 9x9 of EdgeInertial's constructor; info_gyro /
+ * info_acc (:2673, :2680) row major; huber: RobustKernelHuber of delta sqrt(16.92) (:2657-2667); downweight: information() *
+ * 1e-2, applied in double inside the library (:2665).  One incoming and one outgoing edge per KeyFrame, no cycle: anything else
+ * is MSORB_E_CAPACITY, as are more free KeyFrames than msorb_local_inertial_ba_capacity().  An edge between two fixed KeyFrames
+ * is not active.
+ * Visual edges: msorb_local_ba's arrays in point-major order; u_right >= 0 = EdgeStereo, else EdgeMono (cam_idx 0); inv_sigma2 =
+ * mvInvLevelSigma2[octave] / unc2 as the float the host divides (:2771-2773); point_close [n_points] = mTrackDepth < 10.f.
+ * Result: status 0 = optimised; 1 = the FAIL rule of :2911 held; 2 = no free KeyFrame and no edge.  chi2_initial / chi2_final =
+ * the two activeRobustChi2 of :2865 / :2867, err / err_end their float narrowings.  chi2_final and every edge's chi2 of the
+ * classification (:2876-2904, which reads chi2() without computeError()) belong to the state the LAST TRIAL wrote, accepted or
+ * not; isDepthPositive() reads the returned estimate.  With status 1 or 2 every estimate output repeats its input and no flag is
+ * set.  kf_out [n_kf]: the doubles, and what the setters receive: Rcw / tcw narrowed (SetPose, :2937), v (:2943) and the bias in
+ * IMU::Bias's order, acc then gyro (:2946-2948); a fixed KeyFrame's repeat its input.  pos_out [3 n_points], pos_d (may be NULL),
+ * edge_outlier [n_edges] = vToErase.  No stop flag: the reference installs it after optimize() (:2868-2869).
+ * Errors, before anything is launched and with no output written: MSORB_E_INVALID for a null required pointer, a negative count,
+ * an index out of range, kf_prev == kf_cur, edges that are not point-major, an inertial edge on a kind 2 KeyFrame, a non-finite
+ * input, an unknown kind.  Two calls on the same input return the same bits.  Re-entrant.  *elapsed_ms (may be NULL): device time. */
+typedef struct msorb_iba_problem { int32_t large, iterations, reserved[2]; } msorb_iba_problem;
+typedef struct msorb_iba_keyframe {
+    double Rwb[9], twb[3], v[3], bg[3], ba[3], Rcw[9], tcw[3], Rcb[9], tcb[3], tbc[3];
+    float fx, fy, cx, cy, mbf;
+    int32_t kind;
+} msorb_iba_keyframe;
+typedef struct msorb_iba_inertial_edge {
+    msorb_inertial_edge pre;
+    double info_gyro[9], info_acc[9];
+    int32_t huber, downweight;
+} msorb_iba_inertial_edge;
+typedef struct msorb_iba_keyframe_out {
+    double Rwb[9], twb[3], Rcw[9], tcw[3], v[3], bg[3], ba[3];
+    float Rcw_f[9], tcw_f[3], v_f[3], bias_f[6], reserved_f;
+} msorb_iba_keyframe_out;
+typedef struct msorb_iba_result {
+    int32_t status, iterations, trials, rejected_trials, n_outliers, reserved;
+    double chi2_initial, chi2_final, lambda_final;
+    float err, err_end;
+} msorb_iba_result;
+int msorb_local_inertial_ba_capacity(void);            /* free KeyFrames: 25 */
+int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, int n_kf, const msorb_iba_keyframe* kfs, int n_inertial,
+                            const msorb_iba_inertial_edge* iedges, int n_points, const float* pos_w, const uint8_t* point_close,
+                            int n_edges, const int* edge_kf, const int* edge_point, const float* xy, const float* u_right,
+                            const float* inv_sigma2, msorb_iba_keyframe_out* kf_out, float* pos_out, double* pos_d,
+                            uint8_t* edge_outlier, msorb_iba_result* r, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,11 +19,11 @@
 namespace msorb {
 namespace lm {
 
-struct Counts { int iterations, rejected; double chi2_initial; };
+struct Counts { int iterations, rejected; double chi2_initial; int trials; double lambda; };   // lambda: as the last trial left it
 
 template <typename Linearise, typename Trial, typename Accept>
 SE3_HD Counts levenberg(int max_it, bool user_lambda_init, double user_lambda, Linearise linearise, Trial trial, Accept accept) {
-    Counts n{0, 0, 0.0};
+    Counts n{0, 0, 0.0, 0, 0.0};
     double lambda = 0, ni = 2;
     int n_bad = 0;
     bool ok = true;
@@ -60,6 +60,7 @@ SE3_HD Counts levenberg(int max_it, bool user_lambda_init, double user_lambda, L
                 n.rejected++;
             }
             qmax++;
+            n.trials++;
         } while (rho < 0 && qmax < 10);                                        // :149
         n.iterations++;
         if (qmax == 10 || rho == 0) { ok = false; continue; }                  // :151-155 Terminate
@@ -67,6 +68,7 @@ SE3_HD Counts levenberg(int max_it, bool user_lambda_init, double user_lambda, L
         else n_bad = 0;
         if (n_bad >= 3) ok = false;                                            // :164-167
     }
+    n.lambda = lambda;
     return n;
 }
 

@@ -178,9 +178,11 @@ SE3_HD void hat(const double* v, double* W) {
 
 // EdgeInertial::computeError (G2oTypes.cc:514-534) and linearizeOplus (:536-594) at one estimate: 1 = the other end, 2 = the
 // frame.  The bias of GetDelta* is the other end's estimate narrowed to float; inertial::edge_error is this error with Rwg = I,
-// s = 1.  Writes S.e, S.Oe = Omega e and, with `jac`, the non-zero blocks of S.J (the rest stays zero).
-INERTIAL_OUT_OF_LINE SE3_HD void inertial_terms(const msorb_pose_inertial_problem& P, const Vertices& F, const Vertices& O, bool jac,
-                                                Shared& S) {
+// s = 1.  Of one edge `pre` with its information `info`: writes e, Oe = Omega e and, with `jac`, the non-zero blocks of the
+// caller's J [9][kJc] (the rest stays zero).  LocalInertialBA's edges (local_inertial_ba_device.h) share it with the two
+// tracking forms, whose inertial_terms below hands it the problem's edge and the Shared block.
+SE3_HD void inertial_edge_terms(const msorb_inertial_edge& pre, const double* info, const Vertices& F, const Vertices& O, bool jac,
+                                double* SJ, double* Se, double* SOe) {
     inertial::Globals G;
     for (int q = 0; q < 9; q++) G.Rwg[q] = q % 4 == 0 ? 1.0 : 0.0;
     G.scale = 1.0;
@@ -189,50 +191,54 @@ INERTIAL_OUT_OF_LINE SE3_HD void inertial_terms(const msorb_pose_inertial_proble
     for (int k = 0; k < 3; k++) { k1.twb[k] = O.P.twb[k]; k2.twb[k] = F.P.twb[k]; G.bg[k] = O.bg[k]; G.ba[k] = O.ba[k]; }
     double e[9], Oe[9];
     inertial::EdgeTerms T;
-    inertial::edge_error(P.pre, k1, k2, O.v, F.v, G, e, T);
-    inertial::edge_chi2(P.pre.info, e, Oe);
-    for (int k = 0; k < 9; k++) { S.e[k] = e[k]; S.Oe[k] = Oe[k]; }
+    inertial::edge_error(pre, k1, k2, O.v, F.v, G, e, T);
+    inertial::edge_chi2(info, e, Oe);
+    for (int k = 0; k < 9; k++) { Se[k] = e[k]; SOe[k] = Oe[k]; }
     if (!jac) return;
     const double dt = T.dt, g[3] = {0.0, 0.0, -inertial::gravity_value()};
     double invJr[9], nInv[9], A[9], B[9], W[9], tv[3], tp[3], r[3], Rwb2t[9], eRt[9], RJ[9], JRg[9], w[3];
     inertial::inverse_right_jacobian_so3(e[0], e[1], e[2], invJr);                 // :556
-    for (int q = 0; q < 9; q++) { nInv[q] = -invJr[q]; JRg[q] = (double)P.pre.JRg[q]; }
+    for (int q = 0; q < 9; q++) { nInv[q] = -invJr[q]; JRg[q] = (double)pre.JRg[q]; }
     for (int r_ = 0; r_ < 3; r_++)
         for (int c = 0; c < 3; c++) { Rwb2t[3 * r_ + c] = F.P.Rwb[3 * c + r_]; eRt[3 * r_ + c] = T.eR[3 * c + r_]; }
     mul33(nInv, Rwb2t, A);                                                         // :561
     mul33(A, O.P.Rwb, B);
-    put33(S.J, kJc, 0, 0, B, 1.0);
+    put33(SJ, kJc, 0, 0, B, 1.0);
     for (int k = 0; k < 3; k++) {
         tv[k] = T.dv[k] - g[k] * dt;                                               // :562
         tp[k] = T.dp[k] - ((0.5 * g[k]) * dt) * dt;                                // :563-564
     }
     mul3v(T.Rbw1, tv, r);
     hat(r, W);
-    put33(S.J, kJc, 3, 0, W, 1.0);
+    put33(SJ, kJc, 3, 0, W, 1.0);
     mul3v(T.Rbw1, tp, r);
     hat(r, W);
-    put33(S.J, kJc, 6, 0, W, 1.0);
-    for (int k = 0; k < 3; k++) S.J[(6 + k) * kJc + 3 + k] = -1.0;                 // :566
-    put33(S.J, kJc, 3, 6, T.Rbw1, -1.0);                                           // :570
+    put33(SJ, kJc, 6, 0, W, 1.0);
+    for (int k = 0; k < 3; k++) SJ[(6 + k) * kJc + 3 + k] = -1.0;                 // :566
+    put33(SJ, kJc, 3, 6, T.Rbw1, -1.0);                                           // :570
     for (int q = 0; q < 9; q++) A[q] = -T.Rbw1[q] * dt;                            // :571
-    put33(S.J, kJc, 6, 6, A, 1.0);
+    put33(SJ, kJc, 6, 6, A, 1.0);
     mul3v(JRg, T.dbg, w);                                                          // :575: ((-invJr eR^T) RJ) JRg
     inertial::right_jacobian_so3(w[0], w[1], w[2], RJ);
     mul33(nInv, eRt, A);
     mul33(A, RJ, B);
     mul33(B, JRg, A);
-    put33(S.J, kJc, 0, 9, A, 1.0);
+    put33(SJ, kJc, 0, 9, A, 1.0);
     for (int r_ = 0; r_ < 3; r_++)
         for (int c = 0; c < 3; c++) {
-            S.J[(3 + r_) * kJc + 9 + c] = -(double)P.pre.JVg[3 * r_ + c];          // :576
-            S.J[(6 + r_) * kJc + 9 + c] = -(double)P.pre.JPg[3 * r_ + c];          // :577
-            S.J[(3 + r_) * kJc + 12 + c] = -(double)P.pre.JVa[3 * r_ + c];         // :581
-            S.J[(6 + r_) * kJc + 12 + c] = -(double)P.pre.JPa[3 * r_ + c];         // :582
+            SJ[(3 + r_) * kJc + 9 + c] = -(double)pre.JVg[3 * r_ + c];          // :576
+            SJ[(6 + r_) * kJc + 9 + c] = -(double)pre.JPg[3 * r_ + c];          // :577
+            SJ[(3 + r_) * kJc + 12 + c] = -(double)pre.JVa[3 * r_ + c];         // :581
+            SJ[(6 + r_) * kJc + 12 + c] = -(double)pre.JPa[3 * r_ + c];         // :582
         }
-    put33(S.J, kJc, 0, 15, invJr, 1.0);                                            // :587
+    put33(SJ, kJc, 0, 15, invJr, 1.0);                                            // :587
     mul33(T.Rbw1, F.P.Rwb, A);                                                     // :589
-    put33(S.J, kJc, 6, 18, A, 1.0);
-    put33(S.J, kJc, 3, 21, T.Rbw1, 1.0);                                           // :593
+    put33(SJ, kJc, 6, 18, A, 1.0);
+    put33(SJ, kJc, 3, 21, T.Rbw1, 1.0);                                           // :593
+}
+INERTIAL_OUT_OF_LINE SE3_HD void inertial_terms(const msorb_pose_inertial_problem& P, const Vertices& F, const Vertices& O, bool jac,
+                                                Shared& S) {
+    inertial_edge_terms(P.pre, P.pre.info, F, O, jac, S.J, S.e, S.Oe);
 }
 
 // EdgeGyroRW / EdgeAccRW computeError (G2oTypes.h:645-649, :681-685): S.rw = [Og eg | Oa ea | eg | ea]

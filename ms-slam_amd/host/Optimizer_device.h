@@ -31,6 +31,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <list>
 #include <map>
 #include <memory>
@@ -1624,6 +1625,257 @@ int PoseInertialOptimizationLastFrame(FrameT* pFrame, msorb_frame* resident, boo
 template <class FrameT>
 int PoseInertialOptimizationLastFrame(FrameT* pFrame, bool bRecInit = false) {
     return pose_inertial_detail::Run(pFrame, 1, static_cast<msorb_frame*>(nullptr), bRecInit, 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::LocalInertialBA (src/Optimizer.cc:2431-2973; LocalMapping.cc:150) on msorb_local_inertial_ba.
+//
+//   bool ORB_SLAM3::msorb_host::LocalInertialBA(pKF, pbStopFlag, pMap, num_fixedKF, num_OptKF, num_MPs, num_edges, bLarge, bRecInit)
+//
+// the reference's parameter list (pKF is its shared_ptr<KeyFrame>) and its effects: SetNewBias on the window's preintegrations
+// (:2632), then under mMutexMapUpdate the flagged observations erased, mnBAFixedForKF / mnBALocalForKF reset, SetPose, SetVelocity,
+// SetNewBias, SetWorldPos, UpdateNormalAndDepth, IncreaseChangeIndex (:2907-2972).  On the FAIL rule of :2911 it returns true with
+// nothing written and the marks left as the reference leaves them.  The reference never assigns its four num_* outputs, nor does
+// this.  *pbStopFlag is not read: the reference installs it after optimize() (:2868-2869).
+//
+// false = NOT handled, nothing touched, the caller runs Optimizer::LocalInertialBA: a KeyFrame with mpCamera2 anywhere in the
+// problem (the arm :2820-2853), a window KeyFrame or the KeyFrame before the window that would take one of the reference's error
+// branches (:2627-2630, :2642-2646, :2684-2685: !bImu, no mpImuPreintegrated), a covariance without inverse, more free KeyFrames
+// than msorb_local_inertial_ba_capacity().  The decision falls before the first side effect: the chain is walked without a mark
+// first, and the marks the gathering walk sets are put back before a late `false`; SetNewBias runs after the last check.
+//
+// The KeyFrames are handed over in ascending mnId, which is the order of g2o's unknowns (every free pose, then velocity and
+// biases per KeyFrame).  Pinhole::uncertainty2 is 1.f, so inv_sigma2 is mvInvLevelSigma2[octave] / 1.f (:2771-2773).
+template <class KFPtr, class MPPtr>
+struct LocalInertialBAProblem : BaEdges {
+    std::vector<KFPtr> vpOptimizableKFs;               // newest first, as the reference's
+    std::list<KFPtr> lFixedKeyFrames;
+    std::list<MPPtr> lLocalMapPoints;
+    std::vector<KFPtr> kf_of_index;                    // ascending mnId
+    std::vector<msorb_iba_keyframe> kfs;
+    std::vector<msorb_iba_inertial_edge> iedges;       // in the order of the reference's loop (:2624-2686)
+    std::vector<float> pos_w;
+    std::vector<uint8_t> point_close;
+    std::vector<std::pair<KFPtr, MPPtr>> edge_objects;
+    bool handled = true;
+    std::vector<std::pair<KFPtr, std::pair<unsigned long, unsigned long>>> kf_marks;
+    std::vector<std::pair<MPPtr, unsigned long>> mp_marks;
+    void restore_marks() {
+        for (auto it = kf_marks.rbegin(); it != kf_marks.rend(); ++it) { it->first->mnBALocalForKF = it->second.first; it->first->mnBAFixedForKF = it->second.second; }
+        for (auto it = mp_marks.rbegin(); it != mp_marks.rend(); ++it) it->first->mnBALocalForKF = it->second;
+    }
+};
+
+template <class KFPtr>
+msorb_iba_keyframe IbaKeyFrame(const KFPtr& k, int kind) {
+    msorb_iba_keyframe r;
+    std::memset(&r, 0, sizeof r);
+    const auto Tcw = k->GetPose();                                                                       // G2oTypes.cc:95-100
+    const auto Rcw = Tcw.rotationMatrix();
+    const auto tcw = Tcw.translation();
+    const auto Rwb = k->GetImuRotation();
+    const auto twb = k->GetImuPosition();
+    const auto Rcb = k->mImuCalib.mTcb.rotationMatrix();
+    const auto tcb = k->mImuCalib.mTcb.translation();
+    const auto tbc = k->mImuCalib.mTbc.translation();
+    for (int a = 0; a < 3; a++) {
+        for (int b = 0; b < 3; b++) { r.Rwb[3 * a + b] = (double)Rwb(a, b); r.Rcw[3 * a + b] = (double)Rcw(a, b); r.Rcb[3 * a + b] = (double)Rcb(a, b); }
+        r.twb[a] = (double)twb(a); r.tcw[a] = (double)tcw(a); r.tcb[a] = (double)tcb(a); r.tbc[a] = (double)tbc(a);
+    }
+    if (kind != 2) {                                                                                     // VertexVelocity / GyroBias / AccBias(pKF)
+        const auto v = k->GetVelocity();
+        const auto bg = k->GetGyroBias();
+        const auto ba = k->GetAccBias();
+        for (int a = 0; a < 3; a++) { r.v[a] = (double)v(a); r.bg[a] = (double)bg(a); r.ba[a] = (double)ba(a); }
+    }
+    r.fx = k->fx; r.fy = k->fy; r.cx = k->cx; r.cy = k->cy; r.mbf = k->mbf;
+    r.kind = kind;
+    return r;
+}
+
+// :2441-2536 and :2624-2860.  B.handled == false: not handled; the marks are already put back.
+template <class KFPtr, class MapT>
+auto GatherLocalInertialBA(KFPtr pKF, MapT* pMap, bool bLarge, bool bRecInit) {
+    (void)pMap;
+    typedef typename std::decay<decltype(pKF->GetMapPointMatches()[0])>::type MPPtr;
+    LocalInertialBAProblem<KFPtr, MPPtr> B;
+    auto* pCurrentMap = pKF->GetMap();
+    const int maxOpt = bLarge ? 25 : 10;                                                                 // :2435-2440
+    const int Nd = std::min((int)pCurrentMap->KeyFramesInMap() - 2, maxOpt);
+    // ---- the chain, without a mark: everything that can be refused from it is refused here
+    std::vector<KFPtr> chain;
+    chain.push_back(pKF);
+    for (int i = 1; i < Nd; i++) {
+        if (!chain.back()->mPrevKF) break;
+        chain.push_back(chain.back()->mPrevKF);
+    }
+    const bool has_prev = (bool)chain.back()->mPrevKF;
+    const KFPtr first_fixed = has_prev ? chain.back()->mPrevKF : chain.back();
+    const size_t N = has_prev ? chain.size() : chain.size() - 1;                                         // :2480-2488
+    auto refuse = [&] { B.handled = false; return B; };
+    if ((int)N > msorb_local_inertial_ba_capacity()) return refuse();
+    if (first_fixed->mpCamera2 || (N > 0 && !first_fixed->bImu)) return refuse();                        // :2602, :2642-2646
+    for (size_t i = 0; i < N; i++) {
+        const KFPtr& k = chain[i];
+        if (k->mpCamera2 || !k->bImu || !k->mPrevKF || !k->mpImuPreintegrated) return refuse();          // :2568, :2627-2630, :2684-2685
+    }
+    // ---- the reference's walk, with its marks
+    auto mark = [&](const KFPtr& k) { B.kf_marks.push_back({k, {k->mnBALocalForKF, k->mnBAFixedForKF}}); };
+    for (size_t i = 0; i < chain.size(); i++) {                                                          // :2449-2457
+        mark(chain[i]);
+        chain[i]->mnBALocalForKF = pKF->mnId;
+        B.vpOptimizableKFs.push_back(chain[i]);
+    }
+    for (const KFPtr& k : B.vpOptimizableKFs) {                                                          // :2465-2476
+        const auto vpMPs = k->GetMapPointMatches();
+        for (const MPPtr& pMP : vpMPs)
+            if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) {
+                B.lLocalMapPoints.push_back(pMP);
+                B.mp_marks.push_back({pMP, pMP->mnBALocalForKF});
+                pMP->mnBALocalForKF = pKF->mnId;
+            }
+    }
+    if (has_prev) {                                                                                      // :2480-2488
+        mark(first_fixed);
+        first_fixed->mnBAFixedForKF = pKF->mnId;
+    } else {
+        first_fixed->mnBALocalForKF = 0;
+        first_fixed->mnBAFixedForKF = pKF->mnId;
+        B.vpOptimizableKFs.pop_back();
+    }
+    B.lFixedKeyFrames.push_back(first_fixed);
+    // (lpOptVisKFs: maxCovKF = 0 keeps it empty, :2491-2514)
+    bool two_cameras = false;
+    for (const MPPtr& pMP : B.lLocalMapPoints) {                                                         // :2519-2536
+        const auto observations = pMP->GetObservations();
+        for (const auto& ob : observations) {
+            KFPtr pKFi = ob.first;
+            if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+                mark(pKFi);
+                pKFi->mnBAFixedForKF = pKF->mnId;
+                if (!pKFi->isBad()) {
+                    B.lFixedKeyFrames.push_back(pKFi);
+                    if (pKFi->mpCamera2) two_cameras = true;
+                    break;
+                }
+            }
+        }
+        if (B.lFixedKeyFrames.size() >= 200) break;
+    }
+    // ---- the vertices, ascending mnId (:2559-2617)
+    std::map<unsigned long, std::pair<KFPtr, int>> by_id;
+    for (const KFPtr& k : B.vpOptimizableKFs) by_id[k->mnId] = {k, 0};
+    for (const KFPtr& k : B.lFixedKeyFrames) by_id[k->mnId] = {k, k->bImu ? 1 : 2};                      // :2602
+    std::map<KFPtr, int> index;
+    for (const auto& it : by_id) {
+        index[it.second.first] = (int)B.kfs.size();
+        B.kfs.push_back(IbaKeyFrame(it.second.first, it.second.second));
+        B.kf_of_index.push_back(it.second.first);
+    }
+    // ---- the inertial edges (:2624-2686); the bias SetNewBias will install is mPrevKF->GetImuBias(), read here, set by the caller
+    const int Nw = (int)B.vpOptimizableKFs.size();
+    for (int i = 0; i < Nw && !two_cameras; i++) {
+        const KFPtr& k = B.vpOptimizableKFs[i];
+        msorb_iba_inertial_edge e;
+        std::memset(&e, 0, sizeof e);
+        const auto pInt = k->mpImuPreintegrated;
+        if (!pose_inertial_detail::EdgeOf(pInt, e.pre) || !pose_inertial_detail::RandomWalkInformation(pInt, 9, e.info_gyro) ||
+            !pose_inertial_detail::RandomWalkInformation(pInt, 12, e.info_acc)) {
+            two_cameras = true;   // (refused below like a late second camera)
+            break;
+        }
+        e.pre.kf_prev = index[k->mPrevKF];
+        e.pre.kf_cur = index[k];
+        e.huber = (i == Nw - 1 || bRecInit) ? 1 : 0;                                                     // :2657-2667
+        e.downweight = i == Nw - 1 ? 1 : 0;
+        B.iedges.push_back(e);
+    }
+    if (two_cameras) {
+        B.restore_marks();
+        return refuse();
+    }
+    // ---- the points and the visual edges (:2729-2856)
+    int nPoints = 0;
+    for (const MPPtr& pMP : B.lLocalMapPoints) {
+        const auto Xw = pMP->GetWorldPos();
+        B.pos_w.push_back(Xw(0)); B.pos_w.push_back(Xw(1)); B.pos_w.push_back(Xw(2));
+        B.point_close.push_back(pMP->mTrackDepth < 10.f ? 1 : 0);                                        // :2879
+        const auto observations = pMP->GetObservations();
+        for (const auto& ob : observations) {
+            KFPtr pKFi = ob.first;
+            if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) continue;        // :2746
+            if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) continue;                                // :2749
+            const auto at = index.find(pKFi);
+            if (at == index.end()) continue;   // (marked fixed but bad: no vertex; the reference's setVertex would get NULL)
+            if (B.append(pKFi, std::get<0>(ob.second), at->second, nPoints)) B.edge_objects.push_back({pKFi, pMP});
+        }
+        nPoints++;
+    }
+    return B;
+}
+
+template <class KFPtr, class MapT>
+bool LocalInertialBA(KFPtr pKF, bool* pbStopFlag, MapT* pMap, int& num_fixedKF, int& num_OptKF, int& num_MPs, int& num_edges,
+                     bool bLarge = false, bool bRecInit = false, int device = 0) {
+    (void)pbStopFlag; (void)num_fixedKF; (void)num_OptKF; (void)num_MPs; (void)num_edges;
+    auto B = GatherLocalInertialBA(pKF, pMap, bLarge, bRecInit);
+    if (!B.handled) return false;
+    const int K = (int)B.kfs.size(), P = (int)B.lLocalMapPoints.size(), E = (int)B.edge_kf.size(), NI = (int)B.iedges.size();
+    msorb_iba_problem prob;
+    std::memset(&prob, 0, sizeof prob);
+    prob.large = bLarge ? 1 : 0;
+    std::vector<msorb_iba_keyframe_out> kf_out((size_t)K);
+    std::vector<float> pos_out(3 * (size_t)P);
+    std::vector<uint8_t> outlier((size_t)E);
+    msorb_iba_result r;
+    const int rc = msorb_local_inertial_ba(device, &prob, K, B.kfs.data(), NI, B.iedges.data(), P, B.pos_w.data(), B.point_close.data(), E,
+                                           B.edge_kf.data(), B.edge_point.data(), B.xy.data(), B.u_right.data(), B.inv_sigma2.data(),
+                                           kf_out.data(), pos_out.data(), nullptr, outlier.data(), &r, nullptr);
+    if (rc == MSORB_E_CAPACITY) { B.restore_marks(); return false; }
+    if (rc != MSORB_OK) fail_call("msorb_local_inertial_ba");
+    for (const KFPtr& k : B.vpOptimizableKFs) k->mpImuPreintegrated->SetNewBias(k->mPrevKF->GetImuBias());   // :2632
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                                            // :2907
+    if (r.status == 1) return true;                                                                      // :2911-2915
+    for (int pass = 0; pass < 2; pass++)                                                                 // vToErase: the mono edges, then the stereo edges
+        for (int e = 0; e < E; e++) {
+            if (!outlier[e] || (B.u_right[e] >= 0) != (pass == 1)) continue;
+            const auto& o = B.edge_objects[e];
+            if (o.second->isBad()) continue;                                                             // :2881, :2897
+            o.first->EraseMapPointMatch(o.second);                                                       // :2922-2923
+            o.second->EraseObservation(o.first);
+        }
+    for (const KFPtr& k : B.lFixedKeyFrames) k->mnBAFixedForKF = 0;                                      // :2927-2928
+    typedef typename std::decay<decltype(pKF->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(pKF->GetPose().rotationMatrix())>::type RotF;
+    typedef typename std::decay<decltype(pKF->GetPose().translation())>::type VecF;
+    typedef typename std::decay<decltype(pKF->GetVelocity())>::type VelF;
+    typedef typename std::decay<decltype(pKF->GetImuBias())>::type BiasT;
+    std::map<KFPtr, int> index;
+    for (int k = 0; k < K; k++) index[B.kf_of_index[k]] = k;
+    for (const KFPtr& k : B.vpOptimizableKFs) {                                                          // :2933-2951
+        const msorb_iba_keyframe_out& o = kf_out[index[k]];
+        RotF Rf;
+        VecF tf;
+        VelF vf;
+        for (int a = 0; a < 3; a++) {
+            for (int b = 0; b < 3; b++) Rf(a, b) = o.Rcw_f[3 * a + b];
+            tf(a) = o.tcw_f[a];
+            vf(a) = o.v_f[a];
+        }
+        k->SetPose(SE3T(Rf, tf));
+        k->mnBALocalForKF = 0;
+        k->SetVelocity(vf);
+        k->SetNewBias(BiasT(o.bias_f[0], o.bias_f[1], o.bias_f[2], o.bias_f[3], o.bias_f[4], o.bias_f[5]));
+    }
+    typedef typename std::decay<decltype(B.lLocalMapPoints.front()->GetWorldPos())>::type PosT;
+    int p = 0;
+    for (const auto& pMP : B.lLocalMapPoints) {                                                          // :2963-2970
+        const float* o = pos_out.data() + 3 * (size_t)p++;
+        pMP->SetWorldPos(PosT(o[0], o[1], o[2]));
+        pMP->UpdateNormalAndDepth();
+    }
+    pMap->IncreaseChangeIndex();                                                                         // :2972
+    return true;
 }
 
 }  // namespace msorb_host

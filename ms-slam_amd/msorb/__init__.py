@@ -2640,3 +2640,69 @@ def frame_pose_inertial_optimization(frame, problem, has_point, pos_w, close, in
     _check(L.msorb_frame_pose_inertial_optimization(frame.h, _np_ptr(pr), _np_ptr(hp), _np_ptr(pw), _np_ptr(cl), _np_ptr(inv),
                                                     len(inv), _np_ptr(out), _np_ptr(res)), "msorb_frame_pose_inertial_optimization")
     return res[0], out[:frame.n]
+
+
+# ---- Optimizer::LocalInertialBA on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_local_inertial_ba_capacity", "msorb_local_inertial_ba")
+
+IBA_PROBLEM_DTYPE = np.dtype([("large", "<i4"), ("iterations", "<i4"), ("reserved", "<i4", 2)])          # msorb_iba_problem
+IBA_KF_DTYPE = np.dtype([("Rwb", "<f8", 9), ("twb", "<f8", 3), ("v", "<f8", 3), ("bg", "<f8", 3), ("ba", "<f8", 3), ("Rcw", "<f8", 9),
+                         ("tcw", "<f8", 3), ("Rcb", "<f8", 9), ("tcb", "<f8", 3), ("tbc", "<f8", 3), ("fx", "<f4"), ("fy", "<f4"),
+                         ("cx", "<f4"), ("cy", "<f4"), ("mbf", "<f4"), ("kind", "<i4")])                   # msorb_iba_keyframe
+IBA_EDGE_DTYPE = np.dtype([("pre", INERTIAL_EDGE_DTYPE), ("info_gyro", "<f8", 9), ("info_acc", "<f8", 9), ("huber", "<i4"),
+                           ("downweight", "<i4")])                                                         # msorb_iba_inertial_edge
+IBA_KF_OUT_DTYPE = np.dtype([("Rwb", "<f8", 9), ("twb", "<f8", 3), ("Rcw", "<f8", 9), ("tcw", "<f8", 3), ("v", "<f8", 3),
+                             ("bg", "<f8", 3), ("ba", "<f8", 3), ("Rcw_f", "<f4", 9), ("tcw_f", "<f4", 3), ("v_f", "<f4", 3),
+                             ("bias_f", "<f4", 6), ("reserved_f", "<f4")])                                 # msorb_iba_keyframe_out
+IBA_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("rejected_trials", "<i4"),
+                             ("n_outliers", "<i4"), ("reserved", "<i4"), ("chi2_initial", "<f8"), ("chi2_final", "<f8"),
+                             ("lambda_final", "<f8"), ("err", "<f4"), ("err_end", "<f4")])                 # msorb_iba_result
+assert (IBA_PROBLEM_DTYPE.itemsize, IBA_KF_DTYPE.itemsize, IBA_EDGE_DTYPE.itemsize, IBA_KF_OUT_DTYPE.itemsize,
+        IBA_RESULT_DTYPE.itemsize) == (16, 408, 1080, 352, 56)
+
+
+def _iba_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_local_inertial_ba_capacity.argtypes = []
+    L.msorb_local_inertial_ba.argtypes = [ci, vp, ci, vp, ci, vp, ci, vp, vp, ci] + [vp] * 11
+    return L
+
+
+def local_inertial_ba_capacity():
+    """the largest number of free KeyFrames msorb_local_inertial_ba accepts"""
+    return _iba_lib().msorb_local_inertial_ba_capacity()
+
+
+def local_inertial_ba(keyframes, inertial_edges, pos_w, point_close, edge_kf, edge_point, xy, u_right, inv_sigma2, large=False,
+                      iterations=0, device=0, timing=False, out=None):
+    """msorb_local_inertial_ba: Optimizer::LocalInertialBA after its gathering loops, on the device.  keyframes: IBA_KF_DTYPE [K];
+    inertial_edges: IBA_EDGE_DTYPE [NI]; pos_w [P, 3], point_close [P]; the visual edges point-major as for local_ba.  large =
+    bLarge; iterations > 0 replaces the reference's 4 / 10.
+    -> dict(result: IBA_RESULT_DTYPE record, kf: IBA_KF_OUT_DTYPE [K], pos float32 [P, 3], pos_d float64 [P, 3], outlier bool [E])
+    and, with timing, elapsed_ms (device time).  out: (kf, pos, pos_d, outlier uint8) arrays to be written instead of fresh ones
+    (they keep their contents when the call is refused)."""
+    L = _iba_lib()
+    kf = _c(keyframes, IBA_KF_DTYPE).reshape(-1)
+    ie = _c(inertial_edges, IBA_EDGE_DTYPE).reshape(-1)
+    pw, cl = _c(pos_w, np.float32).reshape(-1), _c(point_close, np.uint8).reshape(-1)
+    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
+    px, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
+    P, E = len(cl), len(ek)
+    if len(pw) != 3 * P or [len(a) for a in (ep, px, ur, inv)] != [E, 2 * E, E, E]:
+        raise ValueError("pos_w / point_close or the edge arrays disagree in length")
+    pr = np.zeros(1, IBA_PROBLEM_DTYPE)
+    pr["large"], pr["iterations"] = int(bool(large)), iterations
+    if out is None:
+        out = (np.zeros(max(len(kf), 1), IBA_KF_OUT_DTYPE), np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64),
+               np.zeros(max(E, 1), np.uint8))
+    kf_out, pos, pos_d, flags = out
+    res = np.zeros(1, IBA_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_local_inertial_ba(device, _np_ptr(pr), len(kf), _np_ptr(kf), len(ie), _np_ptr(ie), P, _np_ptr(pw), _np_ptr(cl), E,
+                                     _np_ptr(ek), _np_ptr(ep), _np_ptr(px), _np_ptr(ur), _np_ptr(inv), _np_ptr(kf_out), _np_ptr(pos),
+                                     _np_ptr(pos_d), _np_ptr(flags), _np_ptr(res), C.addressof(ms)), "msorb_local_inertial_ba")
+    r = dict(result=res[0], kf=kf_out[:len(kf)], pos=pos[:P], pos_d=pos_d[:P], outlier=flags[:E].astype(bool))
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r
