@@ -1501,7 +1501,7 @@ int msorb_frame_pose_inertial_optimization(msorb_frame* f, const msorb_pose_iner
                                            uint8_t* outlier, msorb_pose_inertial_result* r);
 
 /* Optimizer::LocalInertialBA (src/Optimizer.cc:2431-2973) after its gathering loops, on the device, for pinhole KeyFrames without a
- * second camera (the mpCamera2 arm of :2820-2853 is not restated; FullInertialBA and MergeInertialBA are not either): EdgeMono /
+ * second camera (the mpCamera2 arm of :2820-2853 is not restated; FullInertialBA is msorb_full_inertial_ba below, MergeInertialBA is not restated): EdgeMono /
  * EdgeStereo over ImuCamPose and the points, EdgeInertial, EdgeGyroRW and EdgeAccRW along the chain of KeyFrames, g2o's Levenberg
  * with setUserLambdaInit, the points eliminated by the Schur complement, in double with the preintegration's bias correction in
  * float as the reference has it.  The whole optimize() is ONE launch of one workgroup.  Appended to ABI 6002: MSORB_ABI_VERSION
@@ -1555,6 +1555,47 @@ int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, int n_kf, co
                             int n_edges, const int* edge_kf, const int* edge_point, const float* xy, const float* u_right,
                             const float* inv_sigma2, msorb_iba_keyframe_out* kf_out, float* pos_out, double* pos_d,
                             uint8_t* edge_outlier, msorb_iba_result* r, float* elapsed_ms);
+
+/* Optimizer::FullInertialBA (src/Optimizer.cc:366-756) after its gathering loops, on the device, for pinhole KeyFrames without a
+ * second camera (the mpCamera2 arm of :643-673 is not restated): g2o's optimize(its) over the whole inertial map, as
+ * LocalMapping::InitializeIMU (init = 1, then init = 0) and the global BA after a loop closure on an inertial map run it.  The host
+ * drives g2o's Levenberg loop launch by launch over the whole chip and looks at *stop_flag (may be NULL) where g2o calls
+ * terminate(); the reduced system is factored by the blocked L D L^T of msorb_bundle_adjustment.  In double, with the
+ * preintegration's bias correction in float as the reference has it.  Appended to ABI 6002: MSORB_ABI_VERSION stays 6002.
+ * problem: init = bInit.  init = 0: per free KeyFrame pose, velocity, gyro bias, acc bias; EdgeInertial, EdgeGyroRW, EdgeAccRW.
+ * init = 1: per free KeyFrame pose and velocity, ONE gyro and one acc bias shared by every EdgeInertial, starting at bg0 / ba0
+ * (the bias of the last KeyFrame the loop of :393-425 visits), no random-walk edge (info_gyro / info_acc are ignored),
+ * EdgePriorGyro / EdgePriorAcc with prior_g / prior_a times the identity and bprior = 0.  iterations = its; lambda starts at 1e-5
+ * (setUserLambdaInit); no classification, no FAIL rule.
+ * kfs, iedges and the visual edges: msorb_local_inertial_ba's records.  huber / downweight are honoured as given (the reference:
+ * huber on every edge, no downweight).  With init = 0 an inertial edge between two fixed KeyFrames is not active; with init = 1 it
+ * is, because the shared biases are free.  No fixed KeyFrame at all is the normal case.  A point none of whose edges ends at a
+ * free KeyFrame is no vertex and its edges do not count (:677-680): point_included [n_points] = 0 and its position repeats.
+ * Result: status 0 = optimised; 2 = nothing to optimise (no KeyFrame, or init = 0 without a free one); 3 = *stop_flag was set
+ * before optimize() (:683-685); with 2 and 3 every output repeats its input.  n_outliers, err, err_end = 0.  reserved = the number of
+ * trials whose factorisation met a pivot that was not positive (g2o's rule then takes the cost as DBL_MAX and may still accept the
+ * trial).  The solve is dense and unpivoted: without a fixed KeyFrame the four gauge directions are held by lambda alone, and on maps of
+ * about 25 KeyFrames and more rounding decides whether a pivot is positive.  A call with reserved != 0 is outside what is claimed:
+ * msorb_host::FullInertialBA hands such a map back to g2o.  kf_out as
+ * msorb_local_inertial_ba's; a fixed KeyFrame's repeats its input, except that with init = 1 every KeyFrame with inertial vertices
+ * (kind 0 and 1) receives the shared biases (:720-733).
+ * Errors as msorb_local_inertial_ba's, nothing written before the last of them has passed; inertial edges that are not chains, or
+ * more free KeyFrames than msorb_full_inertial_ba_capacity(init) (477 / 795: a dense square of 7168 unknowns), are
+ * MSORB_E_CAPACITY.  Two calls on the same input return the same bits.  Re-entrant.  *elapsed_ms (may be NULL): device time.
+ * msorb_full_inertial_ba_stage_ms: with MSORB_FULL_INERTIAL_BA_STAGES=1 in the environment, the calling thread's last call's device
+ * time per stage: linearise, assemble, Schur, solve, trial. */
+typedef struct msorb_fiba_problem {
+    int32_t init, iterations;
+    float prior_g, prior_a;
+    double bg0[3], ba0[3];
+} msorb_fiba_problem;
+int msorb_full_inertial_ba_capacity(int init);
+int msorb_full_inertial_ba_stage_ms(float ms[5]);
+int msorb_full_inertial_ba(int device, const msorb_fiba_problem* p, int n_kf, const msorb_iba_keyframe* kfs, int n_inertial,
+                           const msorb_iba_inertial_edge* iedges, int n_points, const float* pos_w, int n_edges, const int* edge_kf,
+                           const int* edge_point, const float* xy, const float* u_right, const float* inv_sigma2,
+                           const volatile int* stop_flag, msorb_iba_keyframe_out* kf_out, float* pos_out, double* pos_d,
+                           uint8_t* point_included, msorb_iba_result* r, float* elapsed_ms);
 
 #ifdef __cplusplus
 }

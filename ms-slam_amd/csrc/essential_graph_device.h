@@ -191,14 +191,16 @@ struct Outcome {
 //   be.linearise(cur, chi)                       computeActiveErrors + activeRobustChi2 + buildSystem at copy `cur`
 //   be.trial(cur, lambda, chi, scale, solved)    setLambda, solve, update into copy cur ^ 1, the cost there, computeScale
 // Both return 0 or an error code, which ends the loop and is returned.  lambda_init(be) is computeLambdaInit (:172-186), asked once,
-// after the first linearisation.
-template <typename Backend, typename LambdaInit>
-inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o, LambdaInit lambda_init) {
+// after the first linearisation.  stopped() is SparseOptimizer::terminate(), the caller's stop flag, asked where g2o asks it
+// (sparse_optimizer.cpp:376, levenberg.cpp:149); o.stop = 3 when it ended the call.
+template <typename Backend, typename LambdaInit, typename Stopped>
+inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o, LambdaInit lambda_init, Stopped stopped) {
     o = Outcome();
     int cur = 0, n_bad = 0;
     double lambda = 0, ni = 2;
     bool ok = any_edge;   // without an active edge there is nothing to optimise: zero iterations
-    for (int it = 0; it < max_it && ok; it++) {
+    bool flag = false;
+    for (int it = 0; it < max_it && !(flag = stopped()) && ok; it++) {
         double current = 0;
         if (int rc = be.linearise(cur, current)) return rc;
         double temp = current;
@@ -234,7 +236,7 @@ inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o, LambdaI
                 o.rejected++;
             }
             qmax++;
-        } while (rho < 0 && qmax < 10);                    // :149 (neither overload sets a stop flag)
+        } while (rho < 0 && qmax < 10 && !stopped());      // :149
         o.iterations++;
         o.chi2_final = current;
         if (qmax == 10 || rho == 0) { ok = false; o.stop = 1; continue; }   // :151-155
@@ -242,10 +244,17 @@ inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o, LambdaI
         else n_bad = 0;
         if (n_bad >= 3) { ok = false; o.stop = 2; }        // :164-167
     }
+    if (flag && ok) o.stop = 3;
     if (o.iterations == 0) o.chi2_final = o.chi2_initial;
     o.lambda = lambda;
     be.current = cur;
     return 0;
+}
+
+// without a stop flag (OptimizeEssentialGraph sets none)
+template <typename Backend, typename LambdaInit>
+inline int levenberg(Backend& be, int max_it, bool any_edge, Outcome& o, LambdaInit lambda_init) {
+    return levenberg(be, max_it, any_edge, o, lambda_init, [] { return false; });
 }
 
 // the 7-DoF form: computeLambdaInit returns the user value (:174-175), solver->setUserLambdaInit(1e-16) (Optimizer.cc:1423, :1698)

@@ -58,6 +58,7 @@ struct Res { double chi, scale; };   // the cost and computeScale's sum, where e
 
 struct Work {
     int K, Kf, P, E, NI, n, n_pairs, max_it, large;
+    int shared_bias;                              // full_inertial_ba_device.h's init form: one bias pair for every edge, always free
     const msorb_iba_keyframe* kf;
     const msorb_iba_inertial_edge* ie;            // info already downweighted (staged_edge)
     const int *free_of_kf, *kf_of_free, *edge_kf, *edge_pt, *point_begin, *kf_begin, *kf_edge, *pair_begin, *pair_i, *pair_j, *pair_a, *pair_b;
@@ -183,7 +184,7 @@ SE3_HD void visual_edge(const Work& W, int s, int e) {
 // ---- the inertial edges
 
 SE3_HD bool iedge_active(const Work& W, int i) {   // an edge whose vertices are all fixed is not active
-    return W.free_of_kf[W.ie[i].pre.kf_prev] >= 0 || W.free_of_kf[W.ie[i].pre.kf_cur] >= 0;
+    return W.shared_bias || W.free_of_kf[W.ie[i].pre.kf_prev] >= 0 || W.free_of_kf[W.ie[i].pre.kf_cur] >= 0;
 }
 
 // EdgeInertial, EdgeGyroRW and EdgeAccRW number i at state s: errors, chi2, EdgeInertial's Huber of delta sqrt(16.92)
@@ -295,32 +296,42 @@ SE3_HD void evaluate(Exec& ex, const Work& W, int s) {
     ex.barrier();
 }
 
+// Hll / bl of point p over its run of edges, ascending
+SE3_HD void point_gather(const Work& W, int p) {
+    const size_t E = (size_t)W.E;
+    double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int e = W.point_begin[p]; e < W.point_begin[p + 1]; e++)
+        for (int q = 0; q < 9; q++) S[q] += W.lin[(size_t)q * E + e];
+    for (int q = 0; q < 9; q++) W.Hll[9 * (size_t)p + q] = S[q];
+}
+
+// entry t % 27 of Hpp / bp of free KeyFrame t / 27 over its list, ascending
+SE3_HD void hpp_gather(const Work& W, int t) {
+    const size_t E = (size_t)W.E;
+    const int i = t / 27, q = t % 27;
+    double s = 0;
+    for (int m = W.kf_begin[i]; m < W.kf_begin[i + 1]; m++) s += W.lin[(size_t)(kHpp + q) * E + W.kf_edge[m]];
+    W.Hpp[t] = s;
+}
+
+// entry t % (kJc * 9) of inertial edge t / (kJc * 9)'s A^T (rho' omega): robustInformation (base_edge.h:96-100)
+SE3_HD void ato_entry(const Work& W, int t, bool active) {
+    const int m = t / (kJc * 9), q = t % (kJc * 9), a = q / 9, c = q % 9;
+    if (!active) return;
+    IEdgeLin& L = W.il[m];
+    const double* info = W.ie[m].pre.info;
+    double s = L.J[a] * (L.rho1 * info[c]);
+    for (int k = 1; k < 9; k++) s += L.J[k * kJc + a] * (L.rho1 * info[9 * k + c]);
+    L.AtO[q] = s;
+}
+
 // Hll / bl per point, Hpp / bp per free KeyFrame over its list, the inertial edges' A^T (rho' omega), then H and b
 template <typename Exec>
 SE3_HD void build_system(Exec& ex, const Work& W) {
-    const size_t E = (size_t)W.E;
     const int n = W.n;
-    for (int p = ex.tid(); p < W.P; p += ex.stride()) {
-        double S[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int e = W.point_begin[p]; e < W.point_begin[p + 1]; e++)
-            for (int q = 0; q < 9; q++) S[q] += W.lin[(size_t)q * E + e];
-        for (int q = 0; q < 9; q++) W.Hll[9 * (size_t)p + q] = S[q];
-    }
-    for (int t = ex.tid(); t < 27 * W.Kf; t += ex.stride()) {
-        const int i = t / 27, q = t % 27;
-        double s = 0;
-        for (int m = W.kf_begin[i]; m < W.kf_begin[i + 1]; m++) s += W.lin[(size_t)(kHpp + q) * E + W.kf_edge[m]];
-        W.Hpp[t] = s;
-    }
-    for (int t = ex.tid(); t < W.NI * kJc * 9; t += ex.stride()) {   // robustInformation (base_edge.h:96-100)
-        const int m = t / (kJc * 9), q = t % (kJc * 9), a = q / 9, c = q % 9;
-        if (!iedge_active(W, m)) continue;
-        IEdgeLin& L = W.il[m];
-        const double* info = W.ie[m].pre.info;
-        double s = L.J[a] * (L.rho1 * info[c]);
-        for (int k = 1; k < 9; k++) s += L.J[k * kJc + a] * (L.rho1 * info[9 * k + c]);
-        L.AtO[q] = s;
-    }
+    for (int p = ex.tid(); p < W.P; p += ex.stride()) point_gather(W, p);
+    for (int t = ex.tid(); t < 27 * W.Kf; t += ex.stride()) hpp_gather(W, t);
+    for (int t = ex.tid(); t < W.NI * kJc * 9; t += ex.stride()) ato_entry(W, t, iedge_active(W, t / (kJc * 9)));
     ex.barrier();
     for (int t = ex.tid(); t < n * (n + 1); t += ex.stride()) {
         const int r = t / (n + 1), c = t % (n + 1);
@@ -354,25 +365,64 @@ SE3_HD void build_system(Exec& ex, const Work& W) {
     ex.barrier();
 }
 
+// Dinv of point p (block_solver.hpp:389) as Eigen inverts a 3x3, with setLambda on Hll (:573-578), and Dinv bl
+SE3_HD void dinv_point(const Work& W, int p, double lambda) {
+    const double* H = W.Hll + 9 * (size_t)p;
+    const double m00 = H[0] + lambda, m01 = H[1], m02 = H[2], m11 = H[3] + lambda, m12 = H[4], m22 = H[5] + lambda;
+    const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m22 * m01, c20 = m01 * m12 - m02 * m11;
+    const double det = (c00 * m00 + c10 * m01) + c20 * m02, inv = 1.0 / det;
+    const double i00 = c00 * inv, i01 = c10 * inv, i02 = c20 * inv;
+    const double i11 = (m22 * m00 - m02 * m02) * inv, i12 = (m02 * m01 - m00 * m12) * inv, i22 = (m00 * m11 - m01 * m01) * inv;
+    double* o = W.Dinv + 9 * (size_t)p;
+    o[0] = i00; o[1] = i01; o[2] = i02; o[3] = i11; o[4] = i12; o[5] = i22;
+    o[6] = (i00 * H[6] + i01 * H[7]) + i02 * H[8];
+    o[7] = (i01 * H[6] + i11 * H[7]) + i12 * H[8];
+    o[8] = (i02 * H[6] + i12 * H[7]) + i22 * H[8];
+}
+
+// One task of the Schur complement (:381-439): row t % 6 of block pair t / 6 (i <= j) taken off S, or row t % 6 of a KeyFrame's
+// right side.  S and bs hold the system with lambda set; the pose corner is rows and columns 0 .. 6 Kf of the stride-n square.
+SE3_HD void schur_task(const Work& W, int t) {
+    const size_t E = (size_t)W.E;
+    const int n = W.n;
+    const int task = t / 6, r = t % 6;
+    if (task >= W.n_pairs) {
+        const int i = task - W.n_pairs;
+        double c = 0;
+        for (int m = W.kf_begin[i]; m < W.kf_begin[i + 1]; m++) {
+            const int e = W.kf_edge[m];
+            const double* db = W.Dinv + 9 * (size_t)W.edge_pt[e] + 6;
+            const double* Wr = W.lin + (size_t)(kW + 3 * r) * E + e;
+            c += (Wr[0] * db[0] + Wr[E] * db[1]) + Wr[2 * E] * db[2];
+        }
+        W.bs[6 * i + r] = W.bA[6 * i + r] - c;
+        return;
+    }
+    const int i = W.pair_i[task], j = W.pair_j[task];
+    double T[6] = {0, 0, 0, 0, 0, 0};
+    for (int m = W.pair_begin[task]; m < W.pair_begin[task + 1]; m++) {
+        const int a = W.pair_a[m], b = W.pair_b[m];
+        const double* Di = W.Dinv + 9 * (size_t)W.edge_pt[a];
+        const double w0 = W.lin[(size_t)(kW + 3 * r) * E + a], w1 = W.lin[(size_t)(kW + 3 * r + 1) * E + a],
+                     w2 = W.lin[(size_t)(kW + 3 * r + 2) * E + a];
+        const double y0 = (w0 * Di[0] + w1 * Di[1]) + w2 * Di[2], y1 = (w0 * Di[1] + w1 * Di[3]) + w2 * Di[4],
+                     y2 = (w0 * Di[2] + w1 * Di[4]) + w2 * Di[5];
+        for (int c = 0; c < 6; c++)
+            T[c] += (y0 * W.lin[(size_t)(kW + 3 * c) * E + b] + y1 * W.lin[(size_t)(kW + 3 * c + 1) * E + b]) +
+                    y2 * W.lin[(size_t)(kW + 3 * c + 2) * E + b];
+    }
+    for (int c = (i == j ? r : 0); c < 6; c++) {
+        double* s = W.S + (size_t)(6 * j + c) * n + 6 * i + r;
+        *s = *s - T[c];
+    }
+}
+
 // setLambda on all of Hpp and Hll (block_solver.hpp:573-578), Dinv (:389) as Eigen inverts a 3x3, the Schur complement over the
 // plan's lists (:381-439) into the pose corner
 template <typename Exec>
 SE3_HD void reduce_system(Exec& ex, const Work& W, double lambda) {
-    const size_t E = (size_t)W.E;
     const int n = W.n;
-    for (int p = ex.tid(); p < W.P; p += ex.stride()) {
-        const double* H = W.Hll + 9 * (size_t)p;
-        const double m00 = H[0] + lambda, m01 = H[1], m02 = H[2], m11 = H[3] + lambda, m12 = H[4], m22 = H[5] + lambda;
-        const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m22 * m01, c20 = m01 * m12 - m02 * m11;
-        const double det = (c00 * m00 + c10 * m01) + c20 * m02, inv = 1.0 / det;
-        const double i00 = c00 * inv, i01 = c10 * inv, i02 = c20 * inv;
-        const double i11 = (m22 * m00 - m02 * m02) * inv, i12 = (m02 * m01 - m00 * m12) * inv, i22 = (m00 * m11 - m01 * m01) * inv;
-        double* o = W.Dinv + 9 * (size_t)p;
-        o[0] = i00; o[1] = i01; o[2] = i02; o[3] = i11; o[4] = i12; o[5] = i22;
-        o[6] = (i00 * H[6] + i01 * H[7]) + i02 * H[8];
-        o[7] = (i01 * H[6] + i11 * H[7]) + i12 * H[8];
-        o[8] = (i02 * H[6] + i12 * H[7]) + i22 * H[8];
-    }
+    for (int p = ex.tid(); p < W.P; p += ex.stride()) dinv_point(W, p, lambda);
     for (int t = ex.tid(); t < n * n; t += ex.stride()) {
         const int r = t / n, c = t % n;
         if (c <= r) W.S[t] = r == c ? W.A[t] + lambda : W.A[t];
@@ -381,38 +431,7 @@ SE3_HD void reduce_system(Exec& ex, const Work& W, double lambda) {
     ex.barrier();
     // a task = one row of one block pair (i <= j), or one row of a KeyFrame's right side
     const int n_tasks = 6 * (W.n_pairs + W.Kf);
-    for (int t = ex.tid(); t < n_tasks; t += ex.stride()) {
-        const int task = t / 6, r = t % 6;
-        if (task >= W.n_pairs) {
-            const int i = task - W.n_pairs;
-            double c = 0;
-            for (int m = W.kf_begin[i]; m < W.kf_begin[i + 1]; m++) {
-                const int e = W.kf_edge[m];
-                const double* db = W.Dinv + 9 * (size_t)W.edge_pt[e] + 6;
-                const double* Wr = W.lin + (size_t)(kW + 3 * r) * E + e;
-                c += (Wr[0] * db[0] + Wr[E] * db[1]) + Wr[2 * E] * db[2];
-            }
-            W.bs[6 * i + r] = W.bA[6 * i + r] - c;
-            continue;
-        }
-        const int i = W.pair_i[task], j = W.pair_j[task];
-        double T[6] = {0, 0, 0, 0, 0, 0};
-        for (int m = W.pair_begin[task]; m < W.pair_begin[task + 1]; m++) {
-            const int a = W.pair_a[m], b = W.pair_b[m];
-            const double* Di = W.Dinv + 9 * (size_t)W.edge_pt[a];
-            const double w0 = W.lin[(size_t)(kW + 3 * r) * E + a], w1 = W.lin[(size_t)(kW + 3 * r + 1) * E + a],
-                         w2 = W.lin[(size_t)(kW + 3 * r + 2) * E + a];
-            const double y0 = (w0 * Di[0] + w1 * Di[1]) + w2 * Di[2], y1 = (w0 * Di[1] + w1 * Di[3]) + w2 * Di[4],
-                         y2 = (w0 * Di[2] + w1 * Di[4]) + w2 * Di[5];
-            for (int c = 0; c < 6; c++)
-                T[c] += (y0 * W.lin[(size_t)(kW + 3 * c) * E + b] + y1 * W.lin[(size_t)(kW + 3 * c + 1) * E + b]) +
-                        y2 * W.lin[(size_t)(kW + 3 * c + 2) * E + b];
-        }
-        for (int c = (i == j ? r : 0); c < 6; c++) {
-            double* s = W.S + (size_t)(6 * j + c) * n + 6 * i + r;
-            *s = *s - T[c];
-        }
-    }
+    for (int t = ex.tid(); t < n_tasks; t += ex.stride()) schur_task(W, t);
     ex.barrier();
 }
 
@@ -468,12 +487,40 @@ SE3_HD bool solve(Exec& ex, const Work& W) {
     return true;
 }
 
+// xl = Dinv (bl - sum W^T xp) of point p (block_solver.hpp:461-481) added to copy `from` into copy `to`, and the point's term of
+// computeScale (levenberg.cpp:188-195) into part_vtx[slot]
+SE3_HD void point_update(const Work& W, int from, int to, double lambda, int p, int slot) {
+    const size_t E = (size_t)W.E;
+    const double* H = W.Hll + 9 * (size_t)p;
+    double cl[3] = {H[6], H[7], H[8]};
+    for (int e = W.point_begin[p]; e < W.point_begin[p + 1]; e++) {
+        const int i = W.free_of_kf[W.edge_kf[e]];
+        if (i < 0) continue;
+        const double* xp = W.x + 6 * (size_t)i;
+        for (int c = 0; c < 3; c++) {
+            double tsum = 0;
+            for (int r = 0; r < 6; r++) tsum += W.lin[(size_t)(kW + 3 * r + c) * E + e] * (-xp[r]);
+            cl[c] += tsum;
+        }
+    }
+    const double* D = W.Dinv + 9 * (size_t)p;
+    double xl[3];
+    xl[0] = (D[0] * cl[0] + D[1] * cl[1]) + D[2] * cl[2];
+    xl[1] = (D[1] * cl[0] + D[3] * cl[1]) + D[4] * cl[2];
+    xl[2] = (D[2] * cl[0] + D[4] * cl[1]) + D[5] * cl[2];
+    double sc = 0;
+    for (int c = 0; c < 3; c++) {
+        sc += xl[c] * (lambda * xl[c] + H[6 + c]);
+        W.pt[to][3 * (size_t)p + c] = W.pt[from][3 * (size_t)p + c] + xl[c];
+    }
+    W.part_vtx[slot] = sc;
+}
+
 // SparseOptimizer::update of copy `from` into copy `to` (sparse_optimizer.cpp:422-441): a free KeyFrame's four oplusImpl (the copy
 // carries ImuCamPose's update counter, so push / pop keep it as the reference's copy of the estimate does), and per point
 // xl = Dinv (bl - sum W^T xp) (block_solver.hpp:461-481); computeScale's terms (levenberg.cpp:188-195) per vertex
 template <typename Exec>
 SE3_HD void update(Exec& ex, const Work& W, int from, int to, double lambda) {
-    const size_t E = (size_t)W.E;
     for (int v = ex.tid(); v < W.Kf + W.P; v += ex.stride()) {
         if (v < W.Kf) {
             const int k = W.kf_of_free[v];
@@ -489,30 +536,7 @@ SE3_HD void update(Exec& ex, const Work& W, int from, int to, double lambda) {
             W.part_vtx[v] = sc;
             continue;
         }
-        const int p = v - W.Kf;
-        const double* H = W.Hll + 9 * (size_t)p;
-        double cl[3] = {H[6], H[7], H[8]};
-        for (int e = W.point_begin[p]; e < W.point_begin[p + 1]; e++) {
-            const int i = W.free_of_kf[W.edge_kf[e]];
-            if (i < 0) continue;
-            const double* xp = W.x + 6 * (size_t)i;
-            for (int c = 0; c < 3; c++) {
-                double tsum = 0;
-                for (int r = 0; r < 6; r++) tsum += W.lin[(size_t)(kW + 3 * r + c) * E + e] * (-xp[r]);
-                cl[c] += tsum;
-            }
-        }
-        const double* D = W.Dinv + 9 * (size_t)p;
-        double xl[3];
-        xl[0] = (D[0] * cl[0] + D[1] * cl[1]) + D[2] * cl[2];
-        xl[1] = (D[1] * cl[0] + D[3] * cl[1]) + D[4] * cl[2];
-        xl[2] = (D[2] * cl[0] + D[4] * cl[1]) + D[5] * cl[2];
-        double sc = 0;
-        for (int c = 0; c < 3; c++) {
-            sc += xl[c] * (lambda * xl[c] + H[6 + c]);
-            W.pt[to][3 * (size_t)p + c] = W.pt[from][3 * (size_t)p + c] + xl[c];
-        }
-        W.part_vtx[v] = sc;
+        point_update(W, from, to, lambda, v - W.Kf, v);
     }
     ex.barrier();
 }

@@ -1878,6 +1878,187 @@ bool LocalInertialBA(KFPtr pKF, bool* pbStopFlag, MapT* pMap, int& num_fixedKF, 
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::FullInertialBA (src/Optimizer.cc:366-756; LocalMapping.cc:1328, :1330, LoopClosing.cc:2230) on msorb_full_inertial_ba.
+//
+//   bool ORB_SLAM3::msorb_host::FullInertialBA(pMap, its, bFixLocal, nLoopId, pbStopFlag, bInit, priorG, priorA, vSingVal, bHess)
+//
+// the reference's parameter list and defaults (vSingVal and bHess are unused by the reference and unused here) and its effects:
+// SetNewBias(mPrevKF->GetImuBias()) on the preintegration of every inertial link (:456), then for every KeyFrame up to GetMaxKFid()
+// with nLoopId == 0 SetPose / SetVelocity / SetNewBias, otherwise mTcwGBA / mVwbGBA / mBiasGBA and mnBAGlobalForKF; for every point
+// that is a vertex SetWorldPos + UpdateNormalAndDepth, otherwise mPosGBA and mnBAGlobalForKF; IncreaseChangeIndex.  true = done,
+// including bFixLocal's nNonFixed < 3 return (:438-441, nothing touched) and the stop flag found set before optimize() (:683-685,
+// after the SetNewBias of :456 and before any write-back, as in the reference).
+//
+// false = NOT handled, nothing touched, the caller runs Optimizer::FullInertialBA: a KeyFrame with mpCamera2 (the arm :643-673), a
+// free KeyFrame without bImu, an inertial link without mpImuPreintegrated or whose covariance has no inverse, links that are no
+// chains (two KeyFrames with one mPrevKF), more free KeyFrames than msorb_full_inertial_ba_capacity(bInit), or a call in which a
+// factorisation of the reduced system met a pivot that was not positive (msorb_iba_result::reserved; a large map without a fixed
+// KeyFrame under lambda = 1e-5: the dense unpivoted solve cannot stand in for the reference's there).  The decision falls before the
+// first side effect: SetNewBias runs after the call has been accepted.
+//
+// The KeyFrames are handed over in ascending mnId (g2o's order of the unknowns), the inertial edges in the order of the reference's
+// loop over GetAllKeyFrames(), the points in the order of GetAllMapPoints().  With bInit the shared biases start at those of the
+// last KeyFrame the vertex loop visits (pIncKF, :399, :428-435).
+template <class KFPtr, class MPPtr>
+struct FullInertialBAProblem : BaEdges {
+    std::vector<KFPtr> vpKFs;                          // GetAllKeyFrames() up to maxKFid, in its order
+    std::vector<MPPtr> vpMPs;
+    std::vector<KFPtr> kf_of_index;                    // ascending mnId
+    std::vector<msorb_iba_keyframe> kfs;
+    std::vector<msorb_iba_inertial_edge> iedges;
+    std::vector<KFPtr> new_bias;                       // the KeyFrames whose preintegration receives SetNewBias (:456), in order
+    std::vector<float> pos_w;
+    msorb_fiba_problem prob;
+    bool handled = true, too_few = false;              // too_few: nNonFixed < 3
+};
+
+template <class MapT>
+auto GatherFullInertialBA(MapT* pMap, int its, bool bFixLocal, bool bInit, float priorG, float priorA) {
+    const auto all = pMap->GetAllKeyFrames();
+    const auto vpMPs = pMap->GetAllMapPoints();
+    typedef typename std::decay<decltype(all[0])>::type KFPtr;
+    typedef typename std::decay<decltype(vpMPs[0])>::type MPPtr;
+    FullInertialBAProblem<KFPtr, MPPtr> B;
+    std::memset(&B.prob, 0, sizeof B.prob);
+    B.prob.init = bInit ? 1 : 0;
+    B.prob.iterations = its;
+    B.prob.prior_g = priorG;
+    B.prob.prior_a = priorA;
+    const unsigned long maxKFid = pMap->GetMaxKFid();
+    auto refuse = [&] { B.handled = false; return B; };
+    // ---- the vertices (:393-441)
+    int nNonFixed = 0;
+    std::map<unsigned long, std::pair<KFPtr, int>> by_id;
+    KFPtr pIncKF;
+    for (const KFPtr& pKFi : all) {
+        if (pKFi->mnId > maxKFid) continue;
+        B.vpKFs.push_back(pKFi);
+        pIncKF = pKFi;
+        bool bFixed = false;
+        if (bFixLocal) {
+            bFixed = (pKFi->mnBALocalForKF >= (maxKFid - 1)) || (pKFi->mnBAFixedForKF >= (maxKFid - 1));
+            if (!bFixed) nNonFixed++;
+        }
+        if (pKFi->mpCamera2) return refuse();
+        if (!bFixed && !pKFi->bImu) return refuse();
+        by_id[pKFi->mnId] = {pKFi, bFixed ? (pKFi->bImu ? 1 : 2) : 0};
+    }
+    if (bFixLocal && nNonFixed < 3) { B.too_few = true; return B; }
+    std::map<KFPtr, int> index;
+    for (const auto& it : by_id) {
+        index[it.second.first] = (int)B.kfs.size();
+        B.kfs.push_back(IbaKeyFrame(it.second.first, it.second.second));
+        B.kf_of_index.push_back(it.second.first);
+    }
+    if (bInit && pIncKF) {
+        const auto bg = pIncKF->GetGyroBias();
+        const auto ba = pIncKF->GetAccBias();
+        for (int a = 0; a < 3; a++) { B.prob.bg0[a] = (double)bg(a); B.prob.ba0[a] = (double)ba(a); }
+    }
+    // ---- the inertial links (:444-526)
+    for (const KFPtr& pKFi : all) {
+        if (!pKFi->mPrevKF || pKFi->mnId > maxKFid) continue;
+        if (pKFi->isBad() || pKFi->mPrevKF->mnId > maxKFid) continue;
+        if (!(pKFi->bImu && pKFi->mPrevKF->bImu)) continue;                                                    // :523-524
+        if (!pKFi->mpImuPreintegrated) return refuse();
+        B.new_bias.push_back(pKFi);                                                                         // :456
+        const auto prev = index.find(pKFi->mPrevKF);
+        if (prev == index.end()) continue;                                                               // :478-489: a vertex is missing
+        msorb_iba_inertial_edge e;
+        std::memset(&e, 0, sizeof e);
+        if (!pose_inertial_detail::EdgeOf(pKFi->mpImuPreintegrated, e.pre)) return refuse();
+        if (!bInit && (!pose_inertial_detail::RandomWalkInformation(pKFi->mpImuPreintegrated, 9, e.info_gyro) ||
+                       !pose_inertial_detail::RandomWalkInformation(pKFi->mpImuPreintegrated, 12, e.info_acc)))
+            return refuse();
+        e.pre.kf_prev = prev->second;
+        e.pre.kf_cur = index[pKFi];
+        e.huber = 1;                                                                                     // :499-501
+        e.downweight = 0;
+        B.iedges.push_back(e);
+    }
+    // ---- the points and the visual edges (:556-681)
+    int nPoints = 0;
+    for (const MPPtr& pMP : vpMPs) {
+        B.vpMPs.push_back(pMP);
+        const auto Xw = pMP->GetWorldPos();
+        B.pos_w.push_back(Xw(0)); B.pos_w.push_back(Xw(1)); B.pos_w.push_back(Xw(2));
+        const auto observations = pMP->GetObservations();
+        for (const auto& ob : observations) {
+            KFPtr pKFi = ob.first;
+            if (pKFi->mnId > maxKFid || pKFi->isBad()) continue;
+            const auto at = index.find(pKFi);
+            if (at == index.end()) continue;
+            B.append(pKFi, std::get<0>(ob.second), at->second, nPoints);
+        }
+        nPoints++;
+    }
+    return B;
+}
+
+template <class MapT, class VecT = void>
+bool FullInertialBA(MapT* pMap, int its, const bool bFixLocal = false, const unsigned long nLoopId = 0, bool* pbStopFlag = nullptr,
+                    bool bInit = false, float priorG = 1e2, float priorA = 1e6, VecT* vSingVal = nullptr, bool* bHess = nullptr, int device = 0) {
+    (void)vSingVal; (void)bHess;
+    auto B = GatherFullInertialBA(pMap, its, bFixLocal, bInit, priorG, priorA);
+    if (!B.handled) return false;
+    if (B.too_few) return true;                                                                          // :438-441
+    const int K = (int)B.kfs.size(), P = (int)B.vpMPs.size(), E = (int)B.edge_kf.size(), NI = (int)B.iedges.size();
+    std::vector<msorb_iba_keyframe_out> kf_out((size_t)K);
+    std::vector<float> pos_out(3 * (size_t)P);
+    std::vector<uint8_t> included((size_t)P);
+    msorb_iba_result r;
+    int rc;
+    {
+        StopFlagMirror stop(pbStopFlag);
+        rc = msorb_full_inertial_ba(device, &B.prob, K, B.kfs.data(), NI, B.iedges.data(), P, B.pos_w.data(), E, B.edge_kf.data(),
+                                    B.edge_point.data(), B.xy.data(), B.u_right.data(), B.inv_sigma2.data(), stop.get(), kf_out.data(),
+                                    pos_out.data(), nullptr, included.data(), &r, nullptr);
+    }
+    if (rc == MSORB_E_CAPACITY) return false;
+    if (rc != MSORB_OK) fail_call("msorb_full_inertial_ba");
+    if (r.status == 0 && r.reserved != 0) return false;   // a factorisation failed: rounding decided the outcome, nothing touched yet
+    for (const auto& pKFi : B.new_bias) pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());        // :456
+    if (r.status != 0) return true;                                                                      // :683-685: no write-back
+    typedef typename std::decay<decltype(B.vpKFs[0])>::type KFPtr;
+    typedef typename std::decay<decltype(B.vpKFs[0]->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(B.vpKFs[0]->GetPose().rotationMatrix())>::type RotF;
+    typedef typename std::decay<decltype(B.vpKFs[0]->GetPose().translation())>::type VecF;
+    typedef typename std::decay<decltype(B.vpKFs[0]->GetVelocity())>::type VelF;
+    typedef typename std::decay<decltype(B.vpKFs[0]->GetImuBias())>::type BiasT;
+    std::map<KFPtr, int> index;
+    for (int k = 0; k < K; k++) index[B.kf_of_index[k]] = k;
+    for (const KFPtr& pKFi : B.vpKFs) {                                                                     // :694-734
+        const msorb_iba_keyframe_out& o = kf_out[index[pKFi]];
+        RotF Rf;
+        VecF tf;
+        VelF vf;
+        for (int a = 0; a < 3; a++) {
+            for (int b = 0; b < 3; b++) Rf(a, b) = o.Rcw_f[3 * a + b];
+            tf(a) = o.tcw_f[a];
+            vf(a) = o.v_f[a];
+        }
+        if (nLoopId == 0) pKFi->SetPose(SE3T(Rf, tf));
+        else { pKFi->mTcwGBA = SE3T(Rf, tf); pKFi->mnBAGlobalForKF = nLoopId; }
+        if (!pKFi->bImu) continue;
+        const BiasT b(o.bias_f[0], o.bias_f[1], o.bias_f[2], o.bias_f[3], o.bias_f[4], o.bias_f[5]);
+        if (nLoopId == 0) { pKFi->SetVelocity(vf); pKFi->SetNewBias(b); }
+        else { pKFi->mVwbGBA = vf; pKFi->mBiasGBA = b; }
+    }
+    if (P) {
+        typedef typename std::decay<decltype(B.vpMPs[0]->GetWorldPos())>::type PosT;
+        for (int p = 0; p < P; p++) {                                                                    // :737-753
+            if (!included[p]) continue;
+            const float* o = pos_out.data() + 3 * (size_t)p;
+            const auto& pMP = B.vpMPs[p];
+            if (nLoopId == 0) { pMP->SetWorldPos(PosT(o[0], o[1], o[2])); pMP->UpdateNormalAndDepth(); }
+            else { pMP->mPosGBA = PosT(o[0], o[1], o[2]); pMP->mnBAGlobalForKF = nLoopId; }
+        }
+    }
+    pMap->IncreaseChangeIndex();                                                                         // :755
+    return true;
+}
+
 }  // namespace msorb_host
 }  // namespace ORB_SLAM3
 

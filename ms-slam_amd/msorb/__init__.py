@@ -2706,3 +2706,73 @@ def local_inertial_ba(keyframes, inertial_edges, pos_w, point_close, edge_kf, ed
     if timing:
         r["elapsed_ms"] = ms.value
     return r
+
+
+# ---- Optimizer::FullInertialBA on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_full_inertial_ba_capacity", "msorb_full_inertial_ba", "msorb_full_inertial_ba_stage_ms")
+
+FIBA_PROBLEM_DTYPE = np.dtype([("init", "<i4"), ("iterations", "<i4"), ("prior_g", "<f4"), ("prior_a", "<f4"), ("bg0", "<f8", 3),
+                               ("ba0", "<f8", 3)])                                                         # msorb_fiba_problem
+assert FIBA_PROBLEM_DTYPE.itemsize == 64
+FIBA_STAGES = ("linearise", "assemble", "schur", "solve", "trial")
+
+
+def _fiba_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_full_inertial_ba_capacity.argtypes = [ci]
+    L.msorb_full_inertial_ba_stage_ms.argtypes = [vp]
+    L.msorb_full_inertial_ba.argtypes = [ci, vp, ci, vp, ci, vp, ci, vp, ci] + [vp] * 12
+    return L
+
+
+def full_inertial_ba_capacity(init):
+    """the largest number of free KeyFrames msorb_full_inertial_ba accepts in the form `init`"""
+    return _fiba_lib().msorb_full_inertial_ba_capacity(int(bool(init)))
+
+
+def full_inertial_ba_stage_ms():
+    """the calling thread's last call's device time per stage (FIBA_STAGES); needs MSORB_FULL_INERTIAL_BA_STAGES=1 in the environment"""
+    ms = np.zeros(5, np.float32)
+    _check(_fiba_lib().msorb_full_inertial_ba_stage_ms(_np_ptr(ms)), "msorb_full_inertial_ba_stage_ms")
+    return dict(zip(FIBA_STAGES, (float(v) for v in ms)))
+
+
+def full_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, init=False, iterations=7, prior_g=0.0,
+                     prior_a=0.0, bg0=(0, 0, 0), ba0=(0, 0, 0), stop_flag=None, device=0, timing=False, out=None):
+    """msorb_full_inertial_ba: Optimizer::FullInertialBA after its gathering loops, on the device.  keyframes: IBA_KF_DTYPE [K];
+    inertial_edges: IBA_EDGE_DTYPE [NI]; pos_w [P, 3]; the visual edges point-major as for local_inertial_ba.  init = bInit (one
+    shared bias pair starting at bg0 / ba0 under the priors prior_g / prior_a); stop_flag: an int32 array of one element the call
+    polls where g2o calls terminate() (that very memory: anything else is a TypeError), or None.  result["reserved"] counts
+    the trials whose factorisation met a pivot that was not positive.
+    -> dict(result: IBA_RESULT_DTYPE record, kf: IBA_KF_OUT_DTYPE [K], pos float32 [P, 3], pos_d float64 [P, 3], included bool [P])
+    and, with timing, elapsed_ms (device time).  out: (kf, pos, pos_d, included uint8) arrays to be written instead of fresh ones
+    (they keep their contents when the call is refused)."""
+    L = _fiba_lib()
+    kf = _c(keyframes, IBA_KF_DTYPE).reshape(-1)
+    ie = _c(inertial_edges, IBA_EDGE_DTYPE).reshape(-1)
+    pw = _c(pos_w, np.float32).reshape(-1)
+    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
+    px, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
+    P, E = len(pw) // 3, len(ek)
+    if len(pw) != 3 * P or [len(a) for a in (ep, px, ur, inv)] != [E, 2 * E, E, E]:
+        raise ValueError("pos_w or the edge arrays disagree in length")
+    pr = np.zeros(1, FIBA_PROBLEM_DTYPE)
+    pr["init"], pr["iterations"], pr["prior_g"], pr["prior_a"], pr["bg0"], pr["ba0"] = int(bool(init)), iterations, prior_g, prior_a, bg0, ba0
+    if out is None:
+        out = (np.zeros(max(len(kf), 1), IBA_KF_OUT_DTYPE), np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64),
+               np.zeros(max(P, 1), np.uint8))
+    kf_out, pos, pos_d, inc = out
+    flag = stop_flag
+    if flag is not None and not (isinstance(flag, np.ndarray) and flag.dtype == np.int32 and flag.size == 1 and flag.flags.c_contiguous):
+        raise TypeError("stop_flag must be a contiguous int32 numpy array of one element: the call polls that very memory")
+    res = np.zeros(1, IBA_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_full_inertial_ba(device, _np_ptr(pr), len(kf), _np_ptr(kf), len(ie), _np_ptr(ie), P, _np_ptr(pw), E, _np_ptr(ek),
+                                    _np_ptr(ep), _np_ptr(px), _np_ptr(ur), _np_ptr(inv), None if flag is None else _np_ptr(flag),
+                                    _np_ptr(kf_out), _np_ptr(pos), _np_ptr(pos_d), _np_ptr(inc), _np_ptr(res), C.addressof(ms)),
+           "msorb_full_inertial_ba")
+    r = dict(result=res[0], kf=kf_out[:len(kf)], pos=pos[:P], pos_d=pos_d[:P], included=inc[:P].astype(bool))
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r

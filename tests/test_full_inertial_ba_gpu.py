@@ -1,0 +1,266 @@
+"""Optimizer::FullInertialBA on the device (csrc/full_inertial_ba.hip) through the C ABI and its Python mirror, against the forward
+restatement of tests/full_inertial_ba_cases.py and against the host program (the same header through g++ and glibc, a serial
+executor, the column-by-column solve).
+
+Bounds: those of tests/test_full_inertial_ba_cpu.py: 16 D of the scene's own group (with / without a fixed KeyFrame), D from
+tests/golden/full_inertial_ba_sensitivity.json; status, iterations, trials, rejected trials and point_included are equal (the CPU
+test shows that no accept / reject decision comes within 100 times the cost spread).  Byte-equality with the host program is printed,
+not required.  The two scenes whose stop flag is raised by a hand-made hook in mid-call (stop_trial, stop_iteration) run in the host
+program only: the C entry polls a flag it is given, and a flag that is set before the call is tested here."""
+import ctypes as C
+import os
+import subprocess
+import threading
+
+import numpy as np
+import pytest
+
+import full_inertial_ba_cases as fc
+import local_inertial_ba_cases as lc
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ALL = tuple(n for n in fc.ALL if "stop_trials" not in fc._SCENES[n][3] and "stop_iteration" not in fc._SCENES[n][3])
+
+
+def _args(sc):
+    return (sc["kf"], sc["ie"], sc["pos"], sc["edge_kf"], sc["edge_pt"], sc["xy"], sc["ur"], sc["inv"])
+
+
+def _run(msorb_mod, sc, **kw):
+    return msorb_mod.full_inertial_ba(*_args(sc), init=bool(sc["init"]), iterations=int(sc["iterations"]), prior_g=sc["prior_g"],
+                                      prior_a=sc["prior_a"], bg0=sc["bg0"], ba0=sc["ba0"], **kw)
+
+
+def _as_result(r):
+    return fc.from_records(r["result"], r["kf"], r["pos_d"], r["included"])
+
+
+@pytest.fixture(scope="module")
+def host_results(tmp_path_factory):
+    d = tmp_path_factory.mktemp("full_inertial_ba_gpu")
+    exe = str(d / "full_inertial_ba_main")
+    b = subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-O2", os.path.join(ROOT, "tests", "full_inertial_ba_main.cc"), "-o", exe],
+                       capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr
+    scenes = [fc.scene(n) for n in ALL]
+    fc.write_scenes(str(d / "in.bin"), scenes)
+    p = subprocess.run([exe, str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, (p.stdout[-400:], p.stderr[-2000:])
+    return dict(zip(ALL, fc.read_results(str(d / "out.bin"), scenes)))
+
+
+def test_capacity_and_records_are_what_the_scenes_assume(msorb_mod):
+    assert msorb_mod.full_inertial_ba_capacity(0) == fc.CAPACITY[0] == 7168 // 15
+    assert msorb_mod.full_inertial_ba_capacity(1) == fc.CAPACITY[1] == (7168 - 6) // 9
+    assert msorb_mod.FIBA_PROBLEM_DTYPE == fc.FIBA_PROBLEM_DTYPE and msorb_mod.IBA_KF_DTYPE == lc.KF_DTYPE
+    assert all(hasattr(msorb_mod.lib(), s) for s in ("msorb_full_inertial_ba", "msorb_full_inertial_ba_capacity", "msorb_full_inertial_ba_stage_ms"))
+
+
+def _compare(name, sc, r, other, what):
+    g = fc.golden()["D_no_fixed" if name in fc.NO_FIXED else "D_fixed"]
+    d = fc.differences(other, r, sc)
+    print(f"{name}: device / {what}: {fc.decisions(r)[:4]} / {fc.decisions(other)[:4]}, in D: " + " ".join(f"{q} {d[q] / g[q]:.3f}" for q in d))
+    assert fc.decisions(r) == fc.decisions(other), (name, what)
+    assert fc.within(d, fc.bounds(name)), (name, what, d, fc.bounds(name))
+
+
+@pytest.mark.parametrize("name", ALL)
+def test_device_against_the_restatement_and_the_host_program(msorb_mod, host_results, name):
+    sc = fc.scene(name)
+    out = _run(msorb_mod, sc)
+    r = _as_result(out)
+    _compare(name, sc, r, fc.reference(name), "restatement")
+    rec, ko, h = host_results[name]
+    _compare(name, sc, r, h, "host program")
+    same = out["kf"].tobytes() == ko.tobytes() and np.array_equal(out["pos_d"], h["pts"]) and out["result"].tobytes() == rec.tobytes()
+    print(f"{name}: device == host program bytes: {same}")
+    # a second call returns the same bits
+    again = _run(msorb_mod, sc)
+    for k in ("kf", "pos", "pos_d", "included"):
+        assert out[k].tobytes() == again[k].tobytes(), (name, k)
+    assert out["result"].tobytes() == again["result"].tobytes()
+    # the narrowed outputs, the bias in the reference's order (acc, then gyro), a fixed KeyFrame's repeat its input
+    kf, kind = out["kf"], sc["kf"]["kind"]
+    for k in ("Rcw", "tcw", "v"):
+        assert np.array_equal(kf[k + "_f"], kf[k].astype(np.float32)), (name, k)
+    assert np.array_equal(kf["bias_f"], np.concatenate([kf["ba"], kf["bg"]], 1).astype(np.float32))
+    assert np.array_equal(out["pos"], out["pos_d"].astype(np.float32))
+    fixed = kind != 0
+    for k in ("Rwb", "twb", "Rcw", "tcw", "v"):
+        assert np.array_equal(kf[k][fixed], sc["kf"][k][fixed]), (name, k)
+    if sc["init"]:                                                             # every KeyFrame's bias output is the same six numbers
+        assert (kf["bg"] == kf["bg"][0]).all() and (kf["ba"] == kf["ba"][0]).all() and (kind != 2).all()
+        assert not np.array_equal(kf["bg"][0], sc["bg0"]) and not np.array_equal(kf["ba"][0], sc["ba0"])
+    else:
+        assert np.array_equal(kf["bg"][fixed], sc["kf"]["bg"][fixed]) and np.array_equal(kf["ba"][fixed], sc["kf"]["ba"][fixed])
+    left_out = ~out["included"]
+    assert np.array_equal(out["pos"][left_out], sc["pos"][left_out])
+    assert int(out["result"]["n_outliers"]) == 0 and out["result"]["err"] == 0 and out["result"]["err_end"] == 0
+
+
+@pytest.mark.parametrize("name", fc.LIMIT)
+def test_free_gauge_maps_outside_the_comparison_run_and_repeat_their_bits(msorb_mod, name):
+    """16, 26 and 40 free KeyFrames, none fixed, init = 0: the restatement's own variants disagree there (the CPU test pins it), so the
+    estimates are printed, not compared.  What holds: the call runs, two calls return equal bits, `reserved` counts the failed
+    factorisations (never more than the trials), every output is finite."""
+    sc = fc.scene(name)
+    out, again = _run(msorb_mod, sc), _run(msorb_mod, sc)
+    res, ref = out["result"], fc.reference(name)
+    d = fc.differences(ref, _as_result(out), sc)
+    print(f"{name}: device {fc.decisions(_as_result(out))[:4]} failed solves {int(res['reserved'])}; restatement {fc.decisions(ref)[:4]} failed solves "
+          f"{ref['solver_failures']}; differences " + " ".join(f"{q} {v:.2g}" for q, v in d.items()))
+    assert int(res["status"]) == 0 and 1 <= int(res["iterations"]) <= sc["iterations"] and 0 <= int(res["reserved"]) <= int(res["trials"])
+    for k in ("kf", "pos_d", "included"):
+        assert out[k].tobytes() == again[k].tobytes(), (name, k)
+    assert res.tobytes() == again["result"].tobytes()
+    assert np.isfinite(out["pos_d"]).all() and all(np.isfinite(out["kf"][k]).all() for k in ("Rwb", "twb", "v", "bg", "ba"))
+
+
+def _outputs_repeat_inputs(sc, out):
+    for k in ("Rwb", "twb", "Rcw", "tcw", "v", "bg", "ba"):
+        assert np.array_equal(out["kf"][k], sc["kf"][k]), k
+    assert np.array_equal(out["kf"]["Rcw_f"], sc["kf"]["Rcw"].astype(np.float32))
+    assert np.array_equal(out["pos"], sc["pos"]) and np.array_equal(out["pos_d"], sc["pos"].astype(np.float64)) and not out["included"].any()
+
+
+def test_status_2_and_status_3_leave_every_output_equal_to_its_input(msorb_mod):
+    for name in ("f3", "i10"):                                                 # the flag is set before optimize()
+        sc = fc.scene(name)
+        out = _run(msorb_mod, sc, stop_flag=np.ones(1, np.int32))
+        assert int(out["result"]["status"]) == 3 and int(out["result"]["iterations"]) == 0 and int(out["result"]["trials"]) == 0
+        _outputs_repeat_inputs(sc, out)
+        assert fc.optimize(sc, stop_trials=0)["status"] == 3
+        clear = _run(msorb_mod, sc, stop_flag=np.zeros(1, np.int32))           # a flag that stays clear changes nothing
+        assert clear["kf"].tobytes() == _run(msorb_mod, sc)["kf"].tobytes() and int(clear["result"]["status"]) == 0
+    base = fc.scene("f3")                                                      # status 2: init = 0 without a free KeyFrame
+    kf = base["kf"].copy()
+    kf["kind"] = 1
+    sc2 = dict(base, kf=kf)
+    out = _run(msorb_mod, sc2)
+    assert int(out["result"]["status"]) == 2 and fc.optimize(sc2)["status"] == 2
+    _outputs_repeat_inputs(sc2, out)
+    # the same KeyFrames with init = 1: the shared pair is free, the inertial edges are active, no point is a vertex
+    sc3 = dict(sc2, init=1, iterations=1, prior_g=np.float32(1.0), prior_a=np.float32(1.0))   # (its third iteration gains 3e-8 of the cost: the float floor)
+    out, ref = _run(msorb_mod, sc3), fc.optimize(sc3)
+    r = _as_result(out)
+    assert fc.decisions(r) == fc.decisions(ref) and ref["status"] == 0 and ref["iterations"] >= 1 and not out["included"].any()
+    assert fc.within(fc.differences(ref, r, sc3), fc.bounds("i_fixed"))
+    assert (out["kf"]["bg"] == out["kf"]["bg"][0]).all() and (out["kf"]["ba"] == out["kf"]["ba"][0]).all()
+    assert not np.array_equal(out["kf"]["bg"][0], sc3["bg0"]) and ref["rejected_trials"] == 0   # (under the call sites' priors every trial is rejected here)
+
+
+def test_two_host_threads_at_once(msorb_mod):
+    names = ("f4", "i10")
+    single = {n: _run(msorb_mod, fc.scene(n)) for n in names}
+    got, errors = {}, []
+
+    def work(n):
+        try:
+            for _ in range(3):
+                got[n] = _run(msorb_mod, fc.scene(n))
+        except Exception as e:  # noqa: BLE001
+            errors.append((n, e))
+    threads = [threading.Thread(target=work, args=(n,)) for n in names]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for n in names:
+        for k in ("kf", "pos_d", "included"):
+            assert got[n][k].tobytes() == single[n][k].tobytes(), (n, k)
+        assert got[n]["result"].tobytes() == single[n]["result"].tobytes()
+
+
+def _sentinels(sc):
+    K, P = len(sc["kf"]), len(sc["pos"])
+    kf = np.zeros(max(K, 1), lc.KF_OUT_DTYPE)
+    kf.view(np.uint8)[:] = 0xA5
+    return (kf, np.full((max(P, 1), 3), 7.5, np.float32), np.full((max(P, 1), 3), 7.5), np.full(max(P, 1), 9, np.uint8))
+
+
+def _refused(msorb_mod, sc, code):
+    out = _sentinels(sc)
+    before = [a.copy() for a in out]
+    with pytest.raises(msorb_mod.MsorbError) as ei:
+        _run(msorb_mod, sc, out=out)
+    assert ei.value.code == code, (ei.value.code, str(ei.value))
+    for a, b in zip(out, before):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_one_more_free_keyframe_than_the_capacity(msorb_mod):
+    base = fc.scene("f3")
+    e, f = np.zeros(0, np.int32), np.zeros(0, np.float32)
+    for init in (0, 1):                                                        # only what the check reads: the KeyFrames' records
+        kf = np.zeros(fc.CAPACITY[init] + 1, lc.KF_DTYPE)
+        sc = dict(base, init=init, kf=kf, ie=base["ie"][:0], pos=np.zeros((0, 3), np.float32), edge_kf=e, edge_pt=e, xy=np.zeros((0, 2), np.float32), ur=f, inv=f)
+        _refused(msorb_mod, sc, -4)
+    ie = np.concatenate([base["ie"], base["ie"][-1:]])                         # edges that do not form chains are "not handled" too
+    _refused(msorb_mod, dict(base, ie=ie), -4)
+
+
+def test_every_argument_error_is_refused_with_nothing_written(msorb_mod):
+    base = fc.scene("f_fixed")
+    K, P = len(base["kf"]), len(base["pos"])
+
+    def edit(key, fn):
+        a = base[key].copy()
+        fn(a)
+        return dict(base, **{key: a})
+
+    def set_at(i, v):
+        return lambda a: a.__setitem__(i, v)
+
+    def kind2(a):
+        a["kind"][0] = 2
+    cases = {
+        "edge_kf out of range": edit("edge_kf", set_at(5, K)),
+        "edge_kf negative": edit("edge_kf", set_at(5, -1)),
+        "edge_point out of range": edit("edge_pt", set_at(-1, P)),
+        "not point-major": edit("edge_pt", lambda a: a.__setitem__(slice(None), a[::-1].copy())),
+        "non-finite point": edit("pos", set_at((3, 1), np.nan)),
+        "non-finite observation": edit("xy", set_at((0, 0), np.inf)),
+        "non-finite weight": edit("inv", set_at(0, np.nan)),
+        "unknown kind": edit("kf", lambda a: a["kind"].__setitem__(1, 3)),
+        "non-finite KeyFrame": edit("kf", lambda a: a["twb"].__setitem__((1, 0), np.nan)),
+        "inertial edge out of range": edit("ie", lambda a: a["pre"]["kf_cur"].__setitem__(0, K)),
+        "inertial edge to itself": edit("ie", lambda a: a["pre"]["kf_cur"].__setitem__(0, int(a["pre"]["kf_prev"][0]))),
+        "inertial edge on a kind 2 KeyFrame": edit("kf", kind2),
+        "non-finite information": edit("ie", lambda a: a["pre"]["info"].__setitem__((1, 4), np.nan)),
+        "negative iterations": dict(base, iterations=-1),
+        "non-finite prior": dict(base, prior_a=np.float32(np.inf)),
+        "non-finite shared bias": dict(base, bg0=np.array([0.0, np.nan, 0.0])),
+    }
+    for what, sc in cases.items():
+        print(what)
+        _refused(msorb_mod, sc, -1)
+    # a null required pointer, a negative count and an unknown init need the C entry itself
+    L = msorb_mod.lib()
+    out = _sentinels(base)
+    before = [a.copy() for a in out]
+    res = np.zeros(1, lc.RESULT_DTYPE)
+    pr = fc.problem_record(base)
+    ptr = lambda a: np.ascontiguousarray(a).ctypes.data_as(C.c_void_p)  # noqa: E731
+    keep = [np.ascontiguousarray(a) for a in _args(base)]
+    kf, ie, pos, ek, ep, xy, ur, inv = keep
+    full = [0, ptr(pr), K, ptr(kf), len(ie), ptr(ie), P, ptr(pos), len(ek), ptr(ek), ptr(ep), ptr(xy), ptr(ur), ptr(inv), None,
+            ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(res), None]
+    L.msorb_full_inertial_ba.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 12
+    for i in (1, 3, 5, 7, 9, 10, 11, 12, 13, 15, 16, 18, 19):                  # every required pointer (stop_flag, pos_d, elapsed_ms are optional)
+        a = list(full)
+        a[i] = None
+        assert L.msorb_full_inertial_ba(*a) == -1, i
+    for i in (2, 4, 6, 8):
+        a = list(full)
+        a[i] = -1
+        assert L.msorb_full_inertial_ba(*a) == -1, i
+    bad = pr.copy()
+    bad["init"] = 2
+    a = list(full)
+    a[1] = ptr(bad)
+    assert L.msorb_full_inertial_ba(*a) == -1
+    for a, b in zip(out, before):
+        assert a.tobytes() == b.tobytes()
+    assert not res.view(np.uint8).any()
