@@ -1501,7 +1501,7 @@ int msorb_frame_pose_inertial_optimization(msorb_frame* f, const msorb_pose_iner
                                            uint8_t* outlier, msorb_pose_inertial_result* r);
 
 /* Optimizer::LocalInertialBA (src/Optimizer.cc:2431-2973) after its gathering loops, on the device, for pinhole KeyFrames without a
- * second camera (the mpCamera2 arm of :2820-2853 is not restated; FullInertialBA is msorb_full_inertial_ba below, MergeInertialBA is not restated): EdgeMono /
+ * second camera (the mpCamera2 arm of :2820-2853 is not restated; FullInertialBA is msorb_full_inertial_ba below, MergeInertialBA msorb_merge_inertial_ba): EdgeMono /
  * EdgeStereo over ImuCamPose and the points, EdgeInertial, EdgeGyroRW and EdgeAccRW along the chain of KeyFrames, g2o's Levenberg
  * with setUserLambdaInit, the points eliminated by the Schur complement, in double with the preintegration's bias correction in
  * float as the reference has it.  The whole optimize() is ONE launch of one workgroup.  Appended to ABI 6002: MSORB_ABI_VERSION
@@ -1510,8 +1510,9 @@ int msorb_frame_pose_inertial_optimization(msorb_frame* f, const msorb_pose_iner
  * iterations > 0 replaces the 4 / 10.
  * kfs [n_kf]: everything VertexPose(pKF) / ImuCamPose(pKF) reads, in the conventions of msorb_pose_inertial_problem: Rcw / tcw =
  * GetPose() widened, not derived.  kind: 0 = free, with pose, velocity and both biases (15 unknowns); 1 = fixed, with inertial
- * vertices (the KeyFrame before the window, or the window's oldest without mPrevKF); 2 = fixed pose only.  A free KeyFrame without
- * inertial vertices cannot be stated: the caller does not hand such a window over.
+ * vertices (the KeyFrame before the window, or the window's oldest without mPrevKF); 2 = fixed pose only; 3 = free pose only (6
+ * unknowns), which msorb_merge_inertial_ba alone accepts: here and in msorb_full_inertial_ba a kind above 2 is MSORB_E_INVALID,
+ * and the caller does not hand such a window over.
  * iedges [n_inertial]: pre.kf_prev / pre.kf_cur index kfs; pre.info = the full 9x9 of EdgeInertial's constructor; info_gyro /
  * info_acc (:2673, :2680) row major; huber: RobustKernelHuber of delta sqrt(16.92) (:2657-2667); downweight: information() *
  * 1e-2, applied in double inside the library (:2665).  One incoming and one outgoing edge per KeyFrame, no cycle: anything else
@@ -1596,6 +1597,41 @@ int msorb_full_inertial_ba(int device, const msorb_fiba_problem* p, int n_kf, co
                            const int* edge_point, const float* xy, const float* u_right, const float* inv_sigma2,
                            const volatile int* stop_flag, msorb_iba_keyframe_out* kf_out, float* pos_out, double* pos_d,
                            uint8_t* point_included, msorb_iba_result* r, float* elapsed_ms);
+
+/* Optimizer::MergeInertialBA (src/Optimizer.cc:3918-4420) after its gathering loops, on the device, for pinhole KeyFrames without a
+ * second camera: the welding bundle adjustment that LoopClosing runs when two inertial maps are merged.  The engine is
+ * msorb_full_inertial_ba's (init = 0): the host drives g2o's Levenberg loop launch by launch and looks at *stop_flag (may be NULL)
+ * where g2o calls terminate(); the blocked L D L^T solves the reduced system.  Appended to ABI 6002: MSORB_ABI_VERSION stays 6002.
+ * kfs: msorb_local_inertial_ba's records with one more kind.  kind 0: both temporal windows and the covisible KeyFrame an inertial
+ * edge reaches (15 unknowns); kind 3: a covisible KeyFrame whose pose is free and whose velocity and bias vertices no edge reaches
+ * (g2o's active set leaves them out): 6 unknowns, its v / bg / ba outputs repeat the input; kind 1 / 2: fixed.  Unknowns: 6 per free
+ * KeyFrame, then 9 per free KeyFrame of kind 0.  A free KeyFrame that no edge reaches is no vertex: it has no row and its output
+ * repeats its input.  (A kind 0 KeyFrame that only visual edges reach keeps its nine rows, which nothing moves; g2o would number it
+ * as a kind 3, and msorb_host::MergeInertialBA hands it over as one.)  A point none of whose edges ends at a free KeyFrame is no vertex either: point_included = 0, its position
+ * repeats and its edges are not flagged.
+ * iedges: huber / downweight are honoured as given (the reference: huber on every edge, no downweight, :4158-4185).  An inertial
+ * edge on a kind 2 or kind 3 KeyFrame is MSORB_E_INVALID.  Several disjoint chains are normal; forks and cycles are
+ * MSORB_E_CAPACITY, as are more unknowns than msorb_merge_inertial_ba_capacity() (7168, the side of the blocked solve's square).
+ * Visual edges: point-major; u_right >= 0 = EdgeStereo; inv_sigma2 = mvInvLevelSigma2[octave] (:4272, :4293: no division by unc2).
+ * problem: iterations > 0 replaces the 8 of :4317; large is ignored.  lambda starts at 1e3 (:4047).  No second round, no FAIL rule.
+ * edge_outlier [n_edges] = vToErase: chi2() > 5.991f (mono) / 7.815f (stereo) and NO depth test (:4322-4349).  chi2() is read
+ * without computeError(): it belongs to the state the last trial wrote, accepted or not, as in msorb_local_inertial_ba.
+ * Result: status 0 = optimised; 2 = nothing to optimise (no free KeyFrame that an edge reaches); 3 = *stop_flag was set before
+ * optimize() (:4312-4314), or it rose before the first iteration began: g2o would then complete zero iterations and the reference
+ * would classify errors that were never computed, so that call too is handed back untouched.  With 2 and 3 every output repeats its
+ * input and no flag is set.  n_outliers = flags set; reserved = trials whose factorisation met a pivot that was not positive, as
+ * msorb_full_inertial_ba counts them; err, err_end = 0.
+ * Errors as msorb_local_inertial_ba's, before any launch and with no output written.  Two calls on the same input return the same
+ * bits.  Re-entrant per calling thread.  *elapsed_ms (may be NULL): device time.  msorb_merge_inertial_ba_stage_ms: with
+ * MSORB_MERGE_INERTIAL_BA_STAGES=1 in the environment, the calling thread's last call's device time per stage, as
+ * msorb_full_inertial_ba_stage_ms. */
+int msorb_merge_inertial_ba_capacity(void);            /* unknowns: 7168 */
+int msorb_merge_inertial_ba_stage_ms(float ms[5]);
+int msorb_merge_inertial_ba(int device, const msorb_iba_problem* p, int n_kf, const msorb_iba_keyframe* kfs, int n_inertial,
+                            const msorb_iba_inertial_edge* iedges, int n_points, const float* pos_w, int n_edges, const int* edge_kf,
+                            const int* edge_point, const float* xy, const float* u_right, const float* inv_sigma2,
+                            const volatile int* stop_flag, msorb_iba_keyframe_out* kf_out, float* pos_out, double* pos_d,
+                            uint8_t* edge_outlier, uint8_t* point_included, msorb_iba_result* r, float* elapsed_ms);
 
 #ifdef __cplusplus
 }

@@ -53,16 +53,26 @@ struct Work {
     int n_fp;                      // inertial edges with both KeyFrames free
     int bias_kf;                   // a KeyFrame whose copy of the shared pair the priors read
     const int* fp_edge;            // [n_fp], ascending
+    // A free KeyFrame without inertial vertices (kind 3, merge_inertial_ba_device.h) has its six pose unknowns alone.  inert_of_free
+    // [Kf]: a free KeyFrame's index among those that have the `per` further unknowns, or -1; free_of_inert [Ki]: back.  Both null:
+    // every free KeyFrame has them (FullInertialBA).
+    const int *inert_of_free, *free_of_inert;
     double prior_g, prior_a;
     Res* res;
 };
 
-SE3_HD int places(const Work& F) { return 6 + F.per; }
-SE3_HD int unknown_at(const Work& F, int i, int u) { return u < 6 ? 6 * i + u : 6 * F.L.Kf + F.per * i + (u - 6); }
+SE3_HD int places(const Work& F) { return 6 + F.per; }                     // of a free KeyFrame that has inertial vertices
+SE3_HD int inert_of(const Work& F, int i) { return F.inert_of_free ? F.inert_of_free[i] : i; }
+SE3_HD int places(const Work& F, int i) { return inert_of(F, i) >= 0 ? 6 + F.per : 6; }
+SE3_HD int unknown_at(const Work& F, int i, int u) { return u < 6 ? 6 * i + u : 6 * F.L.Kf + F.per * inert_of(F, i) + (u - 6); }
 SE3_HD void unknown_of(const Work& F, int r, int& i, int& u) {
     const int np = 6 * F.L.Kf;
     if (r < np) { i = r / 6; u = r % 6; }
-    else { i = (r - np) / F.per; u = 6 + (r - np) % F.per; }
+    else {
+        const int j = (r - np) / F.per;
+        i = F.free_of_inert ? F.free_of_inert[j] : j;
+        u = 6 + (r - np) % F.per;
+    }
 }
 
 // the inertial edges at KeyFrame k, ascending: the one that ends there comes before the one that starts there exactly when its
@@ -178,6 +188,7 @@ SE3_HD void pass_prepare(Exec& ex, const Work& F, double lambda) {
             int a = 0;                                   // q-th entry of the lower triangle: row a, column b
             while ((a + 1) * (a + 2) / 2 <= q) a++;
             const int b = q - a * (a + 1) / 2;
+            if (a >= places(F, i)) continue;             // a KeyFrame without inertial vertices: its pose block alone
             const int r = unknown_at(F, i, a), c = unknown_at(F, i, b);   // (a >= b gives r >= c)
             const double v = entry_self(F, i, a, b);
             W.S[(size_t)r * n + c] = r == c ? v + lambda : v;
@@ -229,7 +240,7 @@ SE3_HD void pass_update(Exec& ex, const Work& F, int from, int to, double lambda
             Vertices V = W.st[from][k];
             if (i >= 0) {
                 double sc = 0;
-                for (int a = 0; a < places(F); a++) {
+                for (int a = 0; a < places(F, i); a++) {
                     const int r = unknown_at(F, i, a);
                     u[a] = W.x[r];
                     sc += u[a] * (lambda * u[a] + W.bA[r]);
@@ -278,6 +289,7 @@ struct Problem {
     std::string why;
     int Kf = 0, n = 0, P = 0, E = 0, n_active = 0;
     std::vector<int> fixed, e_in, e_out, fp_edge, point_of, edge_of;   // point_of / edge_of: the included ones' caller indices
+    std::vector<int> inert_of_free, free_of_inert;                      // max_kind = 3 alone (Work::inert_of_free)
     std::vector<uint8_t> included;                                      // [n_points]
     std::vector<int> ekf, ept;                                          // the included edges, points renumbered
     LocalBaPlan plan;
@@ -287,14 +299,19 @@ inline void refuse(Problem& q, int code, const char* why) { q.code = code; q.why
 
 // The graph of one call.  A point none of whose edges ends at a free KeyFrame is no vertex and its edges do not count
 // (Optimizer.cc:677-680); the inertial edges must be chains.
+//
+// max_kind = 3 (MergeInertialBA): kind 3 is a free pose without inertial vertices, 6 unknowns; a free KeyFrame that no active edge
+// reaches is no vertex (g2o's active set) and is planned as a fixed one: no row, its output repeats its input; the capacity is the
+// number of unknowns.
 inline void plan_problem(int init, int K, const msorb_iba_keyframe* kfs, int NI, const msorb_iba_inertial_edge* ie, int n_points, int n_edges,
-                         const int* edge_kf, const int* edge_point, Problem& q) {
+                         const int* edge_kf, const int* edge_point, Problem& q, int max_kind = 2) {
     q = Problem();
     q.fixed.resize((size_t)K);
     for (int k = 0; k < K; k++) {
-        if (kfs[k].kind < 0 || kfs[k].kind > 2) return refuse(q, 1, "an unknown kind (0 free, 1 fixed with inertial vertices, 2 fixed pose)");
-        q.fixed[k] = kfs[k].kind != 0;
-        q.Kf += kfs[k].kind == 0;
+        if (kfs[k].kind < 0 || kfs[k].kind > max_kind)
+            return refuse(q, 1, max_kind == 2 ? "an unknown kind (0 free, 1 fixed with inertial vertices, 2 fixed pose)"
+                                              : "an unknown kind (0 free, 1 fixed with inertial vertices, 2 fixed pose, 3 free pose only)");
+        q.fixed[k] = kfs[k].kind != 0 && kfs[k].kind != 3;
     }
     q.e_in.assign((size_t)K, -1);
     q.e_out.assign((size_t)K, -1);
@@ -303,7 +320,7 @@ inline void plan_problem(int init, int K, const msorb_iba_keyframe* kfs, int NI,
         const int a = ie[i].pre.kf_prev, b = ie[i].pre.kf_cur;
         if (a < 0 || a >= K || b < 0 || b >= K) return refuse(q, 1, "an inertial edge names a KeyFrame out of range");
         if (a == b) return refuse(q, 1, "an inertial edge from a KeyFrame to itself");
-        if (kfs[a].kind == 2 || kfs[b].kind == 2) return refuse(q, 1, "an inertial edge on a KeyFrame without inertial vertices (kind 2)");
+        if (kfs[a].kind >= 2 || kfs[b].kind >= 2) return refuse(q, 1, "an inertial edge on a KeyFrame without inertial vertices (kind 2 or 3)");
         if (q.e_out[a] >= 0 || q.e_in[b] >= 0) chains = false;
         q.e_out[a] = i;
         q.e_in[b] = i;
@@ -321,8 +338,29 @@ inline void plan_problem(int init, int K, const msorb_iba_keyframe* kfs, int NI,
         chains = reached == NI;
     }
     if (!chains) return refuse(q, 2, "the inertial edges do not form chains (one incoming and one outgoing edge per KeyFrame)");
-    if (q.Kf > capacity(init)) return refuse(q, 2, "more free KeyFrames than msorb_full_inertial_ba_capacity()");
-    q.n = init ? 9 * q.Kf + 6 : 15 * q.Kf;
+    if (max_kind == 3) {
+        std::vector<uint8_t> reached((size_t)K, 0);
+        for (int e = 0; e < n_edges; e++) reached[edge_kf[e]] = 1;
+        for (int i = 0; i < NI; i++) reached[ie[i].pre.kf_prev] = reached[ie[i].pre.kf_cur] = 1;
+        for (int k = 0; k < K; k++)
+            if (!reached[k]) q.fixed[k] = 1;
+    }
+    int Ki = 0;
+    for (int k = 0; k < K; k++) {
+        if (q.fixed[k]) continue;
+        q.Kf++;
+        if (max_kind == 3) {
+            q.inert_of_free.push_back(kfs[k].kind == 0 ? Ki : -1);
+            if (kfs[k].kind == 0) { q.free_of_inert.push_back(q.Kf - 1); Ki++; }
+        }
+    }
+    if (max_kind == 3) {
+        q.n = 6 * q.Kf + 9 * Ki;
+        if (q.n > kMaxN) return refuse(q, 2, "more unknowns than msorb_merge_inertial_ba_capacity()");
+    } else {
+        if (q.Kf > capacity(init)) return refuse(q, 2, "more free KeyFrames than msorb_full_inertial_ba_capacity()");
+        q.n = init ? 9 * q.Kf + 6 : 15 * q.Kf;
+    }
     q.included.assign((size_t)n_points, 0);
     for (int e = 0; e < n_edges; e++)
         if (!q.fixed[edge_kf[e]]) q.included[edge_point[e]] = 1;

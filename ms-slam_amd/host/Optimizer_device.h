@@ -2059,6 +2059,279 @@ bool FullInertialBA(MapT* pMap, int its, const bool bFixLocal = false, const uns
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Optimizer::MergeInertialBA (src/Optimizer.cc:3918-4420; LoopClosing.cc:1567, :1995) on msorb_merge_inertial_ba.
+//
+//   bool ORB_SLAM3::msorb_host::MergeInertialBA(pCurrKF, pMergeKF, pbStopFlag, pMap, corrPoses)
+//
+// the reference's parameter list and its effects: the marks of the gathering walk, SetNewBias(mPrevKF->GetImuBias()) on the
+// preintegration of every inertial link (:4142), the flagged observations erased, then for both windows and for the covisible
+// KeyFrames SetPose, corrPoses[pKFi] = Sim3(GetPose() widened, 1.0) and, with bImu, SetVelocity / SetNewBias (acc, then gyro); for
+// every local point SetWorldPos + UpdateNormalAndDepth; IncreaseChangeIndex.  true = done, including the stop flag found set before
+// optimize() (:4312-4314: after the marks and the SetNewBias of :4142, before any write-back, as in the reference).
+//
+// false = NOT handled, nothing touched (the marks are put back), the caller runs Optimizer::MergeInertialBA: a KeyFrame with
+// mpCamera2; a window KeyFrame with mPrevKF for which the reference would print its error (no bImu on either end, no
+// mpImuPreintegrated, a covariance without inverse, mPrevKF not among the vertices); vertex ids that would collide in g2o (a
+// gathered KeyFrame with mnId > maxKFid, a KeyFrame gathered twice, maxKFid <= 2: the ids are mnId, maxKFid + 3 mnId + 1..3 and
+// 5 maxKFid + mnId + 1); links that are no chains or more unknowns than msorb_merge_inertial_ba_capacity(); nothing to optimise; a
+// call in which a factorisation met a pivot that was not positive (msorb_iba_result::reserved); and a flag that rose after the
+// gathering and before the first iteration (status 3 without the flag having been set here: the reference would classify errors
+// that were never computed).
+//
+// A KeyFrame's kind follows g2o's active set: free with an inertial edge at it = 0, free without = 3 (its velocity and bias
+// vertices are in the reference's graph but no edge reaches them), fixed = 1 with bImu, else 2.  The KeyFrames are handed over in
+// ascending mnId (g2o's order of the unknowns: every pose id is below every velocity / bias id), the inertial edges in the order of
+// the loop over vpOptimizableKFs, the points in the order of lLocalMapPoints.
+template <class KFPtr, class MPPtr>
+struct MergeInertialBAProblem : BaEdges {
+    std::vector<KFPtr> vpOptimizableKFs, vpOptimizableCovKFs;
+    std::list<KFPtr> lFixedKeyFrames;
+    std::list<MPPtr> lLocalMapPoints;
+    std::vector<KFPtr> kf_of_index;                    // ascending mnId
+    std::vector<msorb_iba_keyframe> kfs;
+    std::vector<msorb_iba_inertial_edge> iedges;
+    std::vector<KFPtr> new_bias;                       // the KeyFrames whose preintegration receives SetNewBias (:4142), in order
+    std::vector<float> pos_w;
+    std::vector<std::pair<KFPtr, MPPtr>> edge_objects;
+    bool handled = true;
+    std::vector<std::pair<KFPtr, std::pair<unsigned long, unsigned long>>> kf_marks;
+    std::vector<std::pair<MPPtr, unsigned long>> mp_marks;
+    void restore_marks() {
+        for (auto it = kf_marks.rbegin(); it != kf_marks.rend(); ++it) { it->first->mnBALocalForKF = it->second.first; it->first->mnBAFixedForKF = it->second.second; }
+        for (auto it = mp_marks.rbegin(); it != mp_marks.rend(); ++it) it->first->mnBALocalForKF = it->second;
+    }
+};
+
+// :3920-4037 and the edge loops :4133-4307.  B.handled == false: not handled; the marks are already put back.
+template <class KFPtr>
+auto GatherMergeInertialBA(KFPtr pCurrKF, KFPtr pMergeKF) {
+    typedef typename std::decay<decltype(pCurrKF->GetMapPointMatches()[0])>::type MPPtr;
+    MergeInertialBAProblem<KFPtr, MPPtr> B;
+    const int Nd = 6;
+    const unsigned long maxKFid = pCurrKF->mnId, id = pCurrKF->mnId;
+    const size_t maxCovKF = 30;
+    auto refuse = [&] { B.restore_marks(); B.handled = false; return B; };
+    auto mark = [&](const KFPtr& k) { B.kf_marks.push_back({k, {k->mnBALocalForKF, k->mnBAFixedForKF}}); };
+    auto local = [&](const KFPtr& k) { mark(k); k->mnBALocalForKF = id; };
+    auto& opt = B.vpOptimizableKFs;
+    opt.push_back(pCurrKF);                                                                              // :3932-3940
+    local(pCurrKF);
+    for (int i = 1; i < Nd; i++) {
+        if (!opt.back()->mPrevKF) break;
+        opt.push_back(opt.back()->mPrevKF);
+        local(opt.back());
+    }
+    if (opt.back()->mPrevKF) {                                                                           // :3943-3949
+        B.vpOptimizableCovKFs.push_back(opt.back()->mPrevKF);
+        local(opt.back()->mPrevKF);
+    } else {
+        B.vpOptimizableCovKFs.push_back(opt.back());
+        opt.pop_back();
+    }
+    opt.push_back(pMergeKF);                                                                             // :3952-3962
+    local(pMergeKF);
+    for (int i = 1; i < Nd / 2; i++) {
+        if (!opt.back()->mPrevKF) break;
+        opt.push_back(opt.back()->mPrevKF);
+        local(opt.back());
+    }
+    if (opt.back()->mPrevKF) {                                                                           // :3965-3973
+        B.lFixedKeyFrames.push_back(opt.back()->mPrevKF);
+        mark(opt.back()->mPrevKF);
+        opt.back()->mPrevKF->mnBAFixedForKF = id;
+    } else {
+        mark(opt.back());
+        opt.back()->mnBALocalForKF = 0;
+        opt.back()->mnBAFixedForKF = id;
+        B.lFixedKeyFrames.push_back(opt.back());
+        opt.pop_back();
+    }
+    if (pMergeKF->mNextKF) {                                                                             // :3976-3987
+        opt.push_back(pMergeKF->mNextKF);
+        local(opt.back());
+    }
+    while (!opt.empty() && opt.size() < (size_t)(2 * Nd)) {
+        const KFPtr pKFlast = opt.back();
+        if (!pKFlast->mNextKF) break;
+        opt.push_back(pKFlast->mNextKF);
+        local(opt.back());
+    }
+    const int N = (int)opt.size();
+    std::map<MPPtr, int> mLocalObs;                                                                      // :3992-4009
+    for (int i = 0; i < N; i++) {
+        const auto vpMPs = opt[i]->GetMapPointMatches();
+        for (const MPPtr& pMP : vpMPs) {
+            if (!pMP || pMP->isBad()) continue;
+            if (pMP->mnBALocalForKF != id) {
+                mLocalObs[pMP] = 1;
+                B.lLocalMapPoints.push_back(pMP);
+                B.mp_marks.push_back({pMP, pMP->mnBALocalForKF});
+                pMP->mnBALocalForKF = id;
+            } else
+                mLocalObs[pMP]++;
+        }
+    }
+    std::vector<std::pair<MPPtr, int>> pairs(mLocalObs.begin(), mLocalObs.end());                         // :4011-4015
+    std::sort(pairs.begin(), pairs.end(), [](const std::pair<MPPtr, int>& a, const std::pair<MPPtr, int>& b) { return a.second < b.second; });
+    size_t i_pair = 0;
+    for (auto lit = pairs.begin(); lit != pairs.end(); ++lit, ++i_pair) {                                // :4018-4037
+        const auto observations = lit->first->GetObservations();
+        if (i_pair >= maxCovKF) break;
+        for (const auto& ob : observations) {
+            KFPtr pKFi = ob.first;
+            if (pKFi->mnBALocalForKF != id && pKFi->mnBAFixedForKF != id) {
+                local(pKFi);
+                if (!pKFi->isBad()) {
+                    B.vpOptimizableCovKFs.push_back(pKFi);
+                    break;
+                }
+            }
+        }
+    }
+    // ---- the vertices (:4052-4127): ascending mnId; what g2o would refuse or number twice is not handled
+    if (maxKFid <= 2) return refuse();
+    std::map<unsigned long, std::pair<KFPtr, int>> by_id;   // second: 0 free, 1 fixed
+    auto add = [&](const KFPtr& k, int fixed) {
+        if (k->mpCamera2 || k->mnId > maxKFid || by_id.count(k->mnId)) return false;
+        by_id[k->mnId] = {k, fixed};
+        return true;
+    };
+    for (const KFPtr& k : opt)
+        if (!add(k, 0)) return refuse();
+    for (const KFPtr& k : B.vpOptimizableCovKFs)
+        if (!add(k, 0)) return refuse();
+    for (const KFPtr& k : B.lFixedKeyFrames)
+        if (!add(k, 1)) return refuse();
+    std::map<KFPtr, int> index;
+    for (const auto& it : by_id) {
+        index[it.second.first] = (int)B.kf_of_index.size();
+        B.kf_of_index.push_back(it.second.first);
+    }
+    // ---- the inertial edges (:4133-4188)
+    std::vector<char> inertial(B.kf_of_index.size(), 0);
+    for (int i = 0; i < N; i++) {
+        const KFPtr& k = opt[i];
+        if (!k->mPrevKF) continue;                                                                       // :4137-4140
+        if (!(k->bImu && k->mPrevKF->bImu && k->mpImuPreintegrated)) return refuse();                    // :4186-4187
+        const auto prev = index.find(k->mPrevKF);
+        if (prev == index.end()) return refuse();                                                        // :4152-4156
+        msorb_iba_inertial_edge e;
+        std::memset(&e, 0, sizeof e);
+        if (!pose_inertial_detail::EdgeOf(k->mpImuPreintegrated, e.pre) || !pose_inertial_detail::RandomWalkInformation(k->mpImuPreintegrated, 9, e.info_gyro) ||
+            !pose_inertial_detail::RandomWalkInformation(k->mpImuPreintegrated, 12, e.info_acc))
+            return refuse();
+        e.pre.kf_prev = prev->second;
+        e.pre.kf_cur = index[k];
+        e.huber = 1;                                                                                     // :4168-4170
+        e.downweight = 0;
+        inertial[e.pre.kf_prev] = inertial[e.pre.kf_cur] = 1;
+        B.iedges.push_back(e);
+        B.new_bias.push_back(k);                                                                         // :4142
+    }
+    for (size_t k = 0; k < B.kf_of_index.size(); k++) {
+        const KFPtr& pKFi = B.kf_of_index[k];
+        const bool fixed = by_id[pKFi->mnId].second != 0;
+        // (a kind 3 record carries the velocity and the biases the write-back hands back unchanged, :4398-4406)
+        B.kfs.push_back(IbaKeyFrame(pKFi, fixed ? (pKFi->bImu ? 1 : 2) : (inertial[k] ? 0 : 3)));
+    }
+    // ---- the points and the visual edges (:4223-4307)
+    int nPoints = 0;
+    for (const MPPtr& pMP : B.lLocalMapPoints) {
+        const auto Xw = pMP->GetWorldPos();
+        B.pos_w.push_back(Xw(0)); B.pos_w.push_back(Xw(1)); B.pos_w.push_back(Xw(2));
+        const auto observations = pMP->GetObservations();
+        for (const auto& ob : observations) {
+            KFPtr pKFi = ob.first;
+            if (!pKFi) continue;
+            if (pKFi->mnBALocalForKF != id && pKFi->mnBAFixedForKF != id) continue;                      // :4247
+            if (pKFi->mnId > maxKFid) continue;                                                          // :4250
+            const auto at = index.find(pKFi);
+            if (at == index.end() || pKFi->isBad()) continue;                                            // :4255, :4258
+            if (B.append(pKFi, std::get<0>(ob.second), at->second, nPoints)) B.edge_objects.push_back({pKFi, pMP});
+        }
+        nPoints++;
+    }
+    return B;
+}
+
+template <class KFPtr, class MapT, class CorrT>
+bool MergeInertialBA(KFPtr pCurrKF, KFPtr pMergeKF, bool* pbStopFlag, MapT* pMap, CorrT& corrPoses, int device = 0) {
+    auto B = GatherMergeInertialBA(pCurrKF, pMergeKF);
+    if (!B.handled) return false;
+    auto set_new_bias = [&] {
+        for (const auto& k : B.new_bias) k->mpImuPreintegrated->SetNewBias(k->mPrevKF->GetImuBias());    // :4142
+    };
+    if (pbStopFlag && *pbStopFlag) {                                                                     // :4312-4314
+        set_new_bias();
+        return true;
+    }
+    const int K = (int)B.kfs.size(), P = (int)B.lLocalMapPoints.size(), E = (int)B.edge_kf.size(), NI = (int)B.iedges.size();
+    msorb_iba_problem prob;
+    std::memset(&prob, 0, sizeof prob);
+    std::vector<msorb_iba_keyframe_out> kf_out((size_t)K);
+    std::vector<float> pos_out(3 * (size_t)P);
+    std::vector<uint8_t> outlier((size_t)E), included((size_t)P);
+    msorb_iba_result r;
+    int rc;
+    {
+        StopFlagMirror stop(pbStopFlag);
+        rc = msorb_merge_inertial_ba(device, &prob, K, B.kfs.data(), NI, B.iedges.data(), P, B.pos_w.data(), E, B.edge_kf.data(),
+                                     B.edge_point.data(), B.xy.data(), B.u_right.data(), B.inv_sigma2.data(), stop.get(), kf_out.data(),
+                                     pos_out.data(), nullptr, outlier.data(), included.data(), &r, nullptr);
+    }
+    if (rc != MSORB_OK && rc != MSORB_E_CAPACITY) fail_call("msorb_merge_inertial_ba");
+    // no chains or too large; nothing to optimise; the flag rose before the first iteration; a factorisation failed
+    if (rc == MSORB_E_CAPACITY || r.status != 0 || r.reserved != 0) { B.restore_marks(); return false; }
+    set_new_bias();
+    std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);                                            // :4352
+    for (int pass = 0; pass < 2; pass++)                                                                 // vToErase: the mono edges, then the stereo edges
+        for (int e = 0; e < E; e++) {
+            if (!outlier[e] || (B.u_right[e] >= 0) != (pass == 1)) continue;
+            const auto& o = B.edge_objects[e];
+            if (o.second->isBad()) continue;                                                             // :4328, :4342
+            o.first->EraseMapPointMatch(o.second);                                                       // :4357-4358
+            o.second->EraseObservation(o.first);
+        }
+    typedef typename std::decay<decltype(pCurrKF->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(pCurrKF->GetPose().rotationMatrix())>::type RotF;
+    typedef typename std::decay<decltype(pCurrKF->GetPose().translation())>::type VecF;
+    typedef typename std::decay<decltype(pCurrKF->GetVelocity())>::type VelF;
+    typedef typename std::decay<decltype(pCurrKF->GetImuBias())>::type BiasT;
+    typedef typename CorrT::mapped_type Sim3T;
+    std::map<KFPtr, int> index;
+    for (int k = 0; k < K; k++) index[B.kf_of_index[k]] = k;
+    for (const auto* list : {&B.vpOptimizableKFs, &B.vpOptimizableCovKFs})                               // :4365-4385, :4387-4407
+        for (const KFPtr& pKFi : *list) {
+            const msorb_iba_keyframe_out& o = kf_out[index[pKFi]];
+            RotF Rf;
+            VecF tf;
+            VelF vf;
+            for (int a = 0; a < 3; a++) {
+                for (int b = 0; b < 3; b++) Rf(a, b) = o.Rcw_f[3 * a + b];
+                tf(a) = o.tcw_f[a];
+                vf(a) = o.v_f[a];
+            }
+            pKFi->SetPose(SE3T(Rf, tf));
+            const auto Tiw = pKFi->GetPose().template cast<double>();
+            corrPoses[pKFi] = Sim3T(Tiw.unit_quaternion(), Tiw.translation(), 1.0);
+            if (!pKFi->bImu) continue;
+            pKFi->SetVelocity(vf);
+            pKFi->SetNewBias(BiasT(o.bias_f[0], o.bias_f[1], o.bias_f[2], o.bias_f[3], o.bias_f[4], o.bias_f[5]));
+        }
+    if (P) {
+        typedef typename std::decay<decltype(B.lLocalMapPoints.front()->GetWorldPos())>::type PosT;
+        int p = 0;
+        for (const auto& pMP : B.lLocalMapPoints) {                                                      // :4410-4417
+            const float* o = pos_out.data() + 3 * (size_t)p++;
+            pMP->SetWorldPos(PosT(o[0], o[1], o[2]));
+            pMP->UpdateNormalAndDepth();
+        }
+    }
+    pMap->IncreaseChangeIndex();                                                                         // :4419
+    return true;
+}
+
 }  // namespace msorb_host
 }  // namespace ORB_SLAM3
 

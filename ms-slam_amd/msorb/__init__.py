@@ -2776,3 +2776,66 @@ def full_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, 
     if timing:
         r["elapsed_ms"] = ms.value
     return r
+
+
+# ---- Optimizer::MergeInertialBA on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_merge_inertial_ba_capacity", "msorb_merge_inertial_ba", "msorb_merge_inertial_ba_stage_ms")
+
+
+def _miba_lib():
+    L = lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_merge_inertial_ba_capacity.argtypes = []
+    L.msorb_merge_inertial_ba_stage_ms.argtypes = [vp]
+    L.msorb_merge_inertial_ba.argtypes = [ci, vp, ci, vp, ci, vp, ci, vp, ci] + [vp] * 13
+    return L
+
+
+def merge_inertial_ba_capacity():
+    """the largest number of unknowns msorb_merge_inertial_ba accepts (6 per free KeyFrame, 9 more per free KeyFrame of kind 0)"""
+    return _miba_lib().msorb_merge_inertial_ba_capacity()
+
+
+def merge_inertial_ba_stage_ms():
+    """the calling thread's last call's device time per stage (FIBA_STAGES); needs MSORB_MERGE_INERTIAL_BA_STAGES=1 in the environment"""
+    ms = np.zeros(5, np.float32)
+    _check(_miba_lib().msorb_merge_inertial_ba_stage_ms(_np_ptr(ms)), "msorb_merge_inertial_ba_stage_ms")
+    return dict(zip(FIBA_STAGES, (float(v) for v in ms)))
+
+
+def merge_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, iterations=0, stop_flag=None,
+                      device=0, timing=False, out=None):
+    """msorb_merge_inertial_ba: Optimizer::MergeInertialBA after its gathering loops, on the device.  keyframes: IBA_KF_DTYPE [K]
+    (kind 3 = free pose only); inertial_edges: IBA_EDGE_DTYPE [NI]; pos_w [P, 3]; the visual edges point-major as for
+    local_inertial_ba.  iterations > 0 replaces the reference's 8; stop_flag as for full_inertial_ba.
+    -> dict(result: IBA_RESULT_DTYPE record, kf: IBA_KF_OUT_DTYPE [K], pos float32 [P, 3], pos_d float64 [P, 3], outlier bool [E],
+    included bool [P]) and, with timing, elapsed_ms (device time).  out: (kf, pos, pos_d, outlier uint8, included uint8) arrays to
+    be written instead of fresh ones (they keep their contents when the call is refused)."""
+    L = _miba_lib()
+    kf = _c(keyframes, IBA_KF_DTYPE).reshape(-1)
+    ie = _c(inertial_edges, IBA_EDGE_DTYPE).reshape(-1)
+    pw = _c(pos_w, np.float32).reshape(-1)
+    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
+    px, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
+    P, E = len(pw) // 3, len(ek)
+    if len(pw) != 3 * P or [len(a) for a in (ep, px, ur, inv)] != [E, 2 * E, E, E]:
+        raise ValueError("pos_w or the edge arrays disagree in length")
+    pr = np.zeros(1, IBA_PROBLEM_DTYPE)
+    pr["iterations"] = iterations
+    if out is None:
+        out = (np.zeros(max(len(kf), 1), IBA_KF_OUT_DTYPE), np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64),
+               np.zeros(max(E, 1), np.uint8), np.zeros(max(P, 1), np.uint8))
+    kf_out, pos, pos_d, flags, inc = out
+    flag = stop_flag
+    if flag is not None and not (isinstance(flag, np.ndarray) and flag.dtype == np.int32 and flag.size == 1 and flag.flags.c_contiguous):
+        raise TypeError("stop_flag must be a contiguous int32 numpy array of one element: the call polls that very memory")
+    res = np.zeros(1, IBA_RESULT_DTYPE)
+    ms = C.c_float()
+    _check(L.msorb_merge_inertial_ba(device, _np_ptr(pr), len(kf), _np_ptr(kf), len(ie), _np_ptr(ie), P, _np_ptr(pw), E, _np_ptr(ek),
+                                     _np_ptr(ep), _np_ptr(px), _np_ptr(ur), _np_ptr(inv), None if flag is None else _np_ptr(flag),
+                                     _np_ptr(kf_out), _np_ptr(pos), _np_ptr(pos_d), _np_ptr(flags), _np_ptr(inc), _np_ptr(res),
+                                     C.addressof(ms)), "msorb_merge_inertial_ba")
+    r = dict(result=res[0], kf=kf_out[:len(kf)], pos=pos[:P], pos_d=pos_d[:P], outlier=flags[:E].astype(bool), included=inc[:P].astype(bool))
+    if timing:
+        r["elapsed_ms"] = ms.value
+    return r
