@@ -1633,6 +1633,55 @@ int msorb_merge_inertial_ba(int device, const msorb_iba_problem* p, int n_kf, co
                             const volatile int* stop_flag, msorb_iba_keyframe_out* kf_out, float* pos_out, double* pos_d,
                             uint8_t* edge_outlier, uint8_t* point_included, msorb_iba_result* r, float* elapsed_ms);
 
+/* The second Optimizer::LocalBundleAdjustment (pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag; src/Optimizer.cc:3494-3915) after its
+ * gathering loops, on the device, for pinhole KeyFrames: the welding bundle adjustment that LoopClosing::MergeLocal runs when the
+ * merged maps are not both inertial (LoopClosing.cc:1571).  The engine, the arrays and the point-major edge order are
+ * msorb_local_ba's, the blocked solve and the capacity and memory check msorb_bundle_adjustment's.  Appended to ABI 6002:
+ * MSORB_ABI_VERSION stays 6002.  What the routine does that no other does, it optimises twice over two graphs:
+ *   round 1  optimize(5), Huber kernels of width (float)sqrt(5.99) (mono) / (float)sqrt(7.815) (stereo) on every edge (:3607-3608);
+ *   levels   chi2() > 5.991 / 7.815, compared in double, or !isDepthPositive() puts an edge on level 1; every kernel is switched
+ *            off (:3726-3753).  No computeError() precedes it: chi2() belongs to the state of round 1's last trial, accepted or
+ *            not; the depth is the estimate's;
+ *   round 2  initializeOptimization(0), optimize(10): the level-0 edges only.  A free KeyFrame or a point that no level-0 edge
+ *            reaches is not in that problem: it keeps, bit for bit, what round 1 left.  lambda, ni and the count of bad
+ *            iterations start anew;
+ *   flags    the same test (:3769-3803): an edge of round 2 with the chi2 of round 2's last trial (if round 2 made no iteration,
+ *            round 1's), a level-1 edge with the chi2 of round 1's, every edge with the depth at the final estimate.
+ * There is no "no fixed KeyFrame" return and no second-camera arm in this routine.  Every point is a vertex; one without an edge
+ * returns its input.  *stop_flag (may be NULL) is read where g2o calls terminate() and once between the rounds (:3718).
+ * edge_level1 [n_edges]: the levels after round 1 (all zero when round 2 was skipped); edge_outlier [n_edges]: vToErase.
+ * status: 0 optimised; 2 the flag was set before optimize (:3709-3711), or rose before the first iteration (the reference would
+ * classify errors it never computed): every output repeats its input, no flag is set; 3 the flag was up after round 1: no levels,
+ * no round 2, the flags of the one classification.  active_keyframes / active_points: the vertices of round 2's problem.
+ * More free KeyFrames than the capacity, or no room for the reduced system: MSORB_E_CAPACITY, nothing launched, nothing written.
+ * MSORB_E_ARG as msorb_local_ba.  Two calls on the same input return the same bits.  Re-entrant like msorb_local_ba.
+ * msorb_welding_ba_stage_ms: msorb_local_ba_stage_ms for the calling thread's last call, both rounds added. */
+typedef struct msorb_welding_ba_round {
+    int iterations, trials, rejected_trials, reserved;
+    double chi2_initial, chi2_final, lambda_final;
+} msorb_welding_ba_round;
+typedef struct msorb_welding_ba_result {
+    int status, n_level1, n_outliers, active_keyframes, active_points, reserved;
+    msorb_welding_ba_round round[2];
+} msorb_welding_ba_result;
+/* Test hook: the calling thread's msorb_welding_ba calls fn(user, round, where, iteration, trials) at every place where it is about
+ * to read *stop_flag after the entry check, so a test raises its flag at a chosen poll and the call takes that arm every time.
+ * round: 0 / 1.  where: before an iteration (sparse_optimizer.cpp:376), after a rejected trial whose rho is negative
+ * (levenberg.cpp:149), between the rounds (Optimizer.cc:3718).  iteration: the iteration about to begin or under way; trials: the
+ * round's trials so far.  fn = NULL (the default) removes it.  No other entry calls it. */
+#define MSORB_WELDING_POLL_ITERATION 0
+#define MSORB_WELDING_POLL_REJECTED 1
+#define MSORB_WELDING_POLL_BETWEEN 2
+typedef void (*msorb_welding_ba_poll_fn)(void* user, int round, int where, int iteration, int trials);
+void msorb_debug_welding_ba_poll_hook(msorb_welding_ba_poll_fn fn, void* user);
+int msorb_welding_ba_capacity(void);                   /* free KeyFrames: msorb_bundle_adjustment_capacity() */
+int msorb_welding_ba_stage_ms(float ms[4]);
+int msorb_welding_ba(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_points, const float* pos_w,
+                     int n_edges, const int* edge_kf, const int* edge_point, const float* xy, const float* u_right,
+                     const float* inv_sigma2, const volatile int* stop_flag,
+                     float* kf_qt_out, double* kf_qt_d, float* pos_out, double* pos_d, uint8_t* edge_level1, uint8_t* edge_outlier,
+                     msorb_welding_ba_result* r, float* elapsed_ms);
+
 #ifdef __cplusplus
 }
 #endif

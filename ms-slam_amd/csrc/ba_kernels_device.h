@@ -1,7 +1,7 @@
-// The kernels under the engine of msorb_local_ba and msorb_bundle_adjustment (bundle_adjustment.hip): the edge linearisation with
-// the Huber switch, the per-vertex gathers, the point inverse, the Schur complement over the plan's index lists, the update, the
-// cost / scale reduction, and the stage timer.  bundle_adjustment.hip's header comment and DESIGN.md sections 10 and 16 say what
-// each does.  Every sum walks an index list of local_ba_plan.h in a fixed order: no floating-point atomics.
+// The kernels under the engine of msorb_local_ba, msorb_bundle_adjustment and msorb_welding_ba (bundle_adjustment.hip): the edge
+// linearisation with the Huber switch, the per-vertex gathers, the point inverse, the Schur complement over the plan's index lists,
+// the update, the cost / scale reduction, the welding entry's classification, and the stage timer.  bundle_adjustment.hip's header
+// comment and DESIGN.md sections 10, 16 and 27 say what each does.  Every sum walks an index list of local_ba_plan.h in a fixed order: no floating-point atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -401,6 +401,26 @@ static __global__ __launch_bounds__(kEdgeThreads) void ba_update_kernel(const Ba
         A.pt[to][3 * (size_t)p + c] = A.pt[from][3 * (size_t)p + c] + xl[c];   // VertexSBAPointXYZ::oplusImpl
     }
     A.part_vtx[v] = sc;
+}
+
+// The two classifications of the welding bundle adjustment (Optimizer.cc:3726-3753, :3769-3803), which call no computeError():
+// chi2() is what the last computeActiveErrors() left, the errors at the last trial's state (copy s_trial, which pop() has dropped
+// if the trial was rejected), compared in double; isDepthPositive() reads the vertices, the estimate (copy s_cur).  chi_flag [E]
+// keeps chi2 > threshold between the two: an edge is refreshed only where the last optimize() computed its error (refresh != 0
+// and the edge is not on level 1), so a level-1 edge's flag stays what round 1 found.  out = chi_flag or the depth is not positive.
+static __global__ __launch_bounds__(kEdgeThreads) void ba_classify_welding_kernel(const BaDev A, int s_trial, int s_cur, int refresh,
+                                                                                  const uint8_t* level, uint8_t* chi_flag, uint8_t* out) {
+    const int e = blockIdx.x * kEdgeThreads + threadIdx.x;
+    if (e >= A.E) return;
+    int k, p;
+    uint8_t c = chi_flag[e];
+    if (refresh && !(level && level[e])) {
+        const EdgeGeom t = edge_geom(A, s_trial, e, k, p);
+        c = t.chi2 > (t.stereo ? 7.815 : 5.991) ? 1 : 0;
+        chi_flag[e] = c;
+    }
+    const EdgeGeom g = edge_geom(A, s_cur, e, k, p);
+    out[e] = (c || !(g.z > 0.0)) ? 1 : 0;
 }
 
 // MSORB_LOCAL_BA_STAGES=1 (read once per process): every stage of a call is bracketed by two events, and

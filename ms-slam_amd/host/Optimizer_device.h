@@ -1,4 +1,4 @@
-// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037), LocalBundleAdjustment, BundleAdjustment / GlobalBundleAdjustemnt, the two OptimizeSim3 and the loop-closing OptimizeEssentialGraph (further down), each on
+// Optimizer::PoseOptimization (src/Optimizer.cc:759-1037), both LocalBundleAdjustment (the local mapper's and the welding one of a map merge), BundleAdjustment / GlobalBundleAdjustemnt, the two OptimizeSim3 and the loop-closing OptimizeEssentialGraph (further down), each on
 // its device entry of libmsorb.  First PoseOptimization (msorb_pose_optimization_batch /
 // msorb_frame_pose_optimization), written against the reference's own types by name (a template: this header compiles inside
 // MS-SLAM, where Frame / MapPoint are the real classes, and in tests/dropin_poseopt_main.cc, where they are minimal stand-ins
@@ -468,6 +468,150 @@ bool GlobalBundleAdjustemnt(MapT* pMap, int nIterations = 5, bool* pbStopFlag = 
     const auto vpKFs = pMap->GetAllKeyFrames();                                                          // :53-56
     const auto vpMP = pMap->GetAllMapPoints();
     return BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, nLoopKF, bRobust, device);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The second Optimizer::LocalBundleAdjustment (src/Optimizer.cc:3494-3915) on msorb_welding_ba: the welding bundle adjustment
+// that LoopClosing::MergeLocal runs when the merged maps are not both inertial (LoopClosing.cc:1571).
+//
+//   bool ORB_SLAM3::msorb_host::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag)
+//
+// the reference's parameter list and its effects: mnBALocalForMerge = pMainKF->mnId on every gathered KeyFrame and point; under
+// the map's mMutexMapUpdate the observations of vToErase erased (EraseMapPointMatch + EraseObservation, the mono edges first),
+// SetPose for every vpAdjustKF that is not bad, SetWorldPos + UpdateNormalAndDepth for every gathered point that is not bad.
+// true = done, including the stop flag found set before optimize (:3709-3711: the marks alone).
+//
+// false = NOT handled, the marks put back, the caller runs Optimizer::LocalBundleAdjustment: a gathered KeyFrame whose camera is
+// not a pinhole, more adjustable KeyFrames than msorb_welding_ba_capacity() (or no room on the device for their reduced system).
+//
+// What is not restated because it has no effect: the counting loops of :3819-3840 and :3852-3899 and their maps (mpObsKFs,
+// mpObsFinalKFs, mpObsMPs); :3883 indexes vpEdgeKFMono with a stereo edge's index, past its end when there are more stereo edges.
+// What the reference leaves undefined is skipped: an observation whose KeyFrame carries the mark without being a vertex (the mark
+// of an earlier merge with the same pMainKF), and the write-back of a vpAdjustKF that is in another map (it has no vertex, :3848
+// would read NULL).  A KeyFrame in both lists keeps the fixed vertex, as g2o's addVertex refuses the second one; its SetPose
+// receives the bits of its own pose, where the reference hands back the fixed vertex's estimate, the same pose with the quaternion
+// normalised in double and narrowed again (equal up to the last bit of a component).
+//
+// What runs where.  The gathering (:3515-3707) stays host code, as the reference's; both optimisations and both classifications
+// are the device's.  *pbStopFlag is a bool another thread may set (LoopClosing's mbStopGBA): StopFlagMirror.
+template <class KFPtr, class MPPtr>
+struct WeldingBAProblem : BaEdges {
+    std::vector<KFPtr> kf_of_index;        // vpFixedKF first, then vpAdjustKF
+    std::vector<msorb_ba_keyframe> kfs;
+    std::map<unsigned long, int> index;    // optimizer.vertex(mnId)
+    int n_free = 0;
+    std::vector<MPPtr> vpMPs;              // :3498, in the order of the walk
+    std::vector<int> vertex_of_mp;         // per vpMPs entry: its point index, -1 = bad when the vertices were made (:3616)
+    std::vector<float> pos_w;
+    std::vector<std::pair<KFPtr, MPPtr>> edge_objects;
+    bool pinhole = true;
+    std::vector<std::pair<KFPtr, unsigned long>> kf_marks;   // what the walk overwrote
+    std::vector<std::pair<MPPtr, unsigned long>> mp_marks;
+    void restore_marks() {
+        for (auto it = kf_marks.rbegin(); it != kf_marks.rend(); ++it) it->first->mnBALocalForMerge = it->second;
+        for (auto it = mp_marks.rbegin(); it != mp_marks.rend(); ++it) it->first->mnBALocalForMerge = it->second;
+    }
+};
+
+// :3515-3707.  Returns the problem as the arrays of msorb_welding_ba.
+template <class KFPtr>
+auto GatherWeldingBA(KFPtr pMainKF, const std::vector<KFPtr>& vpAdjustKF, const std::vector<KFPtr>& vpFixedKF) {
+    typedef typename std::decay<decltype(*pMainKF->GetMapPoints().begin())>::type MPPtr;
+    WeldingBAProblem<KFPtr, MPPtr> B;
+    const unsigned long id = pMainKF->mnId;
+    auto* pCurrentMap = pMainKF->GetMap();
+    unsigned long maxKFid = 0;
+    auto add = [&](const KFPtr& pKFi, bool fixed) {                                                      // :3522-3552, :3557-3585
+        if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) return;
+        B.kf_marks.push_back({pKFi, pKFi->mnBALocalForMerge});
+        pKFi->mnBALocalForMerge = id;
+        if (pKFi->mpCamera->GetType() != pKFi->mpCamera->CAM_PINHOLE) B.pinhole = false;
+        if (!B.index.count(pKFi->mnId)) {
+            B.index[pKFi->mnId] = (int)B.kfs.size();
+            B.kfs.push_back(BaKeyFrame(pKFi, fixed));
+            B.kf_of_index.push_back(pKFi);
+            B.n_free += fixed ? 0 : 1;
+        }
+        if (pKFi->mnId > maxKFid) maxKFid = pKFi->mnId;
+        const auto spViewMPs = pKFi->GetMapPoints();
+        for (const MPPtr& pMPi : spViewMPs)
+            if (pMPi && !pMPi->isBad() && pMPi->GetMap() == pCurrentMap && pMPi->mnBALocalForMerge != id) {
+                B.vpMPs.push_back(pMPi);
+                B.mp_marks.push_back({pMPi, pMPi->mnBALocalForMerge});
+                pMPi->mnBALocalForMerge = id;
+            }
+    };
+    for (const KFPtr& pKFi : vpFixedKF) add(pKFi, true);
+    for (const KFPtr& pKFi : vpAdjustKF) add(pKFi, false);
+    int nPoints = 0;
+    for (const MPPtr& pMPi : B.vpMPs) {                                                                  // :3614-3707
+        if (pMPi->isBad()) { B.vertex_of_mp.push_back(-1); continue; }
+        B.vertex_of_mp.push_back(nPoints);
+        const auto Xw = pMPi->GetWorldPos();
+        B.pos_w.push_back(Xw(0)); B.pos_w.push_back(Xw(1)); B.pos_w.push_back(Xw(2));
+        const auto observations = pMPi->GetObservations();
+        for (const auto& ob : observations) {
+            const KFPtr& pKF = ob.first;
+            const int leftIndex = std::get<0>(ob.second);
+            if (pKF->isBad() || pKF->mnId > maxKFid || pKF->mnBALocalForMerge != id || leftIndex < 0 || !pKF->GetMapPoint(leftIndex)) continue;   // :3633-3635
+            const auto at = B.index.find(pKF->mnId);
+            if (at == B.index.end()) continue;
+            if (B.append(pKF, leftIndex, at->second, nPoints)) B.edge_objects.push_back({pKF, pMPi});    // :3638: octave > 10 makes no edge
+        }
+        nPoints++;
+    }
+    return B;
+}
+
+template <class KFPtr>
+bool LocalBundleAdjustment(KFPtr pMainKF, std::vector<KFPtr> vpAdjustKF, std::vector<KFPtr> vpFixedKF, bool* pbStopFlag, int device = 0) {
+    auto B = GatherWeldingBA(pMainKF, vpAdjustKF, vpFixedKF);
+    if (!B.pinhole || B.n_free > msorb_welding_ba_capacity()) {
+        B.restore_marks();
+        return false;
+    }
+    const int K = (int)B.kfs.size(), P = (int)B.pos_w.size() / 3, E = (int)B.edge_kf.size();
+    std::vector<float> kf_out(7 * (size_t)K), pos_out(3 * (size_t)P);
+    std::vector<uint8_t> level1((size_t)E), outlier((size_t)E);
+    msorb_welding_ba_result r;
+    int rc;
+    {
+        StopFlagMirror stop(pbStopFlag);
+        rc = msorb_welding_ba(device, K, B.kfs.data(), P, B.pos_w.data(), E, B.edge_kf.data(), B.edge_point.data(), B.xy.data(),
+                              B.u_right.data(), B.inv_sigma2.data(), stop.get(), kf_out.data(), nullptr, pos_out.data(), nullptr,
+                              level1.data(), outlier.data(), &r, nullptr);
+    }
+    if (rc == MSORB_E_CAPACITY) { B.restore_marks(); return false; }
+    if (rc != MSORB_OK) fail_call("msorb_welding_ba");
+    if (r.status == 2) return true;                                                                      // :3709-3711
+    typedef typename std::decay<decltype(pMainKF->GetPose())>::type SE3T;
+    typedef typename std::decay<decltype(pMainKF->GetPose().unit_quaternion())>::type QuatT;
+    typedef typename std::decay<decltype(pMainKF->GetPose().translation())>::type VecT;
+    std::unique_lock<std::mutex> lock(pMainKF->GetMap()->mMutexMapUpdate);                               // :3809
+    for (int pass = 0; pass < 2; pass++)                                                                 // vToErase: the mono edges, then the stereo edges
+        for (int e = 0; e < E; e++) {
+            if (!outlier[e] || (B.u_right[e] >= 0) != (pass == 1)) continue;
+            const auto& o = B.edge_objects[e];
+            if (o.second->isBad()) continue;                                                             // :3773, :3791
+            o.first->EraseMapPointMatch(o.second);                                                       // :3815-3816
+            o.second->EraseObservation(o.first);
+        }
+    for (const KFPtr& pKFi : vpAdjustKF) {                                                               // :3844-3902
+        if (pKFi->isBad()) continue;
+        const auto at = B.index.find(pKFi->mnId);
+        if (at == B.index.end() || B.kf_of_index[at->second] != pKFi) continue;
+        const float* o = kf_out.data() + 7 * (size_t)at->second;
+        pKFi->SetPose(SE3T(QuatT(o[3], o[0], o[1], o[2]), VecT(o[4], o[5], o[6])));
+    }
+    for (size_t i = 0; i < B.vpMPs.size(); i++) {                                                        // :3905-3914
+        const auto& pMPi = B.vpMPs[i];
+        if (pMPi->isBad() || B.vertex_of_mp[i] < 0) continue;
+        typedef typename std::decay<decltype(pMPi->GetWorldPos())>::type PosT;
+        const float* o = pos_out.data() + 3 * (size_t)B.vertex_of_mp[i];
+        pMPi->SetWorldPos(PosT(o[0], o[1], o[2]));
+        pMPi->UpdateNormalAndDepth();
+    }
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

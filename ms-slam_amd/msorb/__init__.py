@@ -1970,9 +1970,11 @@ def _ba_lib():
     return L
 
 
-def _ba_call(entry, keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, controls, stop_flag, device, timing, flags_key, per):
-    """msorb_local_ba / msorb_bundle_adjustment: controls = the ints between inv_sigma2 and stop_flag; flags_key names the uint8
-    output that follows pos_d, one entry per edge (per = "E") or per point ("P")"""
+def _ba_call(entry, keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, controls, stop_flag, device, timing, flags_key, per,
+             more_flags=(), result_dtype=None):
+    """msorb_local_ba / msorb_bundle_adjustment / msorb_welding_ba: controls = the ints between inv_sigma2 and stop_flag; flags_key
+    names the uint8 output that comes last before the result, one entry per edge (per = "E") or per point ("P"); more_flags: the
+    names of per-edge uint8 outputs between pos_d and it; result_dtype: the result record, BA_RESULT_DTYPE unless given"""
     L = _ba_lib()
     kf = _c(keyframes, BA_KEYFRAME_DTYPE).reshape(-1)
     pw = _c(pos_w, np.float32).reshape(-1, 3)
@@ -1987,13 +1989,16 @@ def _ba_call(entry, keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigm
     po, pod = np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64)
     n_flags = E if per == "E" else P
     flags = np.zeros(max(n_flags, 1), np.uint8)
-    res = np.zeros(1, BA_RESULT_DTYPE)
+    more = [np.zeros(max(E, 1), np.uint8) for _ in more_flags]
+    res = np.zeros(1, BA_RESULT_DTYPE if result_dtype is None else result_dtype)
     ms = C.c_float()
     _check(getattr(L, entry)(device, K, _np_ptr(kf), P, _np_ptr(pw), E, _np_ptr(ek), _np_ptr(ep), _np_ptr(ob), _np_ptr(ur), _np_ptr(inv),
                              *controls, None if stop_flag is None else _np_ptr(stop_flag), _np_ptr(qt), _np_ptr(qtd), _np_ptr(po),
-                             _np_ptr(pod), _np_ptr(flags), _np_ptr(res), C.addressof(ms)), entry)
+                             _np_ptr(pod), *[_np_ptr(m) for m in more], _np_ptr(flags), _np_ptr(res), C.addressof(ms)), entry)
     r = dict(result=res[0], kf_qt=qt[:K], kf_qt_d=qtd[:K], pos=po[:P], pos_d=pod[:P])
     r[flags_key] = flags[:n_flags].astype(bool)
+    for name, m in zip(more_flags, more):
+        r[name] = m[:E].astype(bool)
     if timing:
         r["elapsed_ms"] = ms.value
     return r
@@ -2087,6 +2092,56 @@ def bundle_adjustment(keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_si
 def bundle_adjustment_stage_ms():
     """local_ba_stage_ms for this thread's last bundle_adjustment call (MSORB_LOCAL_BA_STAGES=1)"""
     return _ba_stage_ms("msorb_bundle_adjustment_stage_ms")
+
+
+# ---- the welding bundle adjustment of a visual map merge: the second Optimizer::LocalBundleAdjustment (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_welding_ba_capacity", "msorb_welding_ba", "msorb_welding_ba_stage_ms", "msorb_debug_welding_ba_poll_hook")
+
+WELDING_BA_ROUND_DTYPE = np.dtype([("iterations", "<i4"), ("trials", "<i4"), ("rejected_trials", "<i4"), ("reserved", "<i4"),
+                                   ("chi2_initial", "<f8"), ("chi2_final", "<f8"), ("lambda_final", "<f8")])   # msorb_welding_ba_round
+WELDING_BA_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_level1", "<i4"), ("n_outliers", "<i4"), ("active_keyframes", "<i4"),
+                                    ("active_points", "<i4"), ("reserved", "<i4"), ("round", WELDING_BA_ROUND_DTYPE, 2)])   # msorb_welding_ba_result
+assert WELDING_BA_ROUND_DTYPE.itemsize == 40 and WELDING_BA_RESULT_DTYPE.itemsize == 104
+WELDING_POLL_ITERATION, WELDING_POLL_REJECTED, WELDING_POLL_BETWEEN = 0, 1, 2      # MSORB_WELDING_POLL_*
+_WELDING_POLL_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int)   # msorb_welding_ba_poll_fn
+
+
+def _wba_lib():
+    L = _ba_lib()
+    vp, ci = C.c_void_p, C.c_int
+    L.msorb_welding_ba_capacity.argtypes = []
+    L.msorb_welding_ba.argtypes = [ci, ci, vp, ci, vp, ci] + [vp] * 5 + [vp] * 9
+    L.msorb_welding_ba_stage_ms.argtypes = [vp]
+    L.msorb_debug_welding_ba_poll_hook.argtypes = [_WELDING_POLL_FN, vp]
+    L.msorb_debug_welding_ba_poll_hook.restype = None
+    return L
+
+
+def welding_ba_capacity():
+    """the largest number of free KeyFrames msorb_welding_ba accepts"""
+    return _wba_lib().msorb_welding_ba_capacity()
+
+
+def welding_ba(keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, stop_flag=None, device=0, timing=False, poll_hook=None):
+    """msorb_welding_ba: the welding Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag) on the device.
+    The arrays are local_ba's; fixed marks vpFixedKF.  -> dict(result: WELDING_BA_RESULT_DTYPE record, kf_qt, kf_qt_d [K, 7], pos,
+    pos_d [P, 3], level1 bool [E] (the edges round 2 leaves out), outlier bool [E] (vToErase)) and, with timing, elapsed_ms.
+    poll_hook (tests): msorb_debug_welding_ba_poll_hook for this call; poll_hook(round, where, iteration, trials) runs before every
+    read of the stop flag after the entry check (where: WELDING_POLL_*) and may set stop_flag[0]."""
+    L = _wba_lib()
+    cb = _WELDING_POLL_FN(lambda user, rnd, where, it, trials: poll_hook(rnd, where, it, trials)) if poll_hook else _WELDING_POLL_FN()
+    L.msorb_debug_welding_ba_poll_hook(cb, None)
+    try:
+        return _ba_call("msorb_welding_ba", keyframes, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, (), stop_flag, device, timing,
+                        "outlier", "E", more_flags=("level1",), result_dtype=WELDING_BA_RESULT_DTYPE)
+    finally:
+        L.msorb_debug_welding_ba_poll_hook(_WELDING_POLL_FN(), None)
+
+
+def welding_ba_stage_ms():
+    """local_ba_stage_ms for this thread's last welding_ba call, both rounds added (MSORB_LOCAL_BA_STAGES=1)"""
+    _wba_lib()
+    return _ba_stage_ms("msorb_welding_ba_stage_ms")
 
 
 EXPORTS = EXPORTS + ("msorb_create_new_map_points_kf", "msorb_create_new_map_points_stage_ms")
