@@ -1582,7 +1582,9 @@ int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, int n_kf, co
  * (kind 0 and 1) receives the shared biases (:720-733).
  * Errors as msorb_local_inertial_ba's, nothing written before the last of them has passed; inertial edges that are not chains, or
  * more free KeyFrames than msorb_full_inertial_ba_capacity(init) (477 / 795: a dense square of 7168 unknowns), are
- * MSORB_E_CAPACITY.  Two calls on the same input return the same bits.  Re-entrant.  *elapsed_ms (may be NULL): device time.
+ * MSORB_E_CAPACITY.  *r, *elapsed_ms and the output arrays are first written when the call has succeeded: a call that returns an
+ * error, MSORB_E_HIP included, leaves them as they were (msorb_merge_inertial_ba does the same).
+ * Two calls on the same input return the same bits.  Re-entrant.  *elapsed_ms (may be NULL): device time.
  * msorb_full_inertial_ba_stage_ms: with MSORB_FULL_INERTIAL_BA_STAGES=1 in the environment, the calling thread's last call's device
  * time per stage: linearise, assemble, Schur, solve, trial. */
 typedef struct msorb_fiba_problem {

@@ -18,12 +18,15 @@
 
 #include "../../include/msorb.h"
 #include "hip_host.h"
+#include "inertial_ba_host.h"
 #include "local_ba_plan.h"
 #include "local_inertial_ba_device.h"
 
 using msorb::set_last_error;
 using msorb::ThreadScratch;
 using msorb::up16;
+using msorb::iba_host::Carve;
+using msorb::iba_host::repeat_inputs;
 using namespace msorb::liba;
 
 namespace {
@@ -46,11 +49,6 @@ __global__ __launch_bounds__(kThreads) void local_inertial_ba_kernel(const Work 
     if (threadIdx.x == 0) *cur_out = cur;
 }
 
-struct Carve {
-    size_t at = 0;
-    size_t take(size_t bytes) { const size_t o = at; at += up16(bytes); return o; }
-};
-
 int refuse(const char* what) {
     set_last_error(std::string("local_inertial_ba: ") + what);
     return MSORB_E_INVALID;
@@ -59,20 +57,6 @@ int not_handled(const char* what) {
     set_last_error(std::string("local_inertial_ba: ") + what);
     return MSORB_E_CAPACITY;
 }
-
-bool finite_all(const double* p, size_t n) {
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-bool finite_all(const float* p, size_t n) {
-    for (size_t i = 0; i < n; i++)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
-void repeat_inputs(int K, const msorb_iba_keyframe* kfs, int P, const float* pos_w, int E, msorb_iba_keyframe_out* kf_out, float* pos_out,
-                   double* pos_d, uint8_t* edge_outlier);
 
 }  // namespace
 
@@ -95,7 +79,6 @@ extern "C" int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, i
     fixed.resize((size_t)K);
     for (int k = 0; k < K; k++) {
         if (kfs[k].kind < 0 || kfs[k].kind > 2) return refuse("an unknown kind (0 free, 1 fixed with inertial vertices, 2 fixed pose)");
-        if (!finite_all(kfs[k].Rwb, 48) || !finite_all(&kfs[k].fx, (size_t)5)) return refuse("a non-finite value in a KeyFrame");
         fixed[k] = kfs[k].kind != 0;
     }
     e_in.assign((size_t)K, -1);
@@ -107,15 +90,11 @@ extern "C" int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, i
         if (a < 0 || a >= K || b < 0 || b >= K) return refuse("an inertial edge names a KeyFrame out of range");
         if (a == b) return refuse("an inertial edge from a KeyFrame to itself");
         if (kfs[a].kind == 2 || kfs[b].kind == 2) return refuse("an inertial edge on a KeyFrame without inertial vertices (kind 2)");
-        if (!finite_all(e.pre.dR, (size_t)67) || !finite_all(e.pre.info, 81) || !finite_all(e.info_gyro, 18))
-            return refuse("a non-finite value in an inertial edge");
         if (e_out[a] >= 0 || e_in[b] >= 0) chains = false;
         e_out[a] = i;
         e_in[b] = i;
     }
-    if (!finite_all(pos_w, 3 * (size_t)P) || !finite_all(xy, 2 * (size_t)E) || !finite_all(u_right, (size_t)E) ||
-        !finite_all(inv_sigma2, (size_t)E))
-        return refuse("a non-finite value in a point or an observation");
+    if (!msorb::iba_host::inputs_finite("local_inertial_ba: ", K, kfs, NI, iedges, P, pos_w, E, xy, u_right, inv_sigma2)) return MSORB_E_INVALID;
     switch (msorb::build_local_ba_plan(K, fixed.data(), P, E, edge_kf, edge_point, plan)) {
         case msorb::kPlanIndexOutOfRange: return refuse("an edge names a KeyFrame or a point out of range");
         case msorb::kPlanNotPointMajor: return refuse("the edges are not point-major");
@@ -135,7 +114,7 @@ extern "C" int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, i
     std::memset(r, 0, sizeof *r);
     if (Kf == 0 && E == 0) {   // g2o's "0 vertices to optimize": nothing moved
         r->status = 2;
-        repeat_inputs(K, kfs, P, pos_w, E, kf_out, pos_out, pos_d, edge_outlier);
+        repeat_inputs(K, kfs, P, pos_w, E, kf_out, pos_out, pos_d, edge_outlier, nullptr);
         return MSORB_OK;
     }
     if (int rc = msorb::require_device(device)) return rc;
@@ -242,13 +221,13 @@ extern "C" int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, i
 #undef IBA_TRY
     *r = *reinterpret_cast<const msorb_iba_result*>(h + h_out);
     if (r->status == 1) {   // :2911-2915: the reference returns before it erases or writes anything
-        repeat_inputs(K, kfs, P, pos_w, E, kf_out, pos_out, pos_d, edge_outlier);
+        repeat_inputs(K, kfs, P, pos_w, E, kf_out, pos_out, pos_d, edge_outlier, nullptr);
         return MSORB_OK;
     }
     const int cur = *reinterpret_cast<const int*>(h + h_cur) & 1;
     const msorb::pinert::Vertices* V = reinterpret_cast<const msorb::pinert::Vertices*>(h + h_back + (cur ? o_st1 - o_st0 : 0));
     const double* X = reinterpret_cast<const double*>(h + h_back + (cur ? o_pt1 : o_pt0) - o_st0);
-    repeat_inputs(K, kfs, 0, nullptr, 0, kf_out, nullptr, nullptr, nullptr);
+    repeat_inputs(K, kfs, 0, nullptr, 0, kf_out, nullptr, nullptr, nullptr, nullptr);
     for (int k = 0; k < K; k++)
         if (!fixed[k]) keyframe_out(V[k], kf_out[k]);
     for (size_t i = 0; i < 3 * (size_t)P; i++) {
@@ -260,21 +239,3 @@ extern "C" int msorb_local_inertial_ba(int device, const msorb_iba_problem* p, i
     r->n_outliers = n_outliers;
     return MSORB_OK;
 }
-
-namespace {
-
-void repeat_inputs(int K, const msorb_iba_keyframe* kfs, int P, const float* pos_w, int E, msorb_iba_keyframe_out* kf_out, float* pos_out,
-                   double* pos_d, uint8_t* edge_outlier) {
-    for (int k = 0; k < K; k++) {
-        msorb::pinert::Vertices V;
-        vertices_from(V, kfs[k]);
-        keyframe_out(V, kf_out[k]);
-    }
-    for (size_t i = 0; i < 3 * (size_t)P; i++) {
-        pos_out[i] = pos_w[i];
-        if (pos_d) pos_d[i] = (double)pos_w[i];
-    }
-    if (E) std::memset(edge_outlier, 0, (size_t)E);
-}
-
-}  // namespace

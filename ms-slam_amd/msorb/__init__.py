@@ -2724,6 +2724,41 @@ def _iba_lib():
     return L
 
 
+def _iba_inputs(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, point_close=None):
+    """the input arrays of the three inertial bundle adjustments, contiguous in their dtypes and flat, with P and E
+    -> (kf, ie, pw, cl or None, ek, ep, px, ur, inv, P, E)"""
+    kf = _c(keyframes, IBA_KF_DTYPE).reshape(-1)
+    ie = _c(inertial_edges, IBA_EDGE_DTYPE).reshape(-1)
+    pw = _c(pos_w, np.float32).reshape(-1)
+    cl = None if point_close is None else _c(point_close, np.uint8).reshape(-1)
+    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
+    px, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
+    P, E = len(pw) // 3 if cl is None else len(cl), len(ek)
+    if len(pw) != 3 * P or [len(a) for a in (ep, px, ur, inv)] != [E, 2 * E, E, E]:
+        raise ValueError(("pos_w" if cl is None else "pos_w / point_close") + " or the edge arrays disagree in length")
+    return kf, ie, pw, cl, ek, ep, px, ur, inv, P, E
+
+
+def _iba_outputs(K, P, *flags):
+    """fresh (kf, pos, pos_d) and one uint8 array per length in flags"""
+    return (np.zeros(max(K, 1), IBA_KF_OUT_DTYPE), np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64)) + \
+        tuple(np.zeros(max(n, 1), np.uint8) for n in flags)
+
+
+def _stop_flag_ptr(flag):
+    if flag is None:
+        return None
+    if not (isinstance(flag, np.ndarray) and flag.dtype == np.int32 and flag.size == 1 and flag.flags.c_contiguous):
+        raise TypeError("stop_flag must be a contiguous int32 numpy array of one element: the call polls that very memory")
+    return _np_ptr(flag)
+
+
+def _iba_stage_ms(entry, name):
+    ms = np.zeros(5, np.float32)
+    _check(entry(_np_ptr(ms)), name)
+    return dict(zip(FIBA_STAGES, (float(v) for v in ms)))
+
+
 def local_inertial_ba_capacity():
     """the largest number of free KeyFrames msorb_local_inertial_ba accepts"""
     return _iba_lib().msorb_local_inertial_ba_capacity()
@@ -2738,20 +2773,11 @@ def local_inertial_ba(keyframes, inertial_edges, pos_w, point_close, edge_kf, ed
     and, with timing, elapsed_ms (device time).  out: (kf, pos, pos_d, outlier uint8) arrays to be written instead of fresh ones
     (they keep their contents when the call is refused)."""
     L = _iba_lib()
-    kf = _c(keyframes, IBA_KF_DTYPE).reshape(-1)
-    ie = _c(inertial_edges, IBA_EDGE_DTYPE).reshape(-1)
-    pw, cl = _c(pos_w, np.float32).reshape(-1), _c(point_close, np.uint8).reshape(-1)
-    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
-    px, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
-    P, E = len(cl), len(ek)
-    if len(pw) != 3 * P or [len(a) for a in (ep, px, ur, inv)] != [E, 2 * E, E, E]:
-        raise ValueError("pos_w / point_close or the edge arrays disagree in length")
+    kf, ie, pw, cl, ek, ep, px, ur, inv, P, E = _iba_inputs(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2,
+                                                            point_close)
     pr = np.zeros(1, IBA_PROBLEM_DTYPE)
     pr["large"], pr["iterations"] = int(bool(large)), iterations
-    if out is None:
-        out = (np.zeros(max(len(kf), 1), IBA_KF_OUT_DTYPE), np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64),
-               np.zeros(max(E, 1), np.uint8))
-    kf_out, pos, pos_d, flags = out
+    kf_out, pos, pos_d, flags = _iba_outputs(len(kf), P, E) if out is None else out
     res = np.zeros(1, IBA_RESULT_DTYPE)
     ms = C.c_float()
     _check(L.msorb_local_inertial_ba(device, _np_ptr(pr), len(kf), _np_ptr(kf), len(ie), _np_ptr(ie), P, _np_ptr(pw), _np_ptr(cl), E,
@@ -2788,9 +2814,7 @@ def full_inertial_ba_capacity(init):
 
 def full_inertial_ba_stage_ms():
     """the calling thread's last call's device time per stage (FIBA_STAGES); needs MSORB_FULL_INERTIAL_BA_STAGES=1 in the environment"""
-    ms = np.zeros(5, np.float32)
-    _check(_fiba_lib().msorb_full_inertial_ba_stage_ms(_np_ptr(ms)), "msorb_full_inertial_ba_stage_ms")
-    return dict(zip(FIBA_STAGES, (float(v) for v in ms)))
+    return _iba_stage_ms(_fiba_lib().msorb_full_inertial_ba_stage_ms, "msorb_full_inertial_ba_stage_ms")
 
 
 def full_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, init=False, iterations=7, prior_g=0.0,
@@ -2804,27 +2828,15 @@ def full_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, 
     and, with timing, elapsed_ms (device time).  out: (kf, pos, pos_d, included uint8) arrays to be written instead of fresh ones
     (they keep their contents when the call is refused)."""
     L = _fiba_lib()
-    kf = _c(keyframes, IBA_KF_DTYPE).reshape(-1)
-    ie = _c(inertial_edges, IBA_EDGE_DTYPE).reshape(-1)
-    pw = _c(pos_w, np.float32).reshape(-1)
-    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
-    px, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
-    P, E = len(pw) // 3, len(ek)
-    if len(pw) != 3 * P or [len(a) for a in (ep, px, ur, inv)] != [E, 2 * E, E, E]:
-        raise ValueError("pos_w or the edge arrays disagree in length")
+    kf, ie, pw, _, ek, ep, px, ur, inv, P, E = _iba_inputs(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2)
     pr = np.zeros(1, FIBA_PROBLEM_DTYPE)
     pr["init"], pr["iterations"], pr["prior_g"], pr["prior_a"], pr["bg0"], pr["ba0"] = int(bool(init)), iterations, prior_g, prior_a, bg0, ba0
-    if out is None:
-        out = (np.zeros(max(len(kf), 1), IBA_KF_OUT_DTYPE), np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64),
-               np.zeros(max(P, 1), np.uint8))
-    kf_out, pos, pos_d, inc = out
-    flag = stop_flag
-    if flag is not None and not (isinstance(flag, np.ndarray) and flag.dtype == np.int32 and flag.size == 1 and flag.flags.c_contiguous):
-        raise TypeError("stop_flag must be a contiguous int32 numpy array of one element: the call polls that very memory")
+    kf_out, pos, pos_d, inc = _iba_outputs(len(kf), P, P) if out is None else out
+    flag = _stop_flag_ptr(stop_flag)
     res = np.zeros(1, IBA_RESULT_DTYPE)
     ms = C.c_float()
     _check(L.msorb_full_inertial_ba(device, _np_ptr(pr), len(kf), _np_ptr(kf), len(ie), _np_ptr(ie), P, _np_ptr(pw), E, _np_ptr(ek),
-                                    _np_ptr(ep), _np_ptr(px), _np_ptr(ur), _np_ptr(inv), None if flag is None else _np_ptr(flag),
+                                    _np_ptr(ep), _np_ptr(px), _np_ptr(ur), _np_ptr(inv), flag,
                                     _np_ptr(kf_out), _np_ptr(pos), _np_ptr(pos_d), _np_ptr(inc), _np_ptr(res), C.addressof(ms)),
            "msorb_full_inertial_ba")
     r = dict(result=res[0], kf=kf_out[:len(kf)], pos=pos[:P], pos_d=pos_d[:P], included=inc[:P].astype(bool))
@@ -2853,9 +2865,7 @@ def merge_inertial_ba_capacity():
 
 def merge_inertial_ba_stage_ms():
     """the calling thread's last call's device time per stage (FIBA_STAGES); needs MSORB_MERGE_INERTIAL_BA_STAGES=1 in the environment"""
-    ms = np.zeros(5, np.float32)
-    _check(_miba_lib().msorb_merge_inertial_ba_stage_ms(_np_ptr(ms)), "msorb_merge_inertial_ba_stage_ms")
-    return dict(zip(FIBA_STAGES, (float(v) for v in ms)))
+    return _iba_stage_ms(_miba_lib().msorb_merge_inertial_ba_stage_ms, "msorb_merge_inertial_ba_stage_ms")
 
 
 def merge_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2, iterations=0, stop_flag=None,
@@ -2867,27 +2877,15 @@ def merge_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy,
     included bool [P]) and, with timing, elapsed_ms (device time).  out: (kf, pos, pos_d, outlier uint8, included uint8) arrays to
     be written instead of fresh ones (they keep their contents when the call is refused)."""
     L = _miba_lib()
-    kf = _c(keyframes, IBA_KF_DTYPE).reshape(-1)
-    ie = _c(inertial_edges, IBA_EDGE_DTYPE).reshape(-1)
-    pw = _c(pos_w, np.float32).reshape(-1)
-    ek, ep = _c(edge_kf, np.int32).reshape(-1), _c(edge_point, np.int32).reshape(-1)
-    px, ur, inv = _c(xy, np.float32).reshape(-1), _c(u_right, np.float32).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1)
-    P, E = len(pw) // 3, len(ek)
-    if len(pw) != 3 * P or [len(a) for a in (ep, px, ur, inv)] != [E, 2 * E, E, E]:
-        raise ValueError("pos_w or the edge arrays disagree in length")
+    kf, ie, pw, _, ek, ep, px, ur, inv, P, E = _iba_inputs(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy, u_right, inv_sigma2)
     pr = np.zeros(1, IBA_PROBLEM_DTYPE)
     pr["iterations"] = iterations
-    if out is None:
-        out = (np.zeros(max(len(kf), 1), IBA_KF_OUT_DTYPE), np.zeros((max(P, 1), 3), np.float32), np.zeros((max(P, 1), 3), np.float64),
-               np.zeros(max(E, 1), np.uint8), np.zeros(max(P, 1), np.uint8))
-    kf_out, pos, pos_d, flags, inc = out
-    flag = stop_flag
-    if flag is not None and not (isinstance(flag, np.ndarray) and flag.dtype == np.int32 and flag.size == 1 and flag.flags.c_contiguous):
-        raise TypeError("stop_flag must be a contiguous int32 numpy array of one element: the call polls that very memory")
+    kf_out, pos, pos_d, flags, inc = _iba_outputs(len(kf), P, E, P) if out is None else out
+    flag = _stop_flag_ptr(stop_flag)
     res = np.zeros(1, IBA_RESULT_DTYPE)
     ms = C.c_float()
     _check(L.msorb_merge_inertial_ba(device, _np_ptr(pr), len(kf), _np_ptr(kf), len(ie), _np_ptr(ie), P, _np_ptr(pw), E, _np_ptr(ek),
-                                     _np_ptr(ep), _np_ptr(px), _np_ptr(ur), _np_ptr(inv), None if flag is None else _np_ptr(flag),
+                                     _np_ptr(ep), _np_ptr(px), _np_ptr(ur), _np_ptr(inv), flag,
                                      _np_ptr(kf_out), _np_ptr(pos), _np_ptr(pos_d), _np_ptr(flags), _np_ptr(inc), _np_ptr(res),
                                      C.addressof(ms)), "msorb_merge_inertial_ba")
     r = dict(result=res[0], kf=kf_out[:len(kf)], pos=pos[:P], pos_d=pos_d[:P], outlier=flags[:E].astype(bool), included=inc[:P].astype(bool))

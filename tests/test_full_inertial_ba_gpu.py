@@ -1,4 +1,4 @@
-"""Optimizer::FullInertialBA on the device (csrc/full_inertial_ba.hip) through the C ABI and its Python mirror, against the forward
+"""Optimizer::FullInertialBA on the device (csrc/inertial_ba_engine.hip) through the C ABI and its Python mirror, against the forward
 restatement of tests/full_inertial_ba_cases.py and against the host program (the same header through g++ and glibc, a serial
 executor, the column-by-column solve).
 

@@ -1,4 +1,4 @@
-"""Optimizer::MergeInertialBA on the device (csrc/merge_inertial_ba.hip) through the C ABI and its Python mirror, against the forward
+"""Optimizer::MergeInertialBA on the device (csrc/inertial_ba_engine.hip) through the C ABI and its Python mirror, against the forward
 restatement of tests/merge_inertial_ba_cases.py and against the host program (the same header through g++ and glibc, a serial
 executor, the column-by-column solve).
 
@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import full_inertial_ba_cases as fc
 import local_inertial_ba_cases as lc
 import merge_inertial_ba_cases as mc
 
@@ -220,3 +221,25 @@ def test_the_other_two_entries_still_refuse_kind_3(msorb_mod):
     with pytest.raises(msorb_mod.MsorbError) as ei:
         msorb_mod.full_inertial_ba(s["kf"], s["ie"], s["pos"], s["edge_kf"], s["edge_pt"], s["xy"], s["ur"], s["inv"], iterations=1)
     assert ei.value.code == -1
+
+
+def test_both_routines_interleaved_on_one_thread_return_the_bytes_of_a_call_alone(msorb_mod):
+    """FullInertialBA and MergeInertialBA share one device block, one pinned block, one stream and one pool of events per thread.  The
+    sequence grows the block, makes a smaller call of the other layout read what a larger one left in it, and comes back."""
+    def full(name):
+        sc = fc.scene(name)
+        return msorb_mod.full_inertial_ba(*_args(sc), init=bool(sc["init"]), iterations=int(sc["iterations"]), prior_g=sc["prior_g"],
+                                          prior_a=sc["prior_a"], bg0=sc["bg0"], ba0=sc["ba0"])
+    calls = {"f1": full, "i1": full, "f16": full, "small": lambda n: _run(msorb_mod, mc.scene(n)),
+             "pose_only_many": lambda n: _run(msorb_mod, mc.scene(n))}
+
+    def kept(name):
+        out = calls[name](name)
+        assert int(out["result"]["status"]) == 0, name
+        return {k: out[k].tobytes() for k in ("kf", "pos", "pos_d", "included", "result", "outlier") if k in out}
+    alone = {name: kept(name) for name in calls}
+    assert all(("outlier" in alone[n]) == (n in ("small", "pose_only_many")) for n in alone)
+    for i, name in enumerate(("f16", "small", "i1", "pose_only_many", "f1", "small", "f16")):
+        got = kept(name)
+        for k in alone[name]:
+            assert got[k] == alone[name][k], (i, name, k)
