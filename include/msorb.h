@@ -812,7 +812,8 @@ int msorb_kf_database_query(msorb_kf_database* db, const int* word, const double
 /* Optimizer::PoseOptimization (src/Optimizer.cc:759-1037) for pinhole mono / stereo frames on the device: the four rounds, every
  * Levenberg step and trial of g2o (core/optimization_algorithm_levenberg.cpp:61-170) and the classification after each round in
  * ONE launch, in double.  Appended to ABI 6002 as the KeyFrame database was: MSORB_ABI_VERSION stays 6002, so a caller that
- * needs these entries asks the loader for them.  The two-camera arm (:870-931) and the inertial variants are not covered.
+ * needs these entries asks the loader for them.  The two-camera arm (:870-931) has its own entry at the end of this header
+ * (msorb_pose_optimization_rig_batch); the inertial variants are not covered here.
  * An observation is a stereo edge when its u_right >= 0 (:808) and a mono edge otherwise.  Two calls on the same input return
  * the same bits.  Re-entrant: every calling thread has its own stream and staging. */
 typedef struct msorb_pose_problem {      /* one Optimizer::PoseOptimization call */
@@ -1683,6 +1684,37 @@ int msorb_welding_ba(int device, int n_kf, const msorb_ba_keyframe* kfs, int n_p
                      const float* inv_sigma2, const volatile int* stop_flag,
                      float* kf_qt_out, double* kf_qt_d, float* pos_out, double* pos_d, uint8_t* edge_level1, uint8_t* edge_outlier,
                      msorb_welding_ba_result* r, float* elapsed_ms);
+
+/* Optimizer::PoseOptimization for a frame with a second camera (the arm src/Optimizer.cc:870-931, e.g. a KannalaBrandt8 stereo rig)
+ * and for a one-camera frame whose camera is not a pinhole, on the device: the routine of msorb_pose_optimization_batch (the four
+ * rounds, g2o's Levenberg loop, the classifications, in double, ONE launch) over the edges EdgeSE3ProjectXYZOnlyPose (left camera:
+ * obs - pCamera->project(T.map(Xw)), Jacobian -projectJac * SE3deriv) and EdgeSE3ProjectXYZOnlyPoseToBody (right camera, through
+ * mTrl; OptimizableTypes.{h,cpp}).  Every edge has two rows, deltaMono and chi2Mono: the reference cannot build a stereo edge in
+ * this arm.  Appended to ABI 6002: MSORB_ABI_VERSION stays 6002.  msorb_pose_result is the one of msorb_pose_optimization_batch.
+ * A camera is GeometricCamera::mvParameters as floats: type 0 = Pinhole (fx fy cx cy in p[0..3]), 1 = KannalaBrandt8 (fx fy cx cy
+ * k0 k1 k2 k3 in p[0..7]).  KannalaBrandt8::project(Vector3d) takes theta and psi through float sqrtf / atan2f
+ * (KannalaBrandt8.cpp:48-49): the device narrows a double atan2 once where glibc runs its float algorithm, so a projection may
+ * differ from the reference's by one float ulp of theta or psi now and then (DESIGN.md has the measured share).  A point exactly
+ * on a KannalaBrandt8 camera's optical axis gives the reference 0/0 in projectJac; that case is not restated.
+ * With n_cameras == 1 and a pinhole the result equals msorb_pose_optimization_batch with every u_right < 0, bit for bit. */
+typedef struct msorb_camera_model { int type; float p[8]; } msorb_camera_model;
+typedef struct msorb_pose_rig_problem {
+    float q[4], t[3];            /* pFrame->GetPose(), the LEFT camera: unit quaternion x,y,z,w + translation */
+    int n_cameras;               /* 1 or 2 */
+    msorb_camera_model cam[2];   /* mpCamera, mpCamera2 */
+    float q_rl[4], t_rl[3];      /* pFrame->GetRelativePoseTrl(); read when n_cameras == 2 */
+    int n;                       /* observations */
+} msorb_pose_rig_problem;
+/* Observations up to which a problem is held in registers; a larger one walks global memory (same additions, same result). */
+int msorb_pose_optimization_rig_capacity(void);
+/* As msorb_pose_optimization_batch (one upload, one launch, one read-back; obs_offset, xy, inv_sigma2, pos_w, outlier_out, results,
+ * elapsed_ms and n < 3 as there), with camera [per observation: 0 = seen by the left camera (i < Nleft, mvKeys), 1 = by the right
+ * (mvKeysRight)] in place of u_right.  Left and right observations may come in any order and are summed in the order given.
+ * MSORB_E_INVALID, with nothing launched: a camera type other than 0 / 1, n_cameras outside {1, 2}, camera[i] == 1 (or above) in
+ * a problem with one camera.  Two calls on the same input return the same bits.  Re-entrant per calling thread. */
+int msorb_pose_optimization_rig_batch(int device, int n_problems, const msorb_pose_rig_problem* problems, const int* obs_offset,
+                                      const float* xy, const uint8_t* camera, const float* inv_sigma2, const float* pos_w,
+                                      uint8_t* outlier_out, msorb_pose_result* results, float* elapsed_ms);
 
 #ifdef __cplusplus
 }

@@ -18,6 +18,11 @@
 // classification is what the LAST computeActiveErrors left, i.e. the error at the last TRIAL pose, also when that trial was rejected
 // and the pose popped.  Every pass therefore writes the edge's chi2 into its per-edge state, and the classification re-computes only
 // the edges that are outliers at that moment.
+//
+// Two kernels share all of the above through one template over an edge model: pose_opt_kernel (PinholeModel: pFrame->fx ... mbf, mono
+// and stereo edges, the arm :806-867) and pose_opt_rig_kernel (RigModel: the arm :870-931 and a one-camera frame whose camera is not
+// a pinhole; mono edges through pCamera->project / projectJac of pose_rig_device.h, the right camera's through mTrl).  The pinhole
+// instantiation is the kernel this file has always had: same registers, same private and LDS bytes, same result bits.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -30,6 +35,7 @@
 #include "../../include/msorb.h"
 #include "hip_host.h"
 #include "matcher_host.h"
+#include "pose_rig_device.h"
 #include "se3_device.h"
 
 namespace msorb {
@@ -194,23 +200,107 @@ __device__ inline bool solve6(const double* Hu, double lambda, const double* b, 
     return true;
 }
 
+// ---- the edge models.  pose_opt_problem below (the rounds, the Levenberg loop, the sums, the classification) is written once over
+// a model M: its argument block and problem record, what it derives from the problem (Setup) and from a pose (AtPose), how an
+// observation is loaded, whether an edge may have a third row, the error and the Jacobian.
+struct PinholeModel {   // the arm :806-867: pFrame->fx ... mbf, mono and stereo edges
+    typedef PoseArgs Args;
+    typedef PoseProblemDev Problem;
+    typedef Cam Setup;
+    struct AtPose {};
+    static constexpr int kPer = kPerThread;
+    static constexpr bool kStereoEdges = true;    // u_right >= 0: a three-row edge (:808)
+    __device__ static inline Setup setup(const Problem& P) {
+        return Cam{(double)P.p.fx, (double)P.p.fy, (double)P.p.cx, (double)P.p.cy, (double)P.p.mbf};
+    }
+    __device__ static inline AtPose at_pose(const Setup&, const Pose&) { return AtPose{}; }
+    __device__ static inline Ob load(const Args& A, int i) { return load_ob(A, i); }
+    __device__ static inline double error(const Pose& T, const AtPose&, const Setup& c, const Ob& o, double* e, double& x, double& y, double& z) {
+        return edge_error(T, c, o, e, x, y, z);
+    }
+    __device__ static inline void jacobian(const Setup& c, const Ob&, bool stereo, double x, double y, double z, double (*J)[6]) {
+        edge_jacobian(c, stereo, x, y, z, J);
+    }
+};
+
+// The arm :870-931 and a one-camera frame through pCamera->project: mono edges only, Ob.ur carries the camera (0 left, 1 right).
+// kRigPerThread: the KannalaBrandt8 edge holds more live doubles than the pinhole one, but with the problem's uniform data in LDS (see
+// setup) 8 observations per thread spill no VGPR (DESIGN.md section 28 has the compiler's figures), so the capacity is the pinhole's.
+constexpr int kRigPerThread = 8;
+struct RigProblemDev {
+    msorb_pose_rig_problem p;
+    int obs0;
+};
+static_assert(sizeof(msorb_camera_model) == 36 && sizeof(msorb_pose_rig_problem) == 136 && sizeof(msorb_camera_model) == sizeof(msorb::rig::Camera),
+              "the records of include/msorb.h as the Python mirror lays them out");
+struct RigArgs {
+    const RigProblemDev* prob;
+    const float* xy;
+    const uint8_t* camera;
+    const float* inv_sigma2;
+    const float* pos_w;
+    float delta_mono, delta_stereo;   // delta_stereo is never read: the arm has no stereo edge
+    double* chi2_ws;
+    uint8_t* outlier;
+    msorb_pose_result* result;
+};
+struct RigModel {
+    typedef RigArgs Args;
+    typedef RigProblemDev Problem;
+    struct Setup { const msorb::rig::Rig* g; };   // in LDS: uniform, read where an edge needs it, so it holds no registers between
+    typedef Pose AtPose;   // mTrl * estimate, the product the right camera's computeError maps through
+    static constexpr int kPer = kRigPerThread;
+    static constexpr bool kStereoEdges = false;   // Ob.ur is the camera, not a coordinate
+    __device__ static inline Setup setup(const Problem& P) {
+        __shared__ msorb::rig::Rig g;
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                g.cam[c].type = P.p.cam[c].type;
+#pragma unroll
+                for (int k = 0; k < 8; k++) g.cam[c].p[k] = P.p.cam[c].p[k];
+            }
+            const float q1[4] = {0, 0, 0, 1}, t1[3] = {0, 0, 0};
+            if (P.p.n_cameras == 2) msorb::rig::set_trl(g, P.p.q_rl, P.p.t_rl);
+            else msorb::rig::set_trl(g, q1, t1);   // never read: no observation names the right camera
+        }
+        __syncthreads();
+        return Setup{&g};
+    }
+    __device__ static inline AtPose at_pose(const Setup& s, const Pose& T) { return msorb::rig::compose(s.g->Trl, T); }
+    __device__ static inline Ob load(const Args& A, int i) {
+        Ob o;
+        o.x = A.xy[2 * (size_t)i]; o.y = A.xy[2 * (size_t)i + 1]; o.ur = (float)A.camera[i]; o.w = A.inv_sigma2[i];
+        o.X = A.pos_w[3 * (size_t)i]; o.Y = A.pos_w[3 * (size_t)i + 1]; o.Z = A.pos_w[3 * (size_t)i + 2];
+        return o;
+    }
+    __device__ static inline double error(const Pose& T, const AtPose& Trw, const Setup& s, const Ob& o, double* e, double& x, double& y, double& z) {
+        e[2] = 0;
+        return msorb::rig::edge_error(*s.g, T, Trw, o.ur != 0, (double)o.x, (double)o.y, (double)o.w, (double)o.X, (double)o.Y, (double)o.Z, e, x, y, z);
+    }
+    __device__ static inline void jacobian(const Setup& s, const Ob& o, bool, double x, double y, double z, double (*J)[6]) {
+        msorb::rig::edge_jacobian(*s.g, o.ur != 0, x, y, z, J);
+    }
+};
+
 // per-edge state of the register-resident form
+template <int PER>
 struct Resident {
-    Ob ob[kPerThread];
-    double chi2[kPerThread];
-    uint8_t level[kPerThread];   // 1 = outlier (e->setLevel(1), Optimizer.cc:966-972)
+    Ob ob[PER];
+    double chi2[PER];
+    uint8_t level[PER];   // 1 = outlier (e->setLevel(1), Optimizer.cc:966-972)
 };
 
 // f(ob, chi2&, level&) over the thread's observations in ascending index
-template <bool RES, typename F>
-__device__ inline void for_each_edge(const PoseArgs& A, Resident& r, int obs0, int n, F f) {
+template <bool RES, typename M, typename F>
+__device__ inline void for_each_edge(const typename M::Args& A, Resident<M::kPer>& r, int obs0, int n, F f) {
     if constexpr (RES) {
 #pragma unroll
-        for (int k = 0; k < kPerThread; k++)
+        for (int k = 0; k < M::kPer; k++)
             if ((int)threadIdx.x + k * kThreads < n) f(r.ob[k], r.chi2[k], r.level[k]);
     } else {
         for (int i = threadIdx.x; i < n; i += kThreads) {
-            const Ob o = load_ob(A, obs0 + i);
+            const Ob o = M::load(A, obs0 + i);
             double chi2 = A.chi2_ws[obs0 + i];
             uint8_t level = A.outlier[obs0 + i];
             f(o, chi2, level);
@@ -220,18 +310,18 @@ __device__ inline void for_each_edge(const PoseArgs& A, Resident& r, int obs0, i
     }
 }
 
-template <bool RES>
-__device__ void pose_opt_problem(const PoseArgs& A, double* lds) {
-    const PoseProblemDev P = A.prob[blockIdx.x];
+template <bool RES, typename M>
+__device__ void pose_opt_problem(const typename M::Args& A, double* lds) {
+    const typename M::Problem P = A.prob[blockIdx.x];
     const int n = P.p.n, obs0 = P.obs0;
-    const Cam cam{(double)P.p.fx, (double)P.p.fy, (double)P.p.cx, (double)P.p.cy, (double)P.p.mbf};
+    const typename M::Setup cam = M::setup(P);
     const double d_mono = (double)A.delta_mono, d_stereo = (double)A.delta_stereo;
-    Resident r;
+    Resident<M::kPer> r;
     if constexpr (RES) {
 #pragma unroll
-        for (int k = 0; k < kPerThread; k++) {
+        for (int k = 0; k < M::kPer; k++) {
             const int i = threadIdx.x + k * kThreads;
-            r.ob[k] = i < n ? load_ob(A, obs0 + i) : Ob{};
+            r.ob[k] = i < n ? M::load(A, obs0 + i) : Ob{};
             r.chi2[k] = 0;
             r.level[k] = 0;
         }
@@ -258,14 +348,16 @@ __device__ void pose_opt_problem(const PoseArgs& A, double* lds) {
                 double S[kSums];
 #pragma unroll
                 for (int k = 0; k < kSums; k++) S[k] = 0;
-                for_each_edge<RES>(A, r, obs0, n, [&](const Ob& o, double& chi2, uint8_t& level) {
+                const typename M::AtPose V = M::at_pose(cam, T);
+                for_each_edge<RES, M>(A, r, obs0, n, [&](const Ob& o, double& chi2, uint8_t& level) {
                     if (level) return;
                     double e[3], px, py, pz, J[3][6], rho0, rho1;
-                    const bool stereo = o.ur >= 0;
-                    chi2 = edge_error(T, cam, o, e, px, py, pz);        // computeActiveErrors (:75)
+                    // (the expression, not a function of the model taking `o`: that form cost the pinhole kernel 28 AGPRs)
+                    const bool stereo = M::kStereoEdges && o.ur >= 0;
+                    chi2 = M::error(T, V, cam, o, e, px, py, pz);       // computeActiveErrors (:75)
                     huber(chi2, stereo ? d_stereo : d_mono, robust, rho0, rho1);
                     S[27] += rho0;                                      // activeRobustChi2 (:82)
-                    edge_jacobian(cam, stereo, px, py, pz, J);          // buildSystem (:87): base_unary_edge.hpp:43-72
+                    M::jacobian(cam, o, stereo, px, py, pz, J);         // buildSystem (:87): base_unary_edge.hpp:43-72
                     const double w = (double)o.w, wr = rho1 * w;        // robustInformation (base_edge.h:96-100)
                     int k = 0;
 #pragma unroll
@@ -300,11 +392,12 @@ __device__ void pose_opt_problem(const PoseArgs& A, double* lds) {
                     const bool ok2 = solve6(Hu, lambda, b, x);   // :109-110
                     T = oplus(T, x);                             // :115
                     double c1[1] = {0};
-                    for_each_edge<RES>(A, r, obs0, n, [&](const Ob& o, double& chi2, uint8_t& level) {
+                    const typename M::AtPose Vt = M::at_pose(cam, T);
+                    for_each_edge<RES, M>(A, r, obs0, n, [&](const Ob& o, double& chi2, uint8_t& level) {
                         if (level) return;
                         double e[3], px, py, pz, rho0, rho1;
-                        chi2 = edge_error(T, cam, o, e, px, py, pz);   // :123
-                        huber(chi2, o.ur >= 0 ? d_stereo : d_mono, robust, rho0, rho1);
+                        chi2 = M::error(T, Vt, cam, o, e, px, py, pz);   // :123
+                        huber(chi2, M::kStereoEdges && o.ur >= 0 ? d_stereo : d_mono, robust, rho0, rho1);
                         c1[0] += rho0;                                 // :124
                     });
                     block_sum<1>(c1, lds + (buf ^= 1) * kWaves * kSums);
@@ -342,11 +435,12 @@ __device__ void pose_opt_problem(const PoseArgs& A, double* lds) {
         rejected[it] = n_rejected;
         // ---- the classification (Optimizer.cc:953-1024) ----
         double bad[1] = {0};
-        for_each_edge<RES>(A, r, obs0, n, [&](const Ob& o, double& chi2, uint8_t& level) {
-            const bool stereo = o.ur >= 0;
-            if (level) {   // :959-961, :1007-1009
+        const typename M::AtPose Vc = M::at_pose(cam, T);
+        for_each_edge<RES, M>(A, r, obs0, n, [&](const Ob& o, double& chi2, uint8_t& level) {
+            const bool stereo = M::kStereoEdges && o.ur >= 0;
+            if (level) {   // :959-961, :1007-1009 (:983-985 for the right camera's edges)
                 double e[3], px, py, pz;
-                chi2 = edge_error(T, cam, o, e, px, py, pz);
+                chi2 = M::error(T, Vc, cam, o, e, px, py, pz);
             }
             const float c = (float)chi2;   // :963, :1011
             level = c > (stereo ? 7.815f : 5.991f) ? 1 : 0;
@@ -359,7 +453,7 @@ __device__ void pose_opt_problem(const PoseArgs& A, double* lds) {
     }
     if constexpr (RES) {
 #pragma unroll
-        for (int k = 0; k < kPerThread; k++) {
+        for (int k = 0; k < M::kPer; k++) {
             const int i = threadIdx.x + k * kThreads;
             if (i < n) A.outlier[obs0 + i] = r.level[k];
         }
@@ -376,11 +470,11 @@ __device__ void pose_opt_problem(const PoseArgs& A, double* lds) {
     }
 }
 
-__global__ __launch_bounds__(kThreads) void pose_opt_kernel(const PoseArgs A) {
-    __shared__ double lds[2 * kWaves * kSums];
+template <typename M>
+__device__ inline void pose_opt_block(const typename M::Args& A, double* lds) {
     const int n = A.prob[blockIdx.x].p.n;
-    if (n < 3) {   // :936-937: return 0, the frame's pose as it was, the flags cleared by the gathering loop (:810, :837)
-        const PoseProblemDev P = A.prob[blockIdx.x];
+    if (n < 3) {   // :936-937: return 0, the frame's pose as it was, the flags cleared by the gathering loop (:810, :837, :878, :907)
+        const typename M::Problem P = A.prob[blockIdx.x];
         for (int i = threadIdx.x; i < n; i += kThreads) A.outlier[P.obs0 + i] = 0;
         if (threadIdx.x == 0) {
             msorb_pose_result& R = A.result[blockIdx.x];
@@ -391,8 +485,18 @@ __global__ __launch_bounds__(kThreads) void pose_opt_kernel(const PoseArgs A) {
         }
         return;
     }
-    if (n <= kResident) pose_opt_problem<true>(A, lds);
-    else pose_opt_problem<false>(A, lds);
+    if (n <= M::kPer * kThreads) pose_opt_problem<true, M>(A, lds);
+    else pose_opt_problem<false, M>(A, lds);
+}
+
+__global__ __launch_bounds__(kThreads) void pose_opt_kernel(const PoseArgs A) {
+    __shared__ double lds[2 * kWaves * kSums];
+    pose_opt_block<PinholeModel>(A, lds);
+}
+
+__global__ __launch_bounds__(kThreads) void pose_opt_rig_kernel(const RigArgs A) {
+    __shared__ double lds[2 * kWaves * kSums];
+    pose_opt_block<RigModel>(A, lds);
 }
 
 int hip_fail(ThreadScratch& scr, const char* what, hipError_t e) {
@@ -422,10 +526,34 @@ struct Staged {
     }
 };
 
-int run_staged(ThreadScratch& scr, const Staged& L, const KpLite* d_kp, const float* level_inv_sigma2, int nlevels, hipStream_t after,
-               float* elapsed_ms) {
+// the upload [0, in_bytes), the launch of one workgroup per problem, the read-back [o_res, o_end), the synchronisation
+template <typename ArgsT>
+int launch_staged(ThreadScratch& scr, void (*kernel)(const ArgsT), const ArgsT& A, int n_problems, size_t in_bytes, size_t o_res, size_t o_end, hipStream_t after,
+                  float* elapsed_ms) {
     uint8_t *const h = scr.h.p, *const d = scr.d.p;
     hipStream_t s = scr.s;
+    hipError_t e = hipSuccess;
+    if (after) {   // the handle's keypoint table may still be in flight on the handle's stream
+        e = hipEventRecord(scr.ev[2], after);
+        if (e == hipSuccess) e = hipStreamWaitEvent(s, scr.ev[2], 0);
+    }
+    if (e == hipSuccess) e = msorb::small_copy(d, h, in_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(kernel, dim3(n_problems), dim3(kThreads), 0, s, A);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
+    if (e == hipSuccess) e = msorb::small_copy(h + o_res, d + o_res, o_end - o_res, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
+    if (e != hipSuccess) return hip_fail(scr, "pose_optimization", e);
+    return MSORB_OK;
+}
+
+int run_staged(ThreadScratch& scr, const Staged& L, const KpLite* d_kp, const float* level_inv_sigma2, int nlevels, hipStream_t after,
+               float* elapsed_ms) {
+    uint8_t* const d = scr.d.p;
     PoseArgs A{};
     A.prob = reinterpret_cast<const PoseProblemDev*>(d + L.o_prob);
     if (L.frame) {
@@ -443,23 +571,7 @@ int run_staged(ThreadScratch& scr, const Staged& L, const KpLite* d_kp, const fl
     A.result = reinterpret_cast<msorb_pose_result*>(d + L.o_res);
     A.outlier = d + L.o_out;
     A.chi2_ws = reinterpret_cast<double*>(d + L.o_ws);
-    hipError_t e = hipSuccess;
-    if (after) {   // the handle's keypoint table may still be in flight on the handle's stream
-        e = hipEventRecord(scr.ev[2], after);
-        if (e == hipSuccess) e = hipStreamWaitEvent(s, scr.ev[2], 0);
-    }
-    if (e == hipSuccess) e = msorb::small_copy(d, h, L.in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[0], s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(pose_opt_kernel, dim3(L.n_problems), dim3(kThreads), 0, s, A);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && elapsed_ms) e = hipEventRecord(scr.ev[1], s);
-    if (e == hipSuccess) e = msorb::small_copy(h + L.o_res, d + L.o_res, L.o_ws - L.o_res, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && elapsed_ms) e = hipEventElapsedTime(elapsed_ms, scr.ev[0], scr.ev[1]);
-    if (e != hipSuccess) return hip_fail(scr, "pose_optimization", e);
-    return MSORB_OK;
+    return launch_staged(scr, pose_opt_kernel, A, L.n_problems, L.in_bytes, L.o_res, L.o_ws, after, elapsed_ms);
 }
 
 }  // namespace
@@ -529,5 +641,71 @@ extern "C" int msorb_frame_pose_optimization(msorb_frame* f, const msorb_pose_pr
     std::memcpy(r, h + L.o_res, sizeof(msorb_pose_result));
     const uint8_t* out = h + L.o_out;
     for (size_t k = 0; k < m; k++) outlier[idx[k]] = out[k];
+    return MSORB_OK;
+}
+
+// ---- the two-camera arm and the non-pinhole one-camera frame (RigModel)
+extern "C" int msorb_pose_optimization_rig_capacity(void) { return kRigPerThread * kThreads; }
+
+extern "C" int msorb_pose_optimization_rig_batch(int device, int n_problems, const msorb_pose_rig_problem* problems, const int* obs_offset,
+                                                 const float* xy, const uint8_t* camera, const float* inv_sigma2, const float* pos_w,
+                                                 uint8_t* outlier_out, msorb_pose_result* results, float* elapsed_ms) {
+    if (elapsed_ms) *elapsed_ms = 0;
+    if (n_problems < 0 || (n_problems > 0 && (!problems || !obs_offset || !results))) return MSORB_E_INVALID;
+    if (n_problems == 0) return MSORB_OK;
+    bool strided = false;
+    if (obs_offset[0] != 0) { set_last_error("pose_optimization_rig_batch: obs_offset[0] must be 0"); return MSORB_E_INVALID; }
+    for (int i = 0; i < n_problems; i++) {
+        const msorb_pose_rig_problem& p = problems[i];
+        if (p.n < 0 || obs_offset[i + 1] - obs_offset[i] != p.n) {
+            set_last_error("pose_optimization_rig_batch: obs_offset does not match the problems' n");
+            return MSORB_E_INVALID;
+        }
+        if (p.n_cameras != 1 && p.n_cameras != 2) { set_last_error("pose_optimization_rig_batch: n_cameras must be 1 or 2"); return MSORB_E_INVALID; }
+        for (int c = 0; c < p.n_cameras; c++)
+            if (p.cam[c].type != msorb::rig::kPinhole && p.cam[c].type != msorb::rig::kKannalaBrandt8) {
+                set_last_error("pose_optimization_rig_batch: unknown camera type");
+                return MSORB_E_INVALID;
+            }
+        strided |= p.n > kRigPerThread * kThreads;
+    }
+    const size_t total = (size_t)obs_offset[n_problems];
+    if (total > 0 && (!xy || !camera || !inv_sigma2 || !pos_w || !outlier_out)) return MSORB_E_INVALID;
+    for (int i = 0; i < n_problems; i++)
+        for (int k = obs_offset[i]; k < obs_offset[i + 1]; k++)
+            if (camera[k] >= problems[i].n_cameras) {
+                set_last_error("pose_optimization_rig_batch: an observation names a camera the problem does not have");
+                return MSORB_E_INVALID;
+            }
+    if (int rc = msorb::require_device(device)) return rc;
+    // staging: [problems | xy | camera | inv_sigma2 | pos_w] up, [results | outlier] down, then the chi2 workspace of the strided problems
+    const size_t o_xy = up16((size_t)n_problems * sizeof(RigProblemDev)), o_cam = o_xy + up16(total * 8), o_inv = o_cam + up16(total);
+    const size_t o_pos = o_inv + up16(total * 4), in_bytes = o_pos + up16(total * 12);
+    const size_t o_res = in_bytes, o_out = o_res + up16((size_t)n_problems * sizeof(msorb_pose_result)), o_ws = o_out + up16(total);
+    static thread_local ThreadScratch scr(true, 3);
+    if (int rc = scr.acquire(device, o_ws + (strided ? total * 8 : 0), o_ws)) return rc;
+    uint8_t *const h = scr.h.p, *const d = scr.d.p;
+    RigProblemDev* hp = reinterpret_cast<RigProblemDev*>(h);
+    for (int i = 0; i < n_problems; i++) { hp[i].p = problems[i]; hp[i].obs0 = obs_offset[i]; }
+    if (total) {
+        std::memcpy(h + o_xy, xy, total * 8);
+        std::memcpy(h + o_cam, camera, total);
+        std::memcpy(h + o_inv, inv_sigma2, total * 4);
+        std::memcpy(h + o_pos, pos_w, total * 12);
+    }
+    RigArgs A{};
+    A.prob = reinterpret_cast<const RigProblemDev*>(d);
+    A.xy = reinterpret_cast<const float*>(d + o_xy);
+    A.camera = d + o_cam;
+    A.inv_sigma2 = reinterpret_cast<const float*>(d + o_inv);
+    A.pos_w = reinterpret_cast<const float*>(d + o_pos);
+    A.delta_mono = (float)std::sqrt(5.991);
+    A.delta_stereo = (float)std::sqrt(7.815);
+    A.result = reinterpret_cast<msorb_pose_result*>(d + o_res);
+    A.outlier = d + o_out;
+    A.chi2_ws = reinterpret_cast<double*>(d + o_ws);
+    if (int rc = launch_staged(scr, pose_opt_rig_kernel, A, n_problems, in_bytes, o_res, o_ws, nullptr, elapsed_ms)) return rc;
+    std::memcpy(results, h + o_res, (size_t)n_problems * sizeof(msorb_pose_result));
+    if (total) std::memcpy(outlier_out, h + o_out, total);
     return MSORB_OK;
 }

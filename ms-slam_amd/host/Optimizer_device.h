@@ -13,8 +13,9 @@
 // What runs where.  The gathering loop (:799-934, under MapPoint::mGlobalMutex) stays on the host: it reads the map points.
 // The four rounds, every Levenberg step and the classifications are one device launch.
 //
-// Scope: pinhole mono / stereo frames.  A frame with a second camera (pFrame->mpCamera2, the arm :870-931) is NOT handled:
-// the function returns -1 without touching the frame and the caller keeps Optimizer::PoseOptimization for it (the inertial
+// Scope: pinhole mono / stereo frames.  A frame with a second camera (pFrame->mpCamera2, the arm :870-931) is NOT handled by
+// these two: they return -1 without touching the frame (PoseOptimizationAnyCamera below takes such a frame, and a one-camera
+// frame whose camera is not a pinhole, to the device; a caller without it keeps Optimizer::PoseOptimization) (the inertial
 // variants, PoseInertialOptimizationLastKeyFrame / LastFrame, have templates of their own at the end of this header).  The camera is read from pFrame->fx, fy, cx, cy, mbf, which for Pinhole are the values pCamera->project
 // uses (mvParameters[0..3]).
 //
@@ -131,6 +132,97 @@ int PoseOptimization(FrameT* pFrame, msorb_frame* resident, int device = 0) {
 template <class FrameT>
 int PoseOptimization(FrameT* pFrame) {
     return PoseOptimization(pFrame, static_cast<msorb_frame*>(nullptr));
+}
+
+// Optimizer::PoseOptimization for every camera the device knows (msorb_pose_optimization_rig_batch):
+//
+//   int ORB_SLAM3::msorb_host::PoseOptimizationAnyCamera(Frame* pFrame[, msorb_frame* resident])
+//
+//   * a pinhole frame without a second camera is handed to PoseOptimization above, `resident` included, and is what that returns;
+//   * a frame with a second camera (the arm :870-931, e.g. a KannalaBrandt8 stereo rig): the observation of entry i is mvKeys[i] seen
+//     by mpCamera for i < Nleft and mvKeysRight[i - Nleft] seen by mpCamera2 through GetRelativePoseTrl() otherwise;
+//   * a one-camera frame whose camera is not a pinhole: mvKeysUn[i] through pCamera->project, as the reference's mono edge has it
+//     (PoseOptimization above must NOT be given such a frame: it reads pFrame->fx ... cy and would optimise it as a pinhole).
+// The cameras are read through GetType() / getParameter(k) (4 parameters for CAM_PINHOLE, 8 for CAM_FISHEYE).  Effects as the
+// reference's: mvbOutlier of every entry with a usable map point, SetPose with the narrowed estimate, the return value
+// nInitialCorrespondences - nBad (0, and no SetPose, below three correspondences).  `resident` is not used for these two kinds of
+// frame: a handle's keypoint table holds one camera's keys.
+// Returns -1 with NOTHING touched, and the caller keeps Optimizer::PoseOptimization, for a camera type other than those two and
+// for a one-camera non-pinhole frame with a stereo observation (mvuRight[i] >= 0 on a usable entry: the reference would build a
+// pinhole stereo edge from pFrame->fx ... mbf there; the two-camera arm never reads mvuRight).
+template <class FrameT>
+int PoseOptimizationAnyCamera(FrameT* pFrame, msorb_frame* resident, int device = 0) {
+    typedef typename std::decay<decltype(*pFrame->mpCamera)>::type CameraT;
+    typedef typename std::decay<decltype(*pFrame->mvpMapPoints[0])>::type MapPointT;
+    const bool rig = static_cast<bool>(pFrame->mpCamera2);
+    if (!rig && pFrame->mpCamera->GetType() == CameraT::CAM_PINHOLE) return PoseOptimization(pFrame, resident, device);
+    msorb_pose_rig_problem p;
+    std::memset(&p, 0, sizeof p);
+    p.n_cameras = rig ? 2 : 1;
+    for (int c = 0; c < p.n_cameras; c++) {
+        auto& cam = c == 0 ? *pFrame->mpCamera : *pFrame->mpCamera2;   // (GetType and getParameter are not const in the reference)
+        const auto type = cam.GetType();
+        int n_par;
+        if (type == CameraT::CAM_PINHOLE) { p.cam[c].type = 0; n_par = 4; }
+        else if (type == CameraT::CAM_FISHEYE) { p.cam[c].type = 1; n_par = 8; }
+        else return -1;
+        for (int k = 0; k < n_par; k++) p.cam[c].p[k] = cam.getParameter(k);
+    }
+    const int N = pFrame->N;
+    static thread_local std::vector<uint8_t> camera, out;
+    static thread_local std::vector<float> pos, xy, inv;
+    static thread_local std::vector<int> index;
+    index.clear(); camera.clear(); pos.clear(); xy.clear(); inv.clear();
+    {
+        std::unique_lock<std::mutex> lock(MapPointT::mGlobalMutex);   // :800
+        for (int i = 0; i < N; i++) {
+            const auto pMP = pFrame->mvpMapPoints[i];
+            if (!(pMP && !pMP->isBad())) continue;                    // :804
+            if (!rig && pFrame->mvuRight[i] >= 0) return -1;          // :834: a stereo edge (nothing has been touched yet)
+            const bool right = rig && i >= pFrame->Nleft;             // :875, :901
+            const auto& kp = !rig ? pFrame->mvKeysUn[i] : right ? pFrame->mvKeysRight[i - pFrame->Nleft] : pFrame->mvKeys[i];   // :813, :876, :902
+            xy.push_back(kp.pt.x); xy.push_back(kp.pt.y);
+            inv.push_back(pFrame->mvInvLevelSigma2[kp.octave]);       // :820, :887, :913
+            camera.push_back(right ? 1 : 0);
+            const auto Xw = pMP->GetWorldPos();                       // :828, :895, :921
+            pos.push_back(Xw(0)); pos.push_back(Xw(1)); pos.push_back(Xw(2));
+            index.push_back(i);
+        }
+    }
+    for (int i : index) pFrame->mvbOutlier[i] = false;                // :810, :878, :907
+    const int nInitialCorrespondences = (int)index.size();            // :809, :871
+    if (nInitialCorrespondences < 3) return 0;                        // :936-937
+    const auto Tcw = pFrame->GetPose();                               // :774
+    typedef typename std::decay<decltype(Tcw)>::type SE3T;
+    typedef typename std::decay<decltype(Tcw.unit_quaternion())>::type QuatT;
+    typedef typename std::decay<decltype(Tcw.translation())>::type VecT;
+    {
+        const auto& q = Tcw.unit_quaternion();
+        const auto& t = Tcw.translation();
+        p.q[0] = q.x(); p.q[1] = q.y(); p.q[2] = q.z(); p.q[3] = q.w();
+        p.t[0] = t(0); p.t[1] = t(1); p.t[2] = t(2);
+    }
+    if (rig) {                                                        // :923-924
+        const auto Trl = pFrame->GetRelativePoseTrl();
+        const auto& q = Trl.unit_quaternion();
+        const auto& t = Trl.translation();
+        p.q_rl[0] = q.x(); p.q_rl[1] = q.y(); p.q_rl[2] = q.z(); p.q_rl[3] = q.w();
+        p.t_rl[0] = t(0); p.t_rl[1] = t(1); p.t_rl[2] = t(2);
+    }
+    p.n = nInitialCorrespondences;
+    msorb_pose_result r;
+    out.assign(index.size(), 0);
+    const int off[2] = {0, p.n};
+    if (msorb_pose_optimization_rig_batch(device, 1, &p, off, xy.data(), camera.data(), inv.data(), pos.data(), out.data(), &r, nullptr) != MSORB_OK)
+        fail_call("msorb_pose_optimization_rig_batch");
+    for (size_t k = 0; k < index.size(); k++) pFrame->mvbOutlier[index[k]] = out[k] != 0;
+    pFrame->SetPose(SE3T(QuatT(r.q[3], r.q[0], r.q[1], r.q[2]), VecT(r.t[0], r.t[1], r.t[2])));   // :1033-1035
+    return r.n_initial - r.n_bad;   // :1036
+}
+
+template <class FrameT>
+int PoseOptimizationAnyCamera(FrameT* pFrame) {
+    return PoseOptimizationAnyCamera(pFrame, static_cast<msorb_frame*>(nullptr));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

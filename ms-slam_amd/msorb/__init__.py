@@ -2892,3 +2892,59 @@ def merge_inertial_ba(keyframes, inertial_edges, pos_w, edge_kf, edge_point, xy,
     if timing:
         r["elapsed_ms"] = ms.value
     return r
+
+
+# ---- Optimizer::PoseOptimization of a two-camera or non-pinhole frame on the device (include/msorb.h, appended to ABI 6002)
+EXPORTS = EXPORTS + ("msorb_pose_optimization_rig_capacity", "msorb_pose_optimization_rig_batch")
+
+CAM_PINHOLE, CAM_KANNALA_BRANDT8 = 0, 1                                                          # msorb_camera_model.type
+CAMERA_MODEL_DTYPE = np.dtype([("type", "<i4"), ("p", "<f4", 8)])                                # msorb_camera_model
+POSE_RIG_PROBLEM_DTYPE = np.dtype([("q", "<f4", 4), ("t", "<f4", 3), ("n_cameras", "<i4"), ("cam", CAMERA_MODEL_DTYPE, 2),
+                                   ("q_rl", "<f4", 4), ("t_rl", "<f4", 3), ("n", "<i4")])        # msorb_pose_rig_problem
+assert CAMERA_MODEL_DTYPE.itemsize == 36 and POSE_RIG_PROBLEM_DTYPE.itemsize == 136
+
+
+def _pose_rig_lib():
+    L = lib()
+    L.msorb_pose_optimization_rig_capacity.argtypes = []
+    L.msorb_pose_optimization_rig_batch.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 9
+    return L
+
+
+def pose_optimization_rig_capacity():
+    """observations up to which the rig kernel keeps a problem in registers"""
+    return _pose_rig_lib().msorb_pose_optimization_rig_capacity()
+
+
+def pose_rig_problem(q, t, cameras, q_rl=None, t_rl=None, n=0):
+    """one msorb_pose_rig_problem record; cameras: one or two (type, parameters) pairs (mpCamera, mpCamera2), parameters =
+    mvParameters (4 for a pinhole, 8 for KannalaBrandt8); q_rl, t_rl: GetRelativePoseTrl() of a two-camera frame"""
+    p = np.zeros(1, POSE_RIG_PROBLEM_DTYPE)
+    p["q"], p["t"], p["n"], p["n_cameras"] = np.asarray(q, np.float32), np.asarray(t, np.float32), n, len(cameras)
+    for c, (kind, par) in enumerate(cameras[:2]):
+        par = np.asarray(par, np.float32).reshape(-1)
+        p["cam"][0, c]["type"] = kind
+        p["cam"][0, c]["p"][:len(par)] = par
+    if q_rl is not None:
+        p["q_rl"], p["t_rl"] = np.asarray(q_rl, np.float32), np.asarray(t_rl, np.float32)
+    return p
+
+
+def pose_optimization_rig_batch(problems, xy, camera, inv_sigma2, pos_w, device=0, timing=False):
+    """msorb_pose_optimization_rig_batch: as pose_optimization_batch, with camera [M] (0 = left, 1 = right) in place of u_right.
+    -> (results: POSE_RESULT_DTYPE [n_problems], outlier: bool [M]) and, with timing, the kernel's device time in ms."""
+    L = _pose_rig_lib()
+    pr = _c(problems, POSE_RIG_PROBLEM_DTYPE).reshape(-1)
+    off = np.zeros(len(pr) + 1, np.int32)
+    off[1:] = np.cumsum(pr["n"])
+    m = int(off[-1])
+    arrs = [_c(xy, np.float32).reshape(-1), _c(camera, np.uint8).reshape(-1), _c(inv_sigma2, np.float32).reshape(-1),
+            _c(pos_w, np.float32).reshape(-1)]
+    if [len(a) for a in arrs] != [2 * m, m, m, 3 * m]:
+        raise ValueError("the flat arrays do not hold sum(problems.n) observations")
+    res = np.zeros(len(pr), POSE_RESULT_DTYPE)
+    out = np.zeros(max(m, 1), np.uint8)
+    ms = C.c_float()
+    _check(L.msorb_pose_optimization_rig_batch(device, len(pr), _np_ptr(pr), _np_ptr(off), *[_np_ptr(a) for a in arrs], _np_ptr(out),
+                                               _np_ptr(res), C.addressof(ms)), "msorb_pose_optimization_rig_batch")
+    return (res, out[:m].astype(bool), ms.value) if timing else (res, out[:m].astype(bool))
