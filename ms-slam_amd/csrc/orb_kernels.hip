@@ -386,7 +386,6 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
     __shared__ uint16_t work[GEO::kWorkCap];
     __shared__ int wave_tot[2][T / 64];
     __shared__ uint32_t kbits[kBitWords];
-    __shared__ int kprefix[kBitWords];
     __shared__ uint16_t lut[32];
     __shared__ uint16_t tbase[T];  // per thread: (tile row of its first detection row) << 7 | tile column of its group
     uint8_t* const tile = tile_mem + kTileFront;
@@ -524,7 +523,10 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
                 lw[k] = *reinterpret_cast<const uint32_t*>(colp + (k + 3) * P - 4);
                 rw_[k] = *reinterpret_cast<const uint32_t*>(colp + (k + 3) * P + 4);
             }
+        // (the odd bytes stay where they are, in the high byte of their 16-bit lane, and meet the threshold shifted up to them:
+        // the subtraction that clamps at 0 gives sat0(v - t) << 8 there, so the even and odd halves merge by a plain OR)
         const ushort2v t2 = __builtin_bit_cast(ushort2v, (uint32_t)th * 0x00010001u);
+        const ushort2v t2o = __builtin_bit_cast(ushort2v, ((uint32_t)th << 8) * 0x00010001u);
 #pragma unroll
         for (int k = 0; k < GEO::kMaxR; k++) {
             if (k >= 3 && k >= R) break;  // wave-uniform: the cells of the BASELINE geometries have R = 3 or 4
@@ -532,13 +534,13 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
             const uint32_t R3 = __builtin_amdgcn_alignbyte(rw_[k], V, 3);  // p[x+3] per byte
             const uint32_t L3 = __builtin_amdgcn_alignbyte(V, lw[k], 1);   // p[x-3] per byte
             // A = sat0(v - t), ~B = sat0(~v - t) on the even / odd bytes (16-bit lanes cannot borrow from each other)
-            const uint32_t Ve = V & 0x00ff00ffu, Vo = (V >> 8) & 0x00ff00ffu;
+            const uint32_t Ve = V & 0x00ff00ffu, Vo = V & 0xff00ff00u;
             const uint32_t Ae = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(ushort2v, Ve), t2));
-            const uint32_t Ao = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(ushort2v, Vo), t2));
-            const uint32_t Qd = ~(Ae | (Ao << 8));
+            const uint32_t Ao = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(ushort2v, Vo), t2o));
+            const uint32_t Qd = ~(Ae | Ao);
             const uint32_t Be = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(ushort2v, Ve ^ 0x00ff00ffu), t2));
-            const uint32_t Bo = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(ushort2v, Vo ^ 0x00ff00ffu), t2));
-            const uint32_t Qb = Be | (Bo << 8);
+            const uint32_t Bo = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(ushort2v, Vo ^ 0xff00ff00u), t2o));
+            const uint32_t Qb = Be | Bo;
             const uint32_t one = 0x01010101u;
             // dark: bit 7 SET means "not darker"
             const uint32_t X = (__builtin_amdgcn_lerp(U, Qd, one) & __builtin_amdgcn_lerp(D, Qd, one)) |
@@ -626,46 +628,44 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
             // the popcount of the bits before it (prefix over the bitmap words, one word per thread).
             constexpr int wpr = GEO::kWordsPerRow;  // bitmap words per detection row
             const int nwords = dh * wpr;
-            uint32_t mine_keep = 0;  // per-thread record of the corners it owns: list slots tid, tid + T, ... (cap / T <= 32)
-            {
-                int slot = 0;
-                for (int m0 = 0; m0 < n_corner; m0 += 64, slot++) {
-                    if (m0 + lane >= n_corner) continue;
-                    const int e = work[w_begin + m0 + lane];
-                    const int ty = e >> 7, tx = e & 127;
-                    const uint8_t* q = &score[(int)__umul24((uint32_t)(ty - 2), SP) + tx + sc_off];
-                    const int sv = q[0];
-                    int m = max3i(q[-SP - 1], q[-SP], q[-SP + 1]);
-                    m = max3i(m, q[-1], q[1]);
-                    m = max(m, max3i(q[SP - 1], q[SP], q[SP + 1]));
-                    if (sv > m) {
-                        const int bx = tx - c_lo, by = ty - 3;       // column inside the group span, detection row
-                        const int b = by * (32 * wpr) + bx;
-                        atomicOr(&kbits[b >> 5], 1u << (b & 31));
-                        mine_keep |= 1u << slot;
-                    }
+            for (int m0 = lane; m0 < n_corner; m0 += 64) {
+                const int e = work[w_begin + m0];
+                const int ty = e >> 7, tx = e & 127;
+                const uint8_t* q = &score[(int)__umul24((uint32_t)(ty - 2), SP) + tx + sc_off];
+                const int sv = q[0];
+                int m = max3i(q[-SP - 1], q[-SP], q[-SP + 1]);
+                m = max3i(m, q[-1], q[1]);
+                m = max(m, max3i(q[SP - 1], q[SP], q[SP + 1]));
+                if (sv > m) {
+                    const int bx = tx - c_lo, by = ty - 3;       // column inside the group span, detection row
+                    const int b = by * (32 * wpr) + bx;
+                    atomicOr(&kbits[b >> 5], 1u << (b & 31));
                 }
             }
             __syncthreads();
             const uint32_t myword = tid < nwords ? kbits[tid] : 0u;
             int n_out = 0;
             const int wprefix = block_excl_scan<T / 64>(__popc(myword), lane, wave, wave_tot[1], &n_out);
-            if (tid < nwords) kprefix[tid] = wprefix;
-            __syncthreads();
-            {
-                int slot = 0;
-                for (int m0 = 0; m0 < n_corner; m0 += 64, slot++) {
-                    if (!(mine_keep & (1u << slot))) continue;
-                    const int e = work[w_begin + m0 + lane];
-                    const int ty = e >> 7, tx = e & 127;
-                    const int b = (ty - 3) * (32 * wpr) + (tx - c_lo);
-                    const int rank = kprefix[b >> 5] + __popc(kbits[b >> 5] & ((1u << (b & 31)) - 1u));
+            // The bitmap holds the kept corners in emission order, so its owner emits them: thread tid walks the set bits of word
+            // tid, lowest first; row and column come from the word's index and the bit, the rank of its i-th bit is wprefix + i.
+            // (Nothing writes kbits[] or the score plane before the barrier in front of the next pass's clear_planes().)
+            if (myword) {   // (tid < nwords)
+                // (row and column base depend on the thread id alone; the empty statement keeps them in this branch, as it does for
+                // the saturated path's task range below — the same static check covers both)
+                int tid_here = tid;
+                asm volatile("" : "+v"(tid_here));
+                const int by = tid_here / wpr, bx0 = (tid_here - by * wpr) * 32;
+                const uint8_t* sp = &score[(by + 1) * SP + 4 + bx0];   // score row = detection row + 1, first group at score column 4
+                const int x0 = gx0 + bx0 - kMinBorder, y = cd.y0 + 3 + by - kMinBorder;
+                Cand16* o = out + wprefix;
+                for (uint32_t w = myword; w; w &= w - 1) {
+                    const int j = __builtin_ctz(w);
                     Cand16 c;
-                    c.x = (uint16_t)(ga + tx - kMinBorder);
-                    c.y = (uint16_t)(cd.y0 + ty - kMinBorder);
-                    c.score = score[(int)__umul24((uint32_t)(ty - 2), SP) + tx + sc_off];
+                    c.x = (uint16_t)(x0 + j);
+                    c.y = (uint16_t)y;
+                    c.score = sp[j];
                     c.pad = 0;
-                    out[rank] = c;
+                    *o++ = c;
                 }
             }
             n_emitted = n_out;
@@ -676,7 +676,8 @@ __device__ __forceinline__ void fast_cells_body(const PyramidView& pyr, const Ce
             // (the empty statement ties the task range to this branch: derived from tid alone it is loop-invariant, and the compiler
             // moves its dozen instructions in front of the pass loop, where every cell pays for what a saturated one uses.  It leans
             // on what this compiler does; the check is the static VALU count in front of the kernel's first s_barrier in
-            // `hipcc -S`: 100 for fast_cells_kernel<true, GeoSmall> with it, 114 without)
+            // `hipcc -S`: 101 for fast_cells_kernel<true, GeoSmall> with it and its twin in the emission branch above (110 without
+            // the twin; 100 with, 114 without this one before the emission moved to the bitmap's owner))
             uint32_t tid_here = (uint32_t)tid;
             asm volatile("" : "+v"(tid_here));
             const int t_begin = (int)(__umul24(tid_here, (uint32_t)n_task) / T),
